@@ -10,6 +10,7 @@ GPU at 1/2/4/8); --scaling weak gives every rank its own 16 tiles.  value = SR o
 (max over ranks).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (+ the last timed step's outputs as DIR/*.npy, see dump_outputs)
     python bench.py --gpus N ...          (no torchrun environment: bench.py starts the N ranks itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -41,6 +42,8 @@ CONV_TFLOP_PER_TILE = 36.48  # conv FLOP one 512x512 LR tile nee
 # positions (corners, edges, interior), all inside the un-padded tile so that each has a true HR counterpart
 PARITY_GRID = (0, 6, 13, 19)
 PARITY_IDX = [r * 21 + c for r in PARITY_GRID for c in PARITY_GRID]
+# --dump-outputs: all files together stay below DUMP_MAX_BYTES; the SR images get what the small arrays leave, as a seeded pixel sample
+DUMP_MAX_BYTES, DUMP_SEED = 64_000_000, 0
 
 
 def tile_patches(lr_tile):
@@ -191,6 +194,34 @@ def trained_like_parity(ctx, model_bf16, lr4, hr4, levels=TRAINED_LIKE_LEVELS, l
     return out, w
 
 
+def sample_pixels(n_tiles, h, w, budget_bytes):
+    """Sorted flat pixel indices of an h x w image that --dump-outputs keeps of each of n_tiles fp32 RGB tiles: every pixel if all tiles fit
+    budget_bytes, else the same fixed random subset of every tile (np.random.default_rng(DUMP_SEED)), as many pixels as fit."""
+    k = min(h * w, budget_bytes // (max(n_tiles, 1) * 3 * 4))
+    if k == h * w:
+        return np.arange(h * w)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, k, replace=False))
+
+
+def dump_outputs(path, srs, psnr, ssim, sums):
+    """--dump-outputs: what the caller of the timed step receives, as .npy files under `path`, DUMP_MAX_BYTES at most in all.
+    srs: this rank's SR tiles [H, W, 3] fp32 (device or host tensors, tile order); psnr / ssim: their metrics against HR; sums: the
+    all-reduced (PSNR sum, SSIM sum, tile count).  Writes
+      sr_sample.npy   fp32 [tiles, k, 3]: every tile at the sample_pixels(tiles, H, W, ...) positions (all H * W pixels when they fit)
+      psnr.npy, ssim.npy  fp64 [tiles];  metric_sums.npy  fp64 [3]
+    -> {name: shape} of the files written."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"psnr": np.asarray(psnr, np.float64), "ssim": np.asarray(ssim, np.float64), "metric_sums": np.asarray(sums, np.float64)}
+    if srs:
+        h, w, c = srs[0].shape
+        idx = sample_pixels(len(srs), h, w, DUMP_MAX_BYTES - 4096 - sum(a.nbytes for a in arrays.values()))   # 4 KB: the .npy headers
+        it = torch.from_numpy(idx).to(srs[0].device)
+        arrays["sr_sample"] = torch.stack([s.reshape(h * w, c).index_select(0, it) for s in srs]).float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -303,6 +334,9 @@ def main():
     ap.add_argument("--no-rows", action="store_true", help="skip the other BASELINE rows (cfg3 training step, cfg4 streaming) that the N = 1 line carries beside the headline")
     ap.add_argument("--fused", type=int, default=511,
                     help="dense-block conv pairs run as one fused kernel: bit 0 conv4+conv5, bit 1 conv2+conv3, bit 2 final_conv2 inside final_conv1, bit 3 attention projections inside the producing conv (0 = layer by layer, for A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's SR tiles as a seeded pixel sample, per-tile PSNR / SSIM, the "
+                         "all-reduced metric sums) as DIR/<name>.npy, at most 64 MB in all: inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
     if args.chunk <= 0:
         args.chunk = 441 * max(1, args.tiles_per_call)
@@ -366,6 +400,7 @@ def main():
     sums = torch.zeros(3, dtype=torch.float64, device=ctx.torch_device)
 
     def step():
+        """-> (sums, [(sr tile, psnr, ssim)] of this rank's tiles): what a caller of the path receives."""
         sums.zero_()
         g = max(1, args.tiles_per_call)
         groups = [list(range(t0, min(t0 + g, n_mine))) for t0 in range(0, n_mine, g)]
@@ -382,15 +417,18 @@ def main():
                     srs, _ = mdl.super_resolve_images([lr[t] for t in ts], patch_size_lr=PATCH, stride=STRIDE, batch_size=args.chunk,
                                                       timed=False)
             done.append((ts, srs, st))
+        outs = []
         for ts, srs, st in done:
             if st is not None:
                 cur.wait_stream(st)
             for t, sr in zip(ts, srs):
-                sums[0] += ctx.psnr(hr[t:t + 1], sr[None])[0].double()
-                sums[1] += ctx.ssim(hr[t:t + 1], sr[None])[0].double()
+                p, s = ctx.psnr(hr[t:t + 1], sr[None])[0].double(), ctx.ssim(hr[t:t + 1], sr[None])[0].double()
+                sums[0] += p
+                sums[1] += s
                 sums[2] += 1.0
+                outs.append((sr, p, s))
         D.allreduce_metric_sums(sums)      # RCCL over xGMI: the path's only exchange step
-        return sums
+        return sums, outs
 
     def fence():
         D.barrier()
@@ -418,10 +456,15 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        out = step()
+        last = None          # the previous step's SR tiles go back to the allocator before the next step asks for its own
+        out, last = step()
         marks[i + 1].record()
     fence()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:          # outside the timed region, before the passes below recompute (and overwrite `out`)
+        dumped = dump_outputs(args.dump_outputs, [o[0] for o in last], [float(o[1]) for o in last], [float(o[2]) for o in last], out.cpu().numpy())
+    del last
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
     # the same K steps again with a HIP-event pair around every hot-kernel launch (on the launching stream):
@@ -501,6 +544,8 @@ def main():
                          "tflops": round(r["flops"] / (r["total_ms"] * 1e-3) / 1e12, 2),
                          "gbps": round(r["bytes"] / (r["total_ms"] * 1e-3) / 1e9, 1)} for r in prof[:8]],
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         kept = {}
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(weights, lr4[0], keep=kept)

@@ -147,3 +147,32 @@ def test_pmc_traffic_is_quoted_only_for_the_sources_it_was_collected_on(bench, t
     p.write_text(bench.json.dumps({"dense_tail_fused<bf16,conv4+conv5>": 8.3e9}))          # round 3's file: no fingerprint at all
     assert bench.pmc_traffic("dense_tail_fused<bf16,conv4+conv5>", str(p))[0] is None
     assert bench.pmc_traffic("x", str(tmp_path / "missing.json")) == (None, "no profiles/pmc_traffic.json")
+
+
+def test_dump_outputs_writes_the_step_outputs_as_float_npy_within_the_budget(bench, tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files only; whole tiles while they fit, else the same seeded pixels of every tile; never over the cap."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    srs = [bench.torch.from_numpy(rng.uniform(0, 1, (40, 30, 3)).astype(np.float32)) for _ in range(3)]
+    flat = np.stack([s.numpy().reshape(-1, 3) for s in srs])
+    args = (srs, [20.0, 21.0, 22.0], [0.5, 0.6, 0.7], np.array([63.0, 1.8, 3.0]))
+    shapes = bench.dump_outputs(str(tmp_path / "all"), *args)
+    assert shapes == {"psnr": [3], "ssim": [3], "metric_sums": [3], "sr_sample": [3, 1200, 3]}
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in shapes}
+    assert got["sr_sample"].dtype == np.float32 and np.array_equal(got["sr_sample"], flat)
+    assert all(got[n].dtype == np.float64 for n in ("psnr", "ssim", "metric_sums")) and got["metric_sums"].tolist() == [63.0, 1.8, 3.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 9 * 8 + 3 * 100 * 12)       # room for 100 pixels per tile
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), *args)["sr_sample"] == [3, 100, 3]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= bench.DUMP_MAX_BYTES
+    idx = bench.sample_pixels(3, 40, 30, 3 * 100 * 12)
+    assert len(set(idx.tolist())) == 100 and np.array_equal(np.load(tmp_path / "a" / "sr_sample.npy"), flat[:, idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "sr_sample.npy"), np.load(tmp_path / "b" / "sr_sample.npy"))
+
+
+def test_dump_budget_at_the_bench_size(bench):
+    """16 SR tiles of 2048 x 2048 (the default batch) are sampled to fit 64 MB; a single tile goes whole."""
+    budget = bench.DUMP_MAX_BYTES - 4096
+    k = len(bench.sample_pixels(16, 2048, 2048, budget))
+    assert 0 < k < 2048 * 2048 and 16 * k * 3 * 4 <= budget
+    assert len(bench.sample_pixels(1, 2048, 2048, budget)) == 2048 * 2048
