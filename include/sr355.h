@@ -263,6 +263,29 @@ int  sr_extract_patches(sr_ctx* ctx, const float* img, int H, int W, int C, int 
 int  sr_overlap_add(sr_ctx* ctx, const void* patches, int in_dtype, int H, int W, int C, int patch,
                     int stride, int scale, float mul, float add, float* out, void* stream);
 
+/* ---- the classical study's other four up-scalers (classic_algorithms.py:23-108), 2-D uint8 grayscale, B images of one size ----
+ * sr_back_projection: back_projection (classic_algorithms.py:23-43).  hr_u8 [B,H,W] is the starting estimate (the reference starts
+ *   from its first argument), lr_u8 [B,h,w] the observation, H >= h, W >= w.  Each of `iterations` rounds: diff = float32(lr) -
+ *   resize(est, (w, h), INTER_LINEAR); est += resize(diff, (W, H), INTER_LINEAR), sr_resize's float32 rules (an exact 2x shrink is the
+ *   2 x 2 area mean).  y_u8 [B,H,W] = clip(est, 0, 255) truncated; y_f32 [B,H,W] (may be NULL) receives est before the clip.
+ * sr_noise_sigma: estimate_sigma(x) as non_local_means calls it (classic_algorithms.py:45): median of |dd band of pywt.dwtn(x, 'db2')|
+ *   ('symmetric' mode, 0..255 units) over its non-zero entries / norm.ppf(0.75) -> sigma_f64 [B] (device; NaN when every entry is 0).
+ * sr_nl_means: denoise_nl_means(x / 255, h = h_scale * sigma_f64[b], patch_size = patch (odd, <= 9), patch_distance = distance (<= 12),
+ *   fast_mode=True) (classic_algorithms.py:47-53): y_f32 [B,h,w]; sigma_f64 is read on the device.
+ * sr_edge_guided: edge_guided_interpolation (classic_algorithms.py:64-85): clip(addWeighted(resize_u8(x, (W, H), INTER_LINEAR), 1,
+ *   resize(hypot(Sobel_x, Sobel_y), (W, H)), weight, 0), 0, 255) truncated -> y_u8 [B,H,W]; up_e_f32 [B,H,W] (may be NULL) receives the
+ *   float32 up-sized edge magnitude.  H >= h, W >= w.
+ * sr_freq_extrapolate: frequency_extrapolation (classic_algorithms.py:87-108): |ifft2 of the centred LR spectrum zero-padded to H x W|
+ *   as the separable fp64 map |A_H X A_W^T| -> y_f64 [B,H,W].  H >= h, W >= w. */
+int  sr_back_projection(sr_ctx* ctx, const uint8_t* hr_u8, const uint8_t* lr_u8, int B, int H, int W, int h, int w, int iterations,
+                        uint8_t* y_u8, float* y_f32, void* stream);
+int  sr_noise_sigma(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, double* sigma_f64, void* stream);
+int  sr_nl_means(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, int patch, int distance, const double* sigma_f64,
+                 double h_scale, float* y_f32, void* stream);
+int  sr_edge_guided(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, int H, int W, float weight, uint8_t* y_u8,
+                    float* up_e_f32, void* stream);
+int  sr_freq_extrapolate(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, int H, int W, double* y_f64, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ struct sr_ctx {
     struct Arena { void* p = nullptr; size_t cap = 0; };
     Arena attn_kn;                // attention: per-key-group largest key norm (stream-ordered reuse)
     Arena dev_w, dev_b, dev_x;    // sr_conv2d_dev: packed weights / padded bias / padded input of the call in flight (stream-ordered reuse)
+    Arena cls_tab, cls_work, cls_fft;   // classic.hip: tap tables, per-call work buffers, the DFT products' operands (stream-ordered reuse)
+    std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
     struct PackKey {

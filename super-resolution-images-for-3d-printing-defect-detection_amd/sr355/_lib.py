@@ -94,6 +94,11 @@ SIGNATURES = {
     "sr_spectral_l1": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_extract_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _i64, C.POINTER(_i), _vp]),
     "sr_overlap_add": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
+    "sr_back_projection": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_noise_sigma": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sr_nl_means": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp]),
+    "sr_edge_guided": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "sr_freq_extrapolate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

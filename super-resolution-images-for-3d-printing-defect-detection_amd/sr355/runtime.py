@@ -241,6 +241,65 @@ class Context:
         self.check(self.lib.sr_mse(self.h, a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), self.stream()))
         return out
 
+    # ------------------------------------------------------------------ the classical study's other four up-scalers (classic_algorithms.py:23-108)
+    def _gray_batch(self, x, name):
+        _check_tensor(self, x, name, (torch.uint8,))
+        if x.dim() != 3:
+            raise ValueError(f"{name}: expected a [B,h,w] uint8 batch of grayscale images, got shape {tuple(x.shape)}")
+        return x.shape
+
+    def back_projection(self, hr, lr, iterations=10, raw=False):
+        """Iterative back-projection (sr_back_projection): hr [B,H,W] uint8 starting estimate, lr [B,h,w] uint8 -> uint8 [B,H,W]; with
+        raw=True also the float32 estimate before the clip and truncation."""
+        B, H, W = self._gray_batch(hr, "back_projection hr")
+        Bl, h, w = self._gray_batch(lr, "back_projection lr")
+        if Bl != B:
+            raise ValueError("back_projection: hr and lr batches differ in size")
+        y = self.empty((B, H, W), torch.uint8)
+        est = self.empty((B, H, W), torch.float32) if raw else None
+        self.check(self.lib.sr_back_projection(self.h, hr.data_ptr(), lr.data_ptr(), B, H, W, h, w, int(iterations), y.data_ptr(),
+                                               None if est is None else est.data_ptr(), self.stream()))
+        return (y, est) if raw else y
+
+    def noise_sigma(self, x):
+        """skimage estimate_sigma of each [h,w] uint8 image of x [B,h,w] (sr_noise_sigma) -> float64 [B] on the device (NaN: no detail)."""
+        B, h, w = self._gray_batch(x, "noise_sigma input")
+        sigma = self.empty((B,), torch.float64)
+        self.check(self.lib.sr_noise_sigma(self.h, x.data_ptr(), B, h, w, sigma.data_ptr(), self.stream()))
+        return sigma
+
+    def non_local_means(self, lr, H, W, patch_size=5, patch_distance=6, h_scale=1.15, raw=False):
+        """non_local_means (classic_algorithms.py:45-62) on lr [B,h,w] uint8: sigma, fast NL-means with h = h_scale * sigma, then
+        INTER_LANCZOS4 to (H, W) -> float32 [B,H,W]; raw=True -> (that, the denoised [B,h,w], sigma [B]).  A sigma that is zero or not
+        finite (an image without detail: the reference divides by zero there) raises ValueError -- checking it waits for the device."""
+        B, h, w = self._gray_batch(lr, "non_local_means input")
+        sigma = self.noise_sigma(lr)
+        bad = ~torch.isfinite(sigma) | (sigma <= 0)
+        if bool(bad.any()):
+            raise ValueError(f"non_local_means: the noise estimate of image(s) {torch.nonzero(bad).flatten().tolist()} is zero or not finite "
+                             "(an image without detail); the reference would divide by zero")
+        den = self.empty((B, h, w), torch.float32)
+        self.check(self.lib.sr_nl_means(self.h, lr.data_ptr(), B, h, w, int(patch_size), int(patch_distance), sigma.data_ptr(), float(h_scale),
+                                        den.data_ptr(), self.stream()))
+        up = self.resize(den.unsqueeze(-1), int(H), int(W), "INTER_LANCZOS4").squeeze(-1)
+        return (up, den, sigma) if raw else up
+
+    def edge_guided(self, x, H, W, weight=0.3, raw=False):
+        """edge_guided_interpolation (sr_edge_guided) on x [B,h,w] uint8 -> uint8 [B,H,W]; raw=True -> (that, the float32 up-sized edges)."""
+        B, h, w = self._gray_batch(x, "edge_guided input")
+        y = self.empty((B, H, W), torch.uint8)
+        up_e = self.empty((B, H, W), torch.float32) if raw else None
+        self.check(self.lib.sr_edge_guided(self.h, x.data_ptr(), B, h, w, int(H), int(W), float(weight), y.data_ptr(),
+                                           None if up_e is None else up_e.data_ptr(), self.stream()))
+        return (y, up_e) if raw else y
+
+    def freq_extrapolate(self, x, H, W):
+        """frequency_extrapolation (sr_freq_extrapolate) on x [B,h,w] uint8 -> float64 [B,H,W]."""
+        B, h, w = self._gray_batch(x, "freq_extrapolate input")
+        y = self.empty((B, H, W), torch.float64)
+        self.check(self.lib.sr_freq_extrapolate(self.h, x.data_ptr(), B, h, w, int(H), int(W), y.data_ptr(), self.stream()))
+        return y
+
     # ------------------------------------------------------------------ channel-range views (the training tape's dense blocks: sr_*_views)
     @staticmethod
     def _view(t, coff, c):
