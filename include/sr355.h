@@ -110,6 +110,10 @@ int64_t sr_debug_stamp_bytes_needed(int which, int64_t workgroups);
  * mask 0 = layer by layer (the A/B switch of the parity tests and of tools/ benchmarks).  max_workgroups > 0 caps the persistent grid (tests: several images per workgroup
  * at small batches); 0 = one workgroup per CU. */
 int  sr_debug_set_fused(sr_ctx* ctx, int mask, int max_workgroups);
+/* The bits of sr_debug_set_fused's mask, as described above.  SR_FUSE_TWO_UP: the bits the two-up packing of 24-pixel-wide images needs. */
+enum { SR_FUSE_DENSE_TAIL = 1, SR_FUSE_DENSE_MID = 2, SR_FUSE_RGB_TAIL = 4, SR_FUSE_ATTN_PROJ = 8, SR_FUSE_CELLS = 16, SR_FUSE_CONV1_STREAM = 32,
+       SR_FUSE_POOL = 64, SR_FUSE_CONV_STREAM = 128, SR_FUSE_SRCNN_1X1 = 256, SR_FUSE_ALL = 511,
+       SR_FUSE_TWO_UP = SR_FUSE_DENSE_TAIL | SR_FUSE_DENSE_MID | SR_FUSE_CONV1_STREAM };
 /* Test hook: device allocations through this ctx fail (SR_ERR_OOM) once the bytes it holds would exceed `bytes`
  * (0 = no cap).  Lets the tests walk the out-of-memory path of sr_forward without filling a 288 GB card. */
 int  sr_debug_set_alloc_cap(sr_ctx* ctx, int64_t bytes);

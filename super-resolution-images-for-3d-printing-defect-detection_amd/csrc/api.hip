@@ -155,8 +155,7 @@ struct sr_model {
     bool finalized = false;
     std::vector<size_t> bufcap;       // bytes currently allocated per workspace buffer (grow-only)
     std::vector<CellGrid> grid_now;   // per workspace buffer: the packed layout its contents have now (gx = 0: plain NHWC)
-    CellGrid cat_grid;                // ESRGAN generator: the cell grid the dense blocks' concat buffers hold now (sr_forward `cellpack`; gx = 0: none / unknown)
-    int cat_dirty = -1;               // ... except this one, which trunk_conv's unpacked input was written to
+    std::vector<int> routes;          // per op: how the current forward computes it (sr_forward: its OpKind, or a Route)
     struct Tap { float* dst; int64_t cap; };
     std::unordered_map<int, Tap> taps; // diagnostic: op index -> device fp32 destination (sr_model_set_tap)
     std::vector<std::string> op_names; // per op, for sr_model_op_info
@@ -165,7 +164,9 @@ struct sr_model {
         for (size_t i = 0; i < params.size(); ++i) if (params[i].which == which && params[i].name == n) return (int)i;
         return -1;
     }
-    void free_bufs() { for (auto& p : bufp) { if (p) ctx->dfree(p); p = nullptr; } bufcap.assign(bufcap.size(), 0); grid_now.assign(grid_now.size(), CellGrid{}); cat_grid = CellGrid{}; cat_dirty = -1; }
+    void free_bufs() { for (auto& p : bufp) { if (p) ctx->dfree(p); p = nullptr; } bufcap.assign(bufcap.size(), 0); grid_now.assign(grid_now.size(), CellGrid{}); }
+    // a channel range of a workspace buffer (buf < 0: none)
+    TensorView view(const Ref& r) const { return r.buf >= 0 ? TensorView{bufp[r.buf], bufs[r.buf].Cbuf, r.coff, bufs[r.buf].blk} : TensorView{}; }
 };
 
 namespace {
@@ -228,7 +229,7 @@ int build_srcnn(sr_model* m) {
     b.conv("conv2d_1", 1, 96, 32, {c1, 0}, {c2, 0}, SR_ACT_RELU);
     if (m->T == SR_DTYPE_F32 && C == 3) {
         // the 96-channel intermediate must never reach HBM -- the head's epilogue computes this 1x1 from its accumulators
-        // (conv.hip, conv_thin_kernel PW2); sr_forward decides per call (a tap on conv2d, or sr_debug_set_fused without bit 8, runs the two convs)
+        // (conv.hip, conv_thin_kernel PW2); sr_forward decides per call (a tap on conv2d, or a mask without SR_FUSE_SRCNN_1X1, runs the two convs)
         Pw2Spec ps; ps.conv = m->ops.back().conv; ps.act = SR_ACT_RELU;
         m->pw2s.push_back(ps);
         m->ops[m->ops.size() - 2].pw2 = (int)m->pw2s.size() - 1;
@@ -290,8 +291,7 @@ int build_esrgan(sr_model* m) {
     // kernel): keep them row-blocked so that a 32-channel chunk of a tile row is one contiguous run of whole 128-byte lines.
     // (round 4: any growth width whose concat tensor is a whole number of 32-channel blocks -- the reference's notebook trains G = 8: 96 channels; a growth conv's
     //  output slice then starts inside a block, which the epilogue's per-lane addressing places)
-    static const bool blk_g32_only = getenv("SR355_BLOCKED_G32_ONLY") != nullptr;       // A/B switch (diagnostic)
-    if (m->T == SR_DTYPE_BF16 && (G % 32 == 0 || (G % 8 == 0 && !blk_g32_only)))
+    if (m->T == SR_DTYPE_BF16 && G % 8 == 0)
         for (int i = 0; i < 3; ++i) m->bufs[cat[i]].blk = 1;
     for (int i = 0; i < 3; ++i) m->bufs[cat[i]].cat = 1;
     Op cv; cv.kind = OP_CONVERT; cv.out = {x0, 0}; m->ops.push_back(cv);
@@ -357,7 +357,7 @@ int build_esrgan(sr_model* m) {
     b.conv("final_conv2", 3, 64, C, {f1, 0}, {-2, 0}, SR_ACT_TANH);
     if (m->T == SR_DTYPE_BF16 && C <= 3) {
         // final_conv2 can ride in final_conv1's epilogue (conv_rows.hip, rows_fuse2): the 64-channel image at the output resolution is
-        // then never written; sr_forward decides per call (a tap on final_conv1, or sr_debug_set_fused without bit 2, runs the two convs)
+        // then never written; sr_forward decides per call (a tap on final_conv1, or a mask without SR_FUSE_RGB_TAIL, runs the two convs)
         RgbTailSpec rt; rt.conv_b = m->ops.back().conv;
         m->rgbtails.push_back(rt);
         m->ops[m->ops.size() - 2].rgbtail = (int)m->rgbtails.size() - 1;
@@ -471,11 +471,6 @@ inline void buf_hw(const BufSpec& b, int H, int W, int* h, int* w) {
     for (int i = 0; i < b.cshift; ++i) { *h = (*h + 1) / 2; *w = (*w + 1) / 2; }
 }
 
-// Workspaces grow on demand and are never shrunk.  Every buffer is [pixels][Cbuf]: the position of the pad
-// channels inside a pixel does not depend on (B,H,W), so zeroing them once at allocation stays valid for every
-// later shape (no kernel ever writes a pad channel).
-// On an allocation failure every workspace buffer is released (after a device sync: earlier forwards may still be running on
-// them) so that a retry with a smaller batch starts from a clean slate instead of from the half-grown oversized set.
 // The packed layout of B images of h x w pixels (CellGrid, common.h), or gx = 0 where packing does not pay: the 64-cout kernel issues MFMAs for
 // 12 x 16 output tiles, so a plain image uses h w / (ceil(h / 12) 12 ceil(w / 16) 16) of them and the grid (h / (h + 1)) (gx w / 16).
 CellGrid cell_grid_for(int B, int h, int w, int Cbuf) {
@@ -491,8 +486,60 @@ CellGrid cell_grid_for(int B, int h, int w, int Cbuf) {
     return g;
 }
 
-// use_cells: buffers marked `cells` adopt the packed layout for this forward where it pays (never with taps set: the tap copy reads plain NHWC)
-int ensure_workspace(sr_model* m, int B, int H, int W, hipStream_t st, bool use_cells) {
+// The cell grid of the ESRGAN generator's concat buffers (Cmax channels per pixel) for B images of H x W, or gx = 0 where it does not pay.  Cell packing
+// for the dense blocks on the TILE kernels (round 4): where the fused kernels do not apply (another growth width than 32, another width than 48 / two-up 24)
+// and the images fill the 16 x 16 output tiles badly -- 24 x 24: 56 % -- the concat buffers hold the batch as one image of gx cells per row, (H + 1) x (W + 1)
+// pixels each with a zero separator row / column: 92 % at 24 x 24.  From the trunk's first concat buffer to trunk_conv's input, as the two-up packing; the
+// convs run on ONE tall image and never store a separator.
+CellGrid cat_grid_for(int B, int H, int W, int Cmax) {
+    CellGrid g;
+    if (B < 4 || H < 2 || W < 2) return g;
+    const double plain = (double)H * W / ((double)((H + 15) / 16 * 16) * ((W + 15) / 16 * 16));
+    const int gx = B < 16 ? B : 16;
+    const int64_t Hv = (int64_t)((B + gx - 1) / gx) * (H + 1), Wv = (int64_t)gx * (W + 1);
+    const double packed = (double)B * H * W / ((double)((Hv + 15) / 16 * 16) * ((Wv + 15) / 16 * 16));
+    if (packed >= 1.15 * plain && Hv * Wv * Cmax < ((int64_t)1 << 31)) { g.gx = gx; g.ch = H + 1; g.cw = W + 1; g.Hv = (int)Hv; g.Wv = (int)Wv; }
+    return g;
+}
+
+// The layouts of one forward, chosen before the workspace is sized (never with taps set, except the two-up packing: the tap copy reads plain NHWC or pairs).
+struct Layout {
+    bool pack2 = false;      // the dense blocks hold two 24-pixel-wide images side by side per 48-pixel row
+    CellGrid cat;            // the cell grid of the concat buffers (gx = 0: plain)
+    bool use_cells = false;  // buffers marked `cells` (VGG16 block 5) adopt a CellGrid where it pays
+    int B_ws = 0;            // the batch the workspace is sized for
+};
+
+Layout choose_layout(const sr_model* m, int B, int H, int W) {
+    const int mask = m->ctx->chain_mask;
+    Layout L;
+    L.use_cells = m->taps.empty() && (mask & SR_FUSE_CELLS) != 0;
+    // 24-pixel-wide patches (patch_size_lr = 24: the reference's own training patch, ESRGAN_model.py:858 / constants.py:8) through the fused dense-block kernels, which are
+    // built for 48-pixel rows: two images side by side per row, [ceil(B / 2)][H][C / 32][48][32], from the trunk's first concat buffer to trunk_conv's input; the kernels
+    // treat columns 23 | 24 as an image border (dense_fused.hip SEAM).  Needs all three fused dense-block kernels; taps read the packed buffers through tap_copy's pair mapping.
+    L.pack2 = m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && W == 24 && (mask & SR_FUSE_TWO_UP) == SR_FUSE_TWO_UP && !m->chains.empty() && B >= 2;
+    for (const auto& tp : m->taps) {                                          // a tap on a tail pair's first conv makes that pair run layer by layer, which the packed layout cannot
+        const Op& to = m->ops[tp.first];
+        if (to.kind == OP_CONV && to.chain >= 0 && m->chains[to.chain].tail && to.chain_pos == 0) L.pack2 = false;
+    }
+    bool cat_blk = false; int Cmax = 0;
+    for (const BufSpec& bs : m->bufs) if (bs.cat) { cat_blk = cat_blk || bs.blk; Cmax = std::max(Cmax, bs.Cbuf); }
+    const bool fused_here = !m->chains.empty() && W == 48 && (mask & (SR_FUSE_DENSE_TAIL | SR_FUSE_DENSE_MID));
+    if (m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && cat_blk && !L.pack2 && !fused_here && m->taps.empty()) L.cat = cat_grid_for(B, H, W, Cmax);
+    L.B_ws = L.pack2 ? (B + 1) & ~1 : L.cat.gx ? (int)std::max<int64_t>(B, ((int64_t)L.cat.Hv * L.cat.Wv + (int64_t)H * W - 1) / ((int64_t)H * W)) : B;
+    return L;
+}
+
+// Workspaces grow on demand and are never shrunk.  Every buffer is [pixels][Cbuf]: the position of the pad
+// channels inside a pixel does not depend on (B,H,W), so zeroing them once at allocation stays valid for every
+// later shape (no kernel ever writes a pad channel).
+// On an allocation failure every workspace buffer is released (after a device sync: earlier forwards may still be running on
+// them) so that a retry with a smaller batch starts from a clean slate instead of from the half-grown oversized set.
+// Sizes the workspace for L.B_ws images of H x W and gives the `cat` and `cells` buffers the layout L chose.  A buffer that adopts a packed layout
+// other than the one it holds is cleared: the separators (and the cells no image is written to) must be zeros.  Nothing else has to be: no conv stores a
+// separator, the cells of another batch size on the same grid lie in the same places, and whatever writes a buffer plainly resets its grid_now.
+int ensure_workspace(sr_model* m, const Layout& L, int H, int W, hipStream_t st) {
+    const int B = L.B_ws;
     if (m->bufp.size() != m->bufs.size()) { m->bufp.assign(m->bufs.size(), nullptr); m->bufcap.assign(m->bufs.size(), 0); m->grid_now.assign(m->bufs.size(), CellGrid{}); }
     for (size_t i = 0; i < m->bufs.size(); ++i) {
         const BufSpec& b = m->bufs[i];
@@ -502,14 +549,12 @@ int ensure_workspace(sr_model* m, int B, int H, int W, hipStream_t st, bool use_
         else {
             int h, w; buf_hw(b, H, W, &h, &w);
             bytes = (size_t)B * h * w * b.Cbuf * dtype_size(m->T) + 4096;
-            if (b.cells && use_cells) {
-                want = cell_grid_for(B, h, w, b.Cbuf);
-                if (want.gx) bytes = std::max(bytes, (size_t)want.Hv * want.Wv * b.Cbuf * dtype_size(m->T) + 4096);
-            }
+            if (b.cat) want = L.cat;
+            else if (b.cells && L.use_cells) want = cell_grid_for(B, h, w, b.Cbuf);
+            if (want.gx) bytes = std::max(bytes, (size_t)want.Hv * want.Wv * b.Cbuf * dtype_size(m->T) + 4096);
         }
         if (bytes <= m->bufcap[i]) {
-            // the separators of a packed layout must be zeros: adopting one over other contents (a plain forward, another grid) clears the buffer
-            const CellGrid& have = m->grid_now[i];                  // (the cells of another batch size lie in the same places: nothing to clear)
+            const CellGrid& have = m->grid_now[i];
             if (want.gx && !(have.gx == want.gx && have.ch == want.ch && have.cw == want.cw && have.Wv == want.Wv)) SR_HIP(m->ctx, hipMemsetAsync(m->bufp[i], 0, m->bufcap[i], st));
             m->grid_now[i] = want;
             continue;
@@ -528,6 +573,74 @@ int ensure_workspace(sr_model* m, int B, int H, int W, hipStream_t st, bool use_
         m->bufcap[i] = bytes;
     }
     return SR_OK;
+}
+
+// ---- the route of every op in one forward: its own kind (OP_CONV: a conv, possibly with the next op in its epilogue), or a fused route --------
+// (CHAIN: a dense-block pair as one kernel, launched at its first conv; CHAIN_SECOND: that pair's second conv; IN_EPILOGUE: computed by the conv in front of it)
+enum Route { RT_CHAIN = OP_PREPROC + 1, RT_CHAIN_SECOND, RT_CONV1_STREAM, RT_RGB_TAIL, RT_PW2, RT_IN_EPILOGUE };
+
+bool tapped(const sr_model* m, size_t oi) { return !m->taps.empty() && m->taps.count((int)oi) != 0; }
+// no skips, no clip, no depth_to_space
+bool bare_epilogue(const Op& op) { return op.skip1.buf < 0 && op.skip2.buf < 0 && op.d2s == 1 && !op.clip; }
+
+// the first conv of a dense-block pair: both as one kernel.  A tap on a tail pair's first conv (conv4) needs that conv's output in memory, which the
+// fused kernel keeps in its LDS ring: such a pair runs layer by layer (the tap used to return stale workspace bytes without an error)
+bool chain_fits(const sr_model* m, size_t oi, int w, bool pack2) {
+    const Op& op = m->ops[oi];
+    if (op.chain < 0 || op.chain_pos != 0) return false;
+    const ChainSpec& ch = m->chains[op.chain];
+    return !(ch.tail && tapped(m, oi)) && (m->ctx->chain_mask & (ch.tail ? SR_FUSE_DENSE_TAIL : SR_FUSE_DENSE_MID)) && chain_supported(ch.w, m->view(op.in), pack2 ? 48 : w);
+}
+// conv1 of a dense block (64 -> 32 channels into its own buffer) on the streaming kernel
+bool conv1_stream_fits(const sr_model* m, const Op& op, int w, bool pack2) {
+    return (m->ctx->chain_mask & SR_FUSE_CONV1_STREAM) && op.chain < 0 && op.act == SR_ACT_RELU && op.alpha == 1.f && bare_epilogue(op) && op.out.buf == op.in.buf &&
+           op.in.coff == 0 && op.out.coff == 64 && conv1_stream_supported(m->convs[op.conv].w, m->view(op.in), pack2 ? 48 : w);
+}
+// final_conv1 + final_conv2 as one kernel and a finishing pass; the partial sums live in the buffer final_conv1's output would have taken
+// (a tile's 3 KiB against the 24 KiB of its 64-channel pixels)
+bool rgb_tail_fits(const sr_model* m, const Op& op, size_t oi, int B, int h, int w) {
+    const ConvWeights& cw = m->convs[op.conv].w;
+    return op.rgbtail >= 0 && (m->ctx->chain_mask & SR_FUSE_RGB_TAIL) && !tapped(m, oi) && cw.rows && cw.NT == 4 && cw.Cout == 64 && bare_epilogue(op) &&
+           op.act != SR_ACT_TANH && op.out.buf >= 0 && (int64_t)m->bufcap[op.out.buf] >= rgbtail_partial_bytes(B, h, w);
+}
+// conv2d (9x9, ReLU) + conv2d_1 (1x1, ReLU) as one kernel: only the 32-channel tensor is stored
+bool pw2_fits(const sr_model* m, const Op& op, size_t oi) {
+    const ConvWeights& cw = m->convs[op.conv].w;
+    return op.pw2 >= 0 && (m->ctx->chain_mask & SR_FUSE_SRCNN_1X1) && !tapped(m, oi) && cw.thin && !cw.few && cw.dtype == SR_DTYPE_F32 && bare_epilogue(op);
+}
+// conv -> MaxPooling2D (every VGG16 block ends so): the pool rides in the conv's epilogue, the full-resolution tensor is never stored
+bool pool_fits(const sr_model* m, const Op& op, size_t oi, int h, int w) {
+    if (oi + 1 >= m->ops.size() || op.out.buf < 0) return false;
+    const Op& pl = m->ops[oi + 1];
+    const ConvWeights& cw = m->convs[op.conv].w;
+    return (m->ctx->chain_mask & SR_FUSE_POOL) && m->T == SR_DTYPE_BF16 && pl.kind == OP_POOL && pl.in.buf == op.out.buf && pl.out.buf >= 0 && cw.rows && cw.NT == 4 &&
+           cw.CoutP == cw.Cout && bare_epilogue(op) && op.act != SR_ACT_TANH && !tapped(m, oi) && !m->grid_now[op.in.buf].gx && !m->grid_now[op.out.buf].gx &&
+           h >= 2 && w >= 2 && m->bufs[pl.out.buf].Cbuf % 8 == 0 && m->bufs[pl.out.buf].Cbuf >= cw.Cout;
+}
+// the SelfAttention layer that follows opens with three 1x1 convs of this conv's output: computed in its epilogue, from registers
+bool proj_fits(const sr_model* m, const Op& op) {
+    const ConvWeights& cw = m->convs[op.conv].w;
+    return op.proj >= 0 && (m->ctx->chain_mask & SR_FUSE_ATTN_PROJ) && cw.rows && cw.NT == 4 && cw.Cout / (op.d2s * op.d2s) == 64 && cw.CoutP == cw.Cout &&
+           op.out.buf >= 0 && !m->bufs[op.out.buf].blk && op.skip2.buf < 0 && !op.clip && op.act != SR_ACT_TANH && m->bufs[op.out.buf].Cbuf % 4 == 0;
+}
+
+// After ensure_workspace (the RGB tail's check reads bufcap, the pool's grid_now): m->routes.  Precedence: a fused pair, conv1's streaming kernel, (the
+// input unpack of trunk_conv, at launch), the RGB tail, SRCNN's fused 1x1, else the conv -- with a max-pool or projection behind it in its epilogue where that fits.
+void plan_routes(sr_model* m, const Layout& L, int B, int H, int W) {
+    std::vector<int>& rt = m->routes;
+    rt.resize(m->ops.size());
+    for (size_t oi = 0; oi < m->ops.size(); ++oi) rt[oi] = m->ops[oi].kind;
+    for (size_t oi = 0; oi < m->ops.size(); ++oi) {
+        const Op& op = m->ops[oi];
+        if (rt[oi] != OP_CONV) continue;                                      // not a conv, or one the conv in front of it has taken
+        int h, w;
+        buf_hw(m->bufs[op.in.buf], H, W, &h, &w);
+        if (chain_fits(m, oi, w, L.pack2)) { rt[oi] = RT_CHAIN; rt[oi + 1] = RT_CHAIN_SECOND; }
+        else if (conv1_stream_fits(m, op, w, L.pack2)) rt[oi] = RT_CONV1_STREAM;
+        else if (rgb_tail_fits(m, op, oi, B, h, w)) { rt[oi] = RT_RGB_TAIL; rt[oi + 1] = RT_IN_EPILOGUE; }
+        else if (pw2_fits(m, op, oi)) { rt[oi] = RT_PW2; rt[oi + 1] = RT_IN_EPILOGUE; }
+        else if (pool_fits(m, op, oi, h, w) || proj_fits(m, op)) rt[oi + 1] = RT_IN_EPILOGUE;
+    }
 }
 
 }  // namespace
@@ -887,245 +1000,132 @@ int sr_forward(sr_model* m, const void* x, int io_dtype, int B, int H, int W, in
     if (y_capacity < os[0] * os[1] * os[2] * os[3]) return ctx->fail(SR_ERR_CAPACITY, "output buffer too small");
     if (m->kind == SR_MODEL_VGG16 && (H < 32 || W < 32)) return ctx->fail(SR_ERR_INVALID, "VGG16 needs H,W >= 32");
     if (m->kind == SR_MODEL_VGG19_FEATURES && (H < 16 || W < 16)) return ctx->fail(SR_ERR_INVALID, "VGG19 features need H,W >= 16");
-    const bool use_cells = m->taps.empty() && (ctx->chain_mask & 16) != 0;
-    // 24-pixel-wide patches (patch_size_lr = 24: the reference's own training patch, ESRGAN_model.py:858 / constants.py:8) through the fused dense-block kernels, which are
-    // built for 48-pixel rows: two images side by side per row, [ceil(B / 2)][H][C / 32][48][32], from the trunk's first concat buffer to trunk_conv's input; the kernels
-    // treat columns 23 | 24 as an image border (dense_fused.hip SEAM).  Needs all three fused dense-block kernels (mask bits 0, 1, 5); taps read the packed buffers through tap_copy's pair mapping.
-    bool pack2 = m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && W == 24 && (ctx->chain_mask & 35) == 35 && !m->chains.empty() && B >= 2;
-    for (const auto& tp : m->taps) {                                          // a tap on a tail pair's first conv makes that pair run layer by layer (below), which the packed layout cannot
-        const Op& to = m->ops[tp.first];
-        if (to.kind == OP_CONV && to.chain >= 0 && m->chains[to.chain].tail && to.chain_pos == 0) pack2 = false;
-    }
-    // Cell packing for the dense blocks on the TILE kernels (round 4): where the fused kernels do not apply (another growth width than 32, another width than 48 / two-up 24) and the
-    // images fill the 16 x 16 output tiles badly -- 24 x 24: 56 % -- the concat buffers hold the batch as one image of gx cells per row, (H + 1) x (W + 1) pixels each with a zero
-    // separator row / column (CellGrid): 92 % at 24 x 24.  From the trunk's first concat buffer to trunk_conv's input, as the two-up packing; the convs run on ONE tall image and never
-    // store a separator.
-    CellGrid cp;
-    {
-        static const bool no_cellpack = getenv("SR355_NO_CELLPACK") != nullptr;      // A/B switch (diagnostic)
-        bool cat_blk = false;
-        for (const BufSpec& bs : m->bufs) if (bs.cat && bs.blk) cat_blk = true;
-        const bool fused_here = !m->chains.empty() && W == 48 && (ctx->chain_mask & 3);
-        if (m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && cat_blk && !pack2 && !fused_here && m->taps.empty() && !no_cellpack && B >= 4 && H >= 2 && W >= 2) {
-            const double plain = (double)H * W / ((double)((H + 15) / 16 * 16) * ((W + 15) / 16 * 16));
-            const int gx = B < 16 ? B : 16;
-            const int64_t Hv = (int64_t)((B + gx - 1) / gx) * (H + 1), Wv = (int64_t)gx * (W + 1);
-            const double packed = (double)B * H * W / ((double)((Hv + 15) / 16 * 16) * ((Wv + 15) / 16 * 16));
-            int Cmax = 0;
-            for (const BufSpec& bs : m->bufs) if (bs.cat) Cmax = std::max(Cmax, bs.Cbuf);
-            if (packed >= 1.15 * plain && Hv * Wv * Cmax < ((int64_t)1 << 31)) { cp.gx = gx; cp.ch = H + 1; cp.cw = W + 1; cp.Hv = (int)Hv; cp.Wv = (int)Wv; }
-        }
-    }
-    const int B_ws = pack2 ? (B + 1) & ~1 : cp.gx ? (int)std::max<int64_t>(B, ((int64_t)cp.Hv * cp.Wv + (int64_t)H * W - 1) / ((int64_t)H * W)) : B;
-    int rc = ensure_workspace(m, B_ws, H, W, st, use_cells);
+    const Layout L = choose_layout(m, B, H, W);
+    int rc = ensure_workspace(m, L, H, W, st);
     if (rc) return rc;
-    if (cp.gx) {
-        // separators (and cells no image has been written to) must be zeros: adopting the grid over other contents clears the buffers; with the grid already in place
-        // only the buffer the last forward unpacked trunk_conv's input into
-        const bool all = !(m->cat_grid == cp);
-        for (size_t i = 0; i < m->bufs.size(); ++i)
-            if (m->bufs[i].cat && (all || (int)i == m->cat_dirty)) SR_HIP(ctx, hipMemsetAsync(m->bufp[i], 0, m->bufcap[i], st));
-        m->cat_grid = cp;
-        m->cat_dirty = -1;
-    } else {
-        m->cat_grid = CellGrid{};                                             // a plain or two-up forward writes where the separators were
-        m->cat_dirty = -1;
-    }
+    plan_routes(m, L, B, H, W);
     SR_HIP(ctx, hipEventRecord(ctx->ev0, st));
     const int T = m->T;
-    int proj_done = -1;                                                       // index of a 1x1 projection op the previous conv's epilogue has already computed
-    int pool_done = -1;                                                       // index of a max-pool op the previous conv's epilogue has already computed
     for (size_t oi = 0; oi < m->ops.size(); ++oi) {
         const Op& op = m->ops[oi];
+        const int route = m->routes[oi];
+        const Op* nx = oi + 1 < m->ops.size() && m->routes[oi + 1] == RT_IN_EPILOGUE ? &m->ops[oi + 1] : nullptr;   // computed in this op's epilogue
         int h = H, w = W;
         if (op.in.buf >= 0) buf_hw(m->bufs[op.in.buf], H, W, &h, &w);
-        switch (op.kind) {
-            case OP_CONVERT:
-                rc = convert_pad_launch(ctx, x, io_dtype, (int64_t)B * H * W, C, m->bufp[op.out.buf], T, m->bufs[op.out.buf].Cbuf, 1.f, 0.f, st);
+        const TensorView vi = m->view(op.in), vo = m->view(op.out);
+        void* const po = op.out.buf >= 0 ? m->bufp[op.out.buf] : nullptr;
+        switch (route) {
+            case RT_CHAIN_SECOND: case RT_IN_EPILOGUE:                        // launched with the op in front of it (a tap reads its output below)
                 break;
-            case OP_CONV: {
-                const ConvSpec& cs = m->convs[op.conv];
-                if ((int)oi == proj_done) break;                              // computed by the producing conv (its output buffer holds the result; a tap reads it below)
-                TensorView xin{m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, m->bufs[op.in.buf].blk};
-                if (op.chain >= 0) {
-                    const ChainSpec& ch = m->chains[op.chain];
-                    // a tap on the tail pair's first conv (conv4) needs that conv's output in memory: the fused kernel keeps it in its LDS
-                    // ring, so such a pair runs layer by layer (the tap used to return stale workspace bytes without an error)
-                    const size_t first = op.chain_pos == 0 ? oi : oi - 1;
-                    const bool tapped_inner = ch.tail && !m->taps.empty() && m->taps.count((int)first) != 0;
-                    if (!tapped_inner && (ctx->chain_mask & (ch.tail ? 1 : 2)) && chain_supported(ch.w, xin, pack2 ? 48 : w)) {
-                        if (op.chain_pos == 0) {                  // the pair runs as one kernel, launched at its first op
-                            const Op& ob = m->ops[oi + 1];
-                            auto view = [&](const Ref& r) { return r.buf >= 0 ? TensorView{m->bufp[r.buf], m->bufs[r.buf].Cbuf, r.coff, m->bufs[r.buf].blk} : TensorView{}; };
-                            TensorView outv{}, so{};
-                            float bx = 0.f, bo = 0.f;
-                            if (ch.tail) {
-                                outv = view(ob.out);
-                                for (int k2 = 0; k2 < 2; ++k2) {   // which skip is the block's own input x, which the other tensor
-                                    const Ref& r = k2 ? ob.skip2 : ob.skip1;
-                                    const float be = k2 ? ob.beta2 : ob.beta1;
-                                    if (r.buf < 0) continue;
-                                    if (r.buf == op.in.buf && r.coff == 0) bx = be; else { so = view(r); bo = be; }
-                                }
-                            }
-                            rc = pack2 ? chain_launch(ctx, ch.w, xin, (B + 1) / 2, h, 48, outv, so, ob.alpha, bx, bo, st, true)
-                                       : chain_launch(ctx, ch.w, xin, B, h, w, outv, so, ob.alpha, bx, bo, st);
-                        }
-                        break;
+            case RT_CHAIN: {
+                const ChainSpec& ch = m->chains[op.chain];
+                const Op& ob = m->ops[oi + 1];
+                TensorView outv{}, so{};
+                float bx = 0.f, bo = 0.f;
+                if (ch.tail) {
+                    outv = m->view(ob.out);
+                    for (int k2 = 0; k2 < 2; ++k2) {   // which skip is the block's own input x, which the other tensor
+                        const Ref& r = k2 ? ob.skip2 : ob.skip1;
+                        const float be = k2 ? ob.beta2 : ob.beta1;
+                        if (r.buf < 0) continue;
+                        if (r.buf == op.in.buf && r.coff == 0) bx = be; else { so = m->view(r); bo = be; }
                     }
                 }
-                if ((ctx->chain_mask & 32) && op.chain < 0 && op.act == SR_ACT_RELU && op.alpha == 1.f && op.skip1.buf < 0 && op.skip2.buf < 0 && op.d2s == 1 && !op.clip &&
-                    op.out.buf == op.in.buf && op.in.coff == 0 && op.out.coff == 64 && conv1_stream_supported(cs.w, xin, pack2 ? 48 : w)) {
-                    rc = pack2 ? conv1_stream_launch(ctx, cs.w, xin, (B + 1) / 2, h, 48, st, true)
-                               : conv1_stream_launch(ctx, cs.w, xin, B, h, w, st);   // conv1 of a dense block: the streaming kernel
-                    break;
-                }
-                if (cp.gx && op.pack_alt >= 0) {
-                    // trunk_conv: its input is cell-packed -- unpacked into a free concat buffer first (as for the two-up packing below)
-                    rc = cell_unpack_launch(ctx, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, B, h, w, 64, m->bufp[op.pack_alt], m->bufs[op.pack_alt].Cbuf, 0, cp, st);
+                rc = chain_launch(ctx, ch.w, vi, L.pack2 ? (B + 1) / 2 : B, h, L.pack2 ? 48 : w, outv, so, ob.alpha, bx, bo, st, L.pack2);
+                break;
+            }
+            case RT_CONV1_STREAM:
+                rc = conv1_stream_launch(ctx, m->convs[op.conv].w, vi, L.pack2 ? (B + 1) / 2 : B, h, L.pack2 ? 48 : w, st, L.pack2);
+                break;
+            case RT_RGB_TAIL: case RT_PW2: case OP_CONV: {
+                const ConvSpec& cs = m->convs[op.conv];
+                int in = op.in.buf;
+                TensorView xin = vi;
+                if (op.pack_alt >= 0 && (L.pack2 || m->grid_now[in].gx)) {
+                    // trunk_conv: its input, channels [0, 64) of the last dense block's buffer, is packed -- unpacked into a free concat buffer first
+                    void* d = m->bufp[op.pack_alt];
+                    const int64_t dC = m->bufs[op.pack_alt].Cbuf;
+                    const CellGrid& g = m->grid_now[in];
+                    rc = g.gx ? cell_unpack_launch(ctx, vi.p, vi.cs, vi.coff, B, h, w, 64, d, dC, 0, g, st) : unpack_pairs_launch(ctx, vi.p, vi.cs, vi.coff, B, h, w, 64, d, dC, 0, st);
                     if (rc) return rc;
-                    m->cat_dirty = op.pack_alt;                               // that buffer holds a plain image now: the next forward clears it before it packs
-                    xin = TensorView{m->bufp[op.pack_alt], m->bufs[op.pack_alt].Cbuf, 0, m->bufs[op.pack_alt].blk};
-                } else if (cp.gx && m->bufs[op.in.buf].cat && !(op.out.buf >= 0 && m->bufs[op.out.buf].cat)) {
-                    return ctx->fail(SR_ERR_STATE, "cell-packed dense blocks: a conv outside them would read a packed buffer");
-                }
-                if (pack2 && op.pack_alt >= 0) {
-                    // trunk_conv: its input, channels [0, 64) of the last dense block's buffer, is two-up packed -- unpacked into a free concat buffer first
-                    rc = unpack_pairs_launch(ctx, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, B, h, w, 64, m->bufp[op.pack_alt], m->bufs[op.pack_alt].Cbuf, 0, st);
-                    if (rc) return rc;
-                    xin = TensorView{m->bufp[op.pack_alt], m->bufs[op.pack_alt].Cbuf, 0, m->bufs[op.pack_alt].blk};
-                } else if (pack2 && m->bufs[op.in.buf].blk) {
+                    in = op.pack_alt;
+                    m->grid_now[in] = CellGrid{};                             // that buffer holds a plain image now: the next packed forward clears it
+                    xin = m->view({in, 0});
+                } else if (L.pack2 && vi.blk) {
                     return ctx->fail(SR_ERR_STATE, "two-up packed dense blocks: a conv outside the fused kernels would read a packed buffer");
                 }
-                if (op.rgbtail >= 0 && (ctx->chain_mask & 4) && m->taps.count((int)oi) == 0 && cs.w.rows && cs.w.NT == 4 && cs.w.Cout == 64 &&
-                    op.skip1.buf < 0 && op.skip2.buf < 0 && op.d2s == 1 && !op.clip && op.act != SR_ACT_TANH && op.out.buf >= 0 &&
-                    (int64_t)m->bufcap[op.out.buf] >= rgbtail_partial_bytes(B, h, w)) {
-                    // final_conv1 + final_conv2 as one kernel and a finishing pass; the partial sums live in the buffer final_conv1's
-                    // output would have taken (a tile's 3 KiB against the 24 KiB of its 64-channel pixels)
-                    const Op& ob = m->ops[oi + 1];
-                    const RgbTailSpec& rt = m->rgbtails[op.rgbtail];
-                    ConvEpilogue ep1;
-                    ep1.act = op.act; ep1.alpha = op.alpha;
-                    ep1.f2 = &rt.w; ep1.f2_part = static_cast<float*>(m->bufp[op.out.buf]);
-                    rc = conv_launch(ctx, cs.w, xin, B, h, w, TensorView{}, ep1, st);
-                    if (rc) return rc;
-                    rc = rgbtail_finish_launch(ctx, rt.w, ep1.f2_part, B, h, w, ob.act, ob.alpha, ob.clip, y, m->out_C, 0, io_dtype == SR_DTYPE_F32, st);
-                    if (rc) return rc;
-                    ++oi;                                             // the second conv has run
-                    break;
-                }
-                if (op.pw2 >= 0 && (ctx->chain_mask & 256) && m->taps.count((int)oi) == 0 && cs.w.thin && !cs.w.few && cs.w.dtype == SR_DTYPE_F32 && op.skip1.buf < 0 &&
-                    op.skip2.buf < 0 && op.d2s == 1 && !op.clip) {
-                    // conv2d (9x9, ReLU) + conv2d_1 (1x1, ReLU) as one kernel: only the 32-channel tensor is stored
-                    const Op& ob = m->ops[oi + 1];
-                    ConvEpilogue ep2;
-                    ep2.act = op.act; ep2.alpha = op.alpha; ep2.pw2 = &m->pw2s[op.pw2].w;
-                    rc = conv_launch(ctx, cs.w, xin, B, h, w, TensorView{m->bufp[ob.out.buf], m->bufs[ob.out.buf].Cbuf, ob.out.coff, m->bufs[ob.out.buf].blk}, ep2, st);
-                    if (rc) return rc;
-                    ++oi;                                             // the 1x1 has run
-                    break;
-                }
+                // a packed layout (CellGrid) in the input, the output and every skip, or in none: the batch is then one tall image to the kernel, separators never stored
+                const CellGrid g = m->grid_now[in];
+                bool same = g.gx == 0 || op.d2s == 1;
+                for (const Ref& r : {op.out, op.skip1, op.skip2})
+                    if (r.buf != -1 && !((r.buf >= 0 ? m->grid_now[r.buf] : CellGrid{}) == g)) same = false;
+                if (!same) return ctx->fail(SR_ERR_STATE, "packed small-image layout: producer and consumer disagree");
+                const int cB = g.gx ? 1 : B;
+                if (g.gx) { h = g.Hv; w = g.Wv; }
                 ConvEpilogue ep;
-                ep.act = op.act; ep.alpha = op.alpha; ep.clip01 = op.clip; ep.d2s_r = op.d2s;
-                int cB = B;
-                if (op.out.buf >= 0 && m->grid_now[op.in.buf].gx) {
-                    // both tensors hold the batch packed in the same CellGrid: one tall image to the kernel, separators never stored
-                    const CellGrid& g = m->grid_now[op.in.buf];
-                    if (!(m->grid_now[op.out.buf] == g) || op.skip1.buf >= 0 || op.skip2.buf >= 0 || op.d2s != 1)
-                        return ctx->fail(SR_ERR_STATE, "packed small-image layout: producer and consumer disagree");
-                    cB = 1; h = g.Hv; w = g.Wv; ep.cell_h = g.ch; ep.cell_w = g.cw;
+                ep.act = op.act; ep.alpha = op.alpha; ep.clip01 = op.clip; ep.d2s_r = op.d2s; ep.cell_h = g.ch; ep.cell_w = g.cw;
+                if (op.skip1.buf >= 0) { ep.skip1 = m->view(op.skip1); ep.beta1 = op.beta1; }
+                if (op.skip2.buf >= 0) { ep.skip2 = m->view(op.skip2); ep.beta2 = op.beta2; }
+                if (route == RT_RGB_TAIL) {
+                    const RgbTailWeights& rt = m->rgbtails[op.rgbtail].w;
+                    ep.f2 = &rt; ep.f2_part = static_cast<float*>(po);
+                    rc = conv_launch(ctx, cs.w, xin, cB, h, w, TensorView{}, ep, st);
+                    if (!rc) rc = rgbtail_finish_launch(ctx, rt, ep.f2_part, cB, h, w, nx->act, nx->alpha, nx->clip, y, m->out_C, 0, io_dtype == SR_DTYPE_F32, st);
+                    break;
                 }
-                if (cp.gx && op.out.buf >= 0 && m->bufs[op.in.buf].cat && m->bufs[op.out.buf].cat) {
-                    // a dense-block conv on the cell-packed concat buffers: input, output and skips share the grid
-                    if ((op.skip1.buf >= 0 && !m->bufs[op.skip1.buf].cat) || (op.skip2.buf >= 0 && !m->bufs[op.skip2.buf].cat) || op.d2s != 1)
-                        return ctx->fail(SR_ERR_STATE, "cell-packed dense blocks: a skip tensor outside the grid");
-                    cB = 1; h = cp.Hv; w = cp.Wv; ep.cell_h = cp.ch; ep.cell_w = cp.cw;
-                }
-                if (op.skip1.buf >= 0) { ep.skip1 = {m->bufp[op.skip1.buf], m->bufs[op.skip1.buf].Cbuf, op.skip1.coff, m->bufs[op.skip1.buf].blk}; ep.beta1 = op.beta1; }
-                if (op.skip2.buf >= 0) { ep.skip2 = {m->bufp[op.skip2.buf], m->bufs[op.skip2.buf].Cbuf, op.skip2.coff, m->bufs[op.skip2.buf].blk}; ep.beta2 = op.beta2; }
-                if ((ctx->chain_mask & 64) && T == SR_DTYPE_BF16 && oi + 1 < m->ops.size() && m->ops[oi + 1].kind == OP_POOL && m->ops[oi + 1].in.buf == op.out.buf &&
-                    op.out.buf >= 0 && m->ops[oi + 1].out.buf >= 0 && cs.w.rows && cs.w.NT == 4 && cs.w.CoutP == cs.w.Cout && op.skip1.buf < 0 && op.skip2.buf < 0 &&
-                    op.d2s == 1 && !op.clip && op.act != SR_ACT_TANH && m->taps.count((int)oi) == 0 && cB == B && !m->grid_now[op.out.buf].gx && h >= 2 && w >= 2 &&
-                    m->bufs[m->ops[oi + 1].out.buf].Cbuf % 8 == 0 && m->bufs[m->ops[oi + 1].out.buf].Cbuf >= cs.w.Cout) {
-                    // conv -> MaxPooling2D (every VGG16 block ends so): the pool rides in the conv's epilogue, the full-resolution tensor is never stored
-                    const Op& opl = m->ops[oi + 1];
-                    ep.pool_out = TensorView{m->bufp[opl.out.buf], m->bufs[opl.out.buf].Cbuf, opl.out.coff, m->bufs[opl.out.buf].blk};
-                    ep.pool_grid = m->grid_now[opl.out.buf];
-                    pool_done = (int)oi + 1;
-                }
-                if (op.proj >= 0 && (ctx->chain_mask & 8) && cs.w.rows && cs.w.NT == 4 && cs.w.Cout / (op.d2s * op.d2s) == 64 && cs.w.CoutP == cs.w.Cout &&
-                    op.out.buf >= 0 && !m->bufs[op.out.buf].blk && op.skip2.buf < 0 && !op.clip && op.act != SR_ACT_TANH && m->bufs[op.out.buf].Cbuf % 4 == 0) {
-                    // the SelfAttention layer that follows opens with three 1x1 convs of this conv's output: computed here, from registers
-                    const Op& oq = m->ops[oi + 1];
-                    ep.pj = &m->projs[op.proj].w;
-                    ep.pj_out = TensorView{m->bufp[oq.out.buf], m->bufs[oq.out.buf].Cbuf, oq.out.coff, m->bufs[oq.out.buf].blk};
-                    proj_done = (int)oi + 1;
-                }
+                if (route == RT_PW2) ep.pw2 = &m->pw2s[op.pw2].w;
+                else if (nx && nx->kind == OP_POOL) { ep.pool_out = m->view(nx->out); ep.pool_grid = m->grid_now[nx->out.buf]; }
+                else if (nx) { ep.pj = &m->projs[op.proj].w; ep.pj_out = m->view(nx->out); }
                 if (op.out.buf == -2) {
                     ep.out_f32 = io_dtype == SR_DTYPE_F32;
                     rc = conv_launch(ctx, cs.w, xin, B, h, w, y, m->out_C, 0, ep, st);
                 } else {
-                    rc = conv_launch(ctx, cs.w, xin, cB, h, w, TensorView{m->bufp[op.out.buf], m->bufs[op.out.buf].Cbuf, op.out.coff, m->bufs[op.out.buf].blk}, ep, st);
+                    rc = conv_launch(ctx, cs.w, xin, cB, h, w, route == RT_PW2 ? m->view(nx->out) : vo, ep, st);
                 }
                 break;
             }
-            case OP_ATTN:
-                rc = attention_launch(ctx, T, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, /*q=g*/ 8, /*k=f*/ 0, /*v=h*/ 16, B, h * w,
-                                      m->bufp[op.out.buf], m->bufs[op.out.buf].Cbuf, 0, st);
-                break;
-            case OP_SUBSAMPLE:
-                rc = subsample2_launch(ctx, T, m->bufp[op.in.buf], B, h, w, m->bufs[op.in.buf].C, m->bufs[op.in.buf].Cbuf, m->bufp[op.out.buf],
-                                       m->bufs[op.out.buf].Cbuf, st);
+            case OP_CONVERT:
+                rc = convert_pad_launch(ctx, x, io_dtype, (int64_t)B * H * W, C, po, T, vo.cs, 1.f, 0.f, st);
                 break;
             case OP_PREPROC:
-                rc = vgg_preproc_launch(ctx, x, io_dtype, (int64_t)B * H * W, m->bufp[op.out.buf], T, m->bufs[op.out.buf].Cbuf, st);
+                rc = vgg_preproc_launch(ctx, x, io_dtype, (int64_t)B * H * W, po, T, vo.cs, st);
                 break;
-            case OP_TOBLK:
-                if (cp.gx) {
-                    rc = cell_pack_launch(ctx, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, B, h, w, 64, m->bufp[op.out.buf], m->bufs[op.out.buf].Cbuf, op.out.coff, cp, st);
-                    break;
-                }
-                if (pack2) {
-                    rc = pack_pairs_launch(ctx, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, B, h, w, 64, m->bufp[op.out.buf], m->bufs[op.out.buf].Cbuf, op.out.coff, st);
-                    break;
-                }
-                rc = nhwc_to_blocked_launch(ctx, m->bufp[op.in.buf], m->bufs[op.in.buf].Cbuf, op.in.coff, B, h, w, 64, m->bufp[op.out.buf],
-                                            m->bufs[op.out.buf].Cbuf, op.out.coff, st);
+            case OP_ATTN:
+                rc = attention_launch(ctx, T, vi.p, vi.cs, /*q=g*/ 8, /*k=f*/ 0, /*v=h*/ 16, B, h * w, po, vo.cs, 0, st);
                 break;
+            case OP_SUBSAMPLE:
+                rc = subsample2_launch(ctx, T, vi.p, B, h, w, m->bufs[op.in.buf].C, vi.cs, po, vo.cs, st);
+                break;
+            case OP_TOBLK: {                                                  // the trunk into the first concat buffer, in the layout the dense blocks take
+                const CellGrid& g = m->grid_now[op.out.buf];
+                rc = g.gx ? cell_pack_launch(ctx, vi.p, vi.cs, vi.coff, B, h, w, 64, po, vo.cs, vo.coff, g, st)
+                   : L.pack2 ? pack_pairs_launch(ctx, vi.p, vi.cs, vi.coff, B, h, w, 64, po, vo.cs, vo.coff, st)
+                             : nhwc_to_blocked_launch(ctx, vi.p, vi.cs, vi.coff, B, h, w, 64, po, vo.cs, vo.coff, st);
+                break;
+            }
             case OP_POOL:
-                if ((int)oi == pool_done) break;                              // computed by the conv in front of it
-                rc = maxpool2_launch(ctx, T, m->bufp[op.in.buf], B, h, w, m->bufs[op.in.buf].C, m->bufs[op.in.buf].Cbuf, m->bufp[op.out.buf],
-                                     m->bufs[op.out.buf].Cbuf, st, m->grid_now[op.in.buf], m->grid_now[op.out.buf]);
+                rc = maxpool2_launch(ctx, T, vi.p, B, h, w, m->bufs[op.in.buf].C, vi.cs, po, vo.cs, st, m->grid_now[op.in.buf], m->grid_now[op.out.buf]);
                 break;
             case OP_GAP:
-                rc = gap_launch(ctx, T, m->bufp[op.in.buf], B, h * w, m->bufs[op.in.buf].C, m->bufs[op.in.buf].Cbuf,
-                                static_cast<float*>(m->bufp[op.out.buf]), st);
+                rc = gap_launch(ctx, T, vi.p, B, h * w, m->bufs[op.in.buf].C, vi.cs, static_cast<float*>(po), st);
                 break;
-            case OP_DENSE: {
-                const float* xin = static_cast<const float*>(m->bufp[op.in.buf]);
-                if (op.out.buf == -2) {
-                    if (io_dtype == SR_DTYPE_F32) rc = dense_launch(ctx, xin, m->dense_dev[op.dw], m->dense_dev[op.db], B, op.In, op.Out, op.act, static_cast<float*>(y), 0, nullptr, st);
-                    else rc = dense_launch(ctx, xin, m->dense_dev[op.dw], m->dense_dev[op.db], B, op.In, op.Out, op.act, nullptr, io_dtype, y, st);
-                } else {
-                    rc = dense_launch(ctx, xin, m->dense_dev[op.dw], m->dense_dev[op.db], B, op.In, op.Out, op.act, static_cast<float*>(m->bufp[op.out.buf]), 0, nullptr, st);
-                }
+            case OP_DENSE: {                                                  // fp32 out, except the caller's y in a bf16 forward
+                const bool f32 = op.out.buf != -2 || io_dtype == SR_DTYPE_F32;
+                float* yf = static_cast<float*>(op.out.buf == -2 ? y : po);
+                rc = dense_launch(ctx, static_cast<const float*>(vi.p), m->dense_dev[op.dw], m->dense_dev[op.db], B, op.In, op.Out, op.act, f32 ? yf : nullptr,
+                                  f32 ? 0 : io_dtype, f32 ? nullptr : y, st);
                 break;
             }
         }
         if (rc) return rc;
-        if (!m->taps.empty()) {
-            auto it = m->taps.find((int)oi);
-            if (it != m->taps.end()) {
-                const Op& top = m->ops[oi];                                  // oi may have moved on to a second conv computed in this one's epilogue (the fused 1x1): the tap is on THAT op
-                int C_, mu, sh;
-                op_out_view(m, top, &C_, &mu, &sh);
-                int th, tw;
-                buf_hw(m->bufs[top.out.buf], H, W, &th, &tw);
-                if (it->second.cap < (int64_t)B * th * tw * C_) return ctx->fail(SR_ERR_CAPACITY, "tap buffer too small");
-                const BufSpec& ob = m->bufs[top.out.buf];
-                rc = tap_copy_launch(ctx, m->bufp[top.out.buf], T, ob.blk, ob.Cbuf, top.out.coff, B, th, tw, C_, it->second.dst, st, pack2 && ob.blk);
-                if (rc) return rc;
-            }
+        if (tapped(m, oi)) {
+            int C_, mu, sh, th, tw;
+            op_out_view(m, op, &C_, &mu, &sh);
+            buf_hw(m->bufs[op.out.buf], H, W, &th, &tw);
+            const sr_model::Tap& tp = m->taps.at((int)oi);
+            if (tp.cap < (int64_t)B * th * tw * C_) return ctx->fail(SR_ERR_CAPACITY, "tap buffer too small");
+            rc = tap_copy_launch(ctx, vo.p, T, vo.blk, vo.cs, vo.coff, B, th, tw, C_, tp.dst, st, L.pack2 && vo.blk);
+            if (rc) return rc;
         }
     }
     SR_HIP(ctx, hipEventRecord(ctx->ev1, st));
@@ -1181,8 +1181,7 @@ int sr_conv2d_dev(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, cons
     if (rc) return rc;
     const int Cp = cw.thin ? cw.CinP : round_up(cw.CinP, 32);
     const void* xp = x;
-    static const bool force_copy = getenv("SR355_CONV_DEV_COPY") != nullptr;   // A/B switch (diagnostic)
-    if (force_copy || Cp != Cin || ((uintptr_t)x % 16) != 0) {          // channel padding needed: a padded copy in the arena (else the conv reads x in place)
+    if (Cp != Cin || ((uintptr_t)x % 16) != 0) {          // channel padding needed: a padded copy in the arena (else the conv reads x in place)
         void* xa = ctx->arena(ctx->dev_x, (size_t)B * H * W * Cp * 4 + 4096, st);
         if (!xa) return SR_ERR_OOM;
         rc = convert_pad_launch(ctx, x, SR_DTYPE_F32, (int64_t)B * H * W, Cin, xa, SR_DTYPE_F32, Cp, 1.f, 0.f, st);

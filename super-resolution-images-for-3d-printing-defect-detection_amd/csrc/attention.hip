@@ -473,8 +473,7 @@ int attention_launch(sr_ctx* ctx, int dtype, const void* qkv, int64_t cs, int qo
     if (dtype == SR_DTYPE_BF16) {
         // two 32-query blocks per wave (256 queries per workgroup): the blocks share the key fragment and give the
         // scheduler two independent softmax chains (measured 3 % faster than one block per wave)
-        static const int qb_env = [] { const char* e = getenv("SR355_ATTN_QB"); return e ? atoi(e) : 2; }();      // tuning switch: query blocks per wave
-        const int QBr = qb_env == 1 ? 1 : 2;
+        constexpr int QBr = 2;
         const int64_t nwg = (int64_t)B * ((N + 128 * QBr - 1) / (128 * QBr));
         const int ngroups = (N + KT2 - 1) / KT2;
         if (nwg >= (1ll << 31) || (int64_t)B * ngroups >= (1ll << 31)) { ctx->prof_close(rec, st); return ctx->fail(SR_ERR_INVALID, "attention: too many workgroups for one launch"); }
@@ -482,8 +481,7 @@ int attention_launch(sr_ctx* ctx, int dtype, const void* qkv, int64_t cs, int qo
         if (!kn) { ctx->prof_close(rec, st); return SR_ERR_OOM; }
         p.knorm = kn;
         hipLaunchKernelGGL(attn_knorm_kernel, dim3((unsigned)((int64_t)B * ngroups)), dim3(64), 0, st, reinterpret_cast<const bf16_t*>(qkv) + 0, cs, koff, N, ngroups, kn);
-        if (QBr == 1) hipLaunchKernelGGL(attn_bf16_kernel<1>, dim3((unsigned)nwg), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(attn_bf16_kernel<2>, dim3((unsigned)nwg), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(attn_bf16_kernel<QBr>, dim3((unsigned)nwg), dim3(256), 0, st, p);
     }
     else hipLaunchKernelGGL(attn_f32_kernel, grid, dim3(256), 0, st, p);
     ctx->prof_close(rec, st);

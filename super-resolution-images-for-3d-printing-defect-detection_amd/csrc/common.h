@@ -73,7 +73,7 @@ struct sr_ctx {
                                   // synchronously in sr_init, so that no launch on any stream can see it before it is zero
     int num_cus = 0;
     int cu_count();               // compute units of the device (queried once)
-    int chain_mask = 511;          // bit 0: fuse conv4+conv5 of a dense block, bit 1: fuse conv2+conv3, bit 2: fold the generator's RGB conv into final_conv1, bit 3: SelfAttention's f / g / h projections in the producing conv's epilogue bit 4: batches of small images (VGG16 block 5) packed in a CellGrid, bit 5: conv1 of a dense block on the streaming kernel, bit 6: a 2x2 max-pool inside the conv in front of it, bit 7: 64-input-channel 3x3 convs on the persistent kernel of conv_stream.hip, bit 8: SRCNN's 1x1 conv inside the 9x9 head's epilogue (sr_debug_set_fused; default all)
+    int chain_mask = 511;          // SR_FUSE_* bits (include/sr355.h): which fused / persistent paths sr_forward may take (sr_debug_set_fused; default all)
     int chain_max_wgs = 0;        // test hook: cap the persistent grid so that small batches still give several images per workgroup
     int64_t alloc_cap = 0;        // test hook (sr_debug_set_alloc_cap): dalloc fails once cur_bytes would exceed it; 0 = none
 
@@ -82,6 +82,8 @@ struct sr_ctx {
     void* scratch(size_t bytes);  // reduction scratch; stream-ordered reuse (one stream per ctx at a time)
     int fail(int code, const std::string& msg) { err = msg; return code; }
 };
+static_assert(511 == SR_FUSE_ALL && SR_FUSE_ALL == (SR_FUSE_DENSE_TAIL | SR_FUSE_DENSE_MID | SR_FUSE_RGB_TAIL | SR_FUSE_ATTN_PROJ | SR_FUSE_CELLS | SR_FUSE_CONV1_STREAM |
+                                             SR_FUSE_POOL | SR_FUSE_CONV_STREAM | SR_FUSE_SRCNN_1X1), "sr_ctx::chain_mask's default is every SR_FUSE_* bit");
 
 // Every ABI entry that allocates or launches binds the calling thread to the context's device first and puts the
 // previous device back on return (the current device is per-thread state the caller -- torch -- may have changed).

@@ -460,9 +460,8 @@ int launch_wide(sr_ctx* ctx, const ConvParams& p0, int nct, hipStream_t st) {
         const int64_t wgs3 = (int64_t)((p0.W + 15) / 16) * ((p0.H + 8 * MT_DEFAULT - 1) / (8 * MT_DEFAULT)) * p0.B * nct;
         if constexpr (KS == 3 && KGPT == 2) {
             // still fewer than one 8 x 16 tile per CU: split K inside the workgroup (conv_wide_sk_kernel) -- 4 x the workgroups, a quarter of the chain each
-            static const bool no_sk = getenv("SR355_NO_SPLITK") != nullptr;      // A/B switch (diagnostic)
             const int64_t wgs1 = (int64_t)((p0.W + 15) / 16) * ((p0.H + 7) / 8) * p0.B * nct;
-            if (!no_sk && p0.splitk_ok && wgs1 < ctx->cu_count()) return launch_wide_sk<KS, KGPT, NT>(ctx, p0, nct, st);
+            if (p0.splitk_ok && wgs1 < ctx->cu_count()) return launch_wide_sk<KS, KGPT, NT>(ctx, p0, nct, st);
         }
         if (wgs3 < 2 * ctx->cu_count()) return launch_wide_mt<T, KS, KGPT, NT, 1>(ctx, p0, nct, st);
     }
@@ -656,8 +655,7 @@ int launch_fewcout(sr_ctx* ctx, const ConvParams& p, hipStream_t st) {
     constexpr int PS = 16 + KS - 1;
     const int CinP = p.nchunks * 4;
     const int lds = PS * PS * (CinP + 4) * 4 + p.nchunks * KS * KS * 16 * 4;
-    static const bool chunked = getenv("SR355_FEW_CHUNKED") != nullptr;      // A/B switch (diagnostic): round 3's four-channels-at-a-time kernel
-    if (!chunked && lds <= 80 * 1024 && (p.in_cs & 3) == 0 && (p.in_coff & 3) == 0) {      // two workgroups per CU
+    if (lds <= 80 * 1024 && (p.in_cs & 3) == 0 && (p.in_coff & 3) == 0) {      // two workgroups per CU
         auto kern = conv_fewcout_full_kernel<KS>;
         if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
         hipLaunchKernelGGL(kern, dim3((p.W + 15) / 16, (p.H + 15) / 16, p.B), dim3(256), lds, st, p);
@@ -1051,7 +1049,7 @@ int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, i
         p.f2w = static_cast<const char*>(ep.f2->a); p.f2part = ep.f2_part; p.f2c = ep.f2->c2;
     }
     const int nct = w.CoutP / 32 / w.NT;
-    const bool stream = (ctx->chain_mask & 128) != 0 && conv_stream_supported(w, p);
+    const bool stream = (ctx->chain_mask & SR_FUSE_CONV_STREAM) != 0 && conv_stream_supported(w, p);
     int rec = -1;
     if (ctx->prof && ep.f2) {
         const double px = (double)B * H * W;

@@ -191,8 +191,7 @@ __global__ void __launch_bounds__((S_NCOMP + S_NLOAD) * 64, (S_NCOMP + S_NLOAD +
 }  // namespace
 
 bool conv_stream_supported(const ConvWeights& w, const convk::ConvParams& p) {
-    static const bool off = getenv("SR355_NO_CONV_STREAM") != nullptr;
-    return !off && w.rows && w.dtype == SR_DTYPE_BF16 && w.NT == 4 && w.nchunks == 2 && w.Cin == 64 && w.CoutP == w.Cout && p.in_ps == 32 && p.in_cs >= 64 && p.in_cs % 8 == 0 &&
+    return w.rows && w.dtype == SR_DTYPE_BF16 && w.NT == 4 && w.nchunks == 2 && w.Cin == 64 && w.CoutP == w.Cout && p.in_ps == 32 && p.in_cs >= 64 && p.in_cs % 8 == 0 &&
            p.in_coff % 8 == 0 && p.H % S_TH == 0 && p.W % S_TW == 0 && p.skip_lds == 0 && !p.f2w && !p.pjw && !p.plout && !p.dbg && p.cell_h == 0 && p.cell_w == 0 &&
            // the vector epilogues with at most one skip (conv_rows_epi.h kinds 0..3; the host passes a lone skip as skip 1)
            p.vec != 0 && (p.Cout & 3) == 0 && p.act != SR_ACT_TANH && (p.r <= 1 || (p.Cd & 15) == 0) && !p.s2;

@@ -1011,8 +1011,6 @@ int chain_launch(sr_ctx* ctx, const ChainWeights& w, TensorView in, int B, int H
     if ((T + 16) * (int64_t)(H + 1) * (H + 1) >= (1ll << 32)) return ctx->fail(SR_ERR_INVALID, "fused dense-block pair: stream too long");
     const int nwg_target = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, (T + 23) / 24));
     p.rows_per_wg = (int)((T + nwg_target - 1) / nwg_target);
-    static const bool whole_images = getenv("SR355_CHAIN_WHOLE_IMAGES") != nullptr;       // A/B switch (diagnostic): round 2's partition, ranges = whole images
-    if (whole_images) p.rows_per_wg = ((B + ncu - 1) / ncu) * (H + 1);
     const int nwg = (int)((T + p.rows_per_wg - 1) / p.rows_per_wg);
     p.magic = (unsigned)(((1ull << 32) + (unsigned)H) / (unsigned)(H + 1));                 // ceil(2^32 / (H+1)): exact quotient for g (H+1)^2 < 2^32 (checked above)
     p.alpha = alpha; p.xscale = tail ? beta_x / alpha : 0.f; p.oscale = tail && skip_o.p ? beta_o / alpha : 0.f;

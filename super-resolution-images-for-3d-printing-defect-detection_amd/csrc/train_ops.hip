@@ -488,9 +488,7 @@ int wgrad_launch_views(sr_ctx* ctx, const float* x, int64_t x_cs, const float* d
     if (KS < 1 || !(KS & 1) || KS > 15) return ctx->fail(SR_ERR_INVALID, "wgrad: odd kernel sizes up to 15 only");
     const int nci = (Cin + 31) / 32, nco = (Cout + 31) / 32, ntiles = KS * KS * nci * nco;
     const int64_t P = (int64_t)B * H * W;
-    static const bool per_tap_env = getenv("SR355_WGRAD_PER_TAP") != nullptr;   // A/B switch (diagnostic): round 3's kernel for every layer (dense tensors only)
-    const bool per_tap = per_tap_env && x_cs == Cin && dy_cs == Cout;
-    if (KS == 3 && !per_tap) {
+    if (KS == 3) {
         const int tilesX = (W + WT_W - 1) / WT_W, tilesY = (H + WT_H - 1) / WT_H, ntile = B * tilesY * tilesX;
         // pixel splits: enough workgroups for ~1.5 per CU, each a whole number of 8 x 24 tiles
         int nsplit = (3 * ctx->cu_count() / 2 + nci * nco - 1) / (nci * nco);

@@ -17,6 +17,10 @@ ACT_LINEAR, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 WEIGHT_KERNEL, WEIGHT_BIAS = 0, 1
 SP_MAXPOOL2, SP_GAP, SP_PICK2, SP_VGG_PREPROCESS = 0, 1, 2, 3
 ELT_AXPBY, ELT_RELU_BWD, ELT_LRELU_BWD, ELT_CLIP01_BWD, ELT_MUL, ELT_TANH_BWD, ELT_CLIP01, ELT_SIGN_DIFF = 0, 1, 2, 3, 4, 5, 6, 7
+FUSE_DENSE_TAIL, FUSE_DENSE_MID, FUSE_RGB_TAIL, FUSE_ATTN_PROJ, FUSE_CELLS, FUSE_CONV1_STREAM, FUSE_POOL, FUSE_CONV_STREAM, FUSE_SRCNN_1X1 = \
+    1, 2, 4, 8, 16, 32, 64, 128, 256
+FUSE_ALL = 511
+FUSE_TWO_UP = FUSE_DENSE_TAIL | FUSE_DENSE_MID | FUSE_CONV1_STREAM
 
 
 class ModelCfg(C.Structure):

@@ -212,9 +212,7 @@ class Tape:
 
 # ----------------------------------------------------------------------------------------------------------------- networks
 # dense blocks on one virtual-concat buffer per block (Tape.dense_block) where the growth width is a whole number of the fp32 conv's 16-channel chunks
-# (G = 32: yes; the notebook's G = 8: the cat path); SR355_TAPE_CAT=1 restores round 3's cat path for A/B runs
-import os as _os
-VIRTUAL_CONCAT = _os.environ.get("SR355_TAPE_CAT") is None
+# (G = 32: yes; the notebook's G = 8: the cat path)
 
 
 def generator_forward(t, x, scale, num_rrdb, attention=True):
@@ -226,7 +224,7 @@ def generator_forward(t, x, scale, num_rrdb, attention=True):
         for d in (1, 2, 3):
             n = f"rrdb_{b}_dense{d}"
             growth = t.w[f"{n}_conv1"][0].shape[3]
-            if VIRTUAL_CONCAT and growth % 16 == 0:
+            if growth % 16 == 0:
                 x = t.dense_block(x, n, growth)
                 continue
             feats = [x]

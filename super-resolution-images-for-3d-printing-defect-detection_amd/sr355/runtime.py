@@ -114,10 +114,18 @@ class Context:
         return mhz.value
 
     FUSED_ALL = 511
+    FUSED_DENSE_TAIL, FUSED_DENSE_MID, FUSED_RGB_TAIL = L.FUSE_DENSE_TAIL, L.FUSE_DENSE_MID, L.FUSE_RGB_TAIL
+    FUSED_ATTN_PROJ, FUSED_CELLS, FUSED_CONV1_STREAM = L.FUSE_ATTN_PROJ, L.FUSE_CELLS, L.FUSE_CONV1_STREAM
+    FUSED_POOL, FUSED_CONV_STREAM, FUSED_SRCNN_1X1 = L.FUSE_POOL, L.FUSE_CONV_STREAM, L.FUSE_SRCNN_1X1
+    FUSED_TWO_UP = L.FUSE_TWO_UP
 
     def set_fused(self, mask=511, max_workgroups=0):
-        """Which dense-block conv pairs run as one fused kernel (bit 0: conv4+conv5, bit 1: conv2+conv3) and whether the generator's RGB conv rides in
-        final_conv1's epilogue (bit 2) and SelfAttention's f / g / h projections in the epilogue of the conv before it (bit 3); bit 4: batches of small images (VGG16 block 5) packed into one tall image with zero separators; bit 5: conv1 of a dense block on the streaming line-buffer kernel; bit 6: a 2x2 max-pool inside the epilogue of the conv in front of it; bit 7: 3x3 convs from 64 input channels on the persistent kernel with resident weights; 0 = layer by layer."""
+        """Which fused / persistent paths sr_forward may take: an OR of the FUSED_* bits (include/sr355.h, SR_FUSE_*): FUSED_DENSE_TAIL / FUSED_DENSE_MID:
+        a dense block's conv4+conv5 / conv2+conv3 as one kernel; FUSED_RGB_TAIL: the generator's RGB conv in final_conv1's epilogue; FUSED_ATTN_PROJ:
+        SelfAttention's f / g / h projections in the epilogue of the conv before it; FUSED_CELLS: batches of small images (VGG16 block 5) packed into one
+        tall image with zero separators; FUSED_CONV1_STREAM: conv1 of a dense block on the streaming line-buffer kernel; FUSED_POOL: a 2x2 max-pool inside
+        the epilogue of the conv in front of it; FUSED_CONV_STREAM: 3x3 convs from 64 input channels on the persistent kernel with resident weights;
+        FUSED_SRCNN_1X1: SRCNN's 1x1 conv in the 9x9 head's epilogue.  FUSED_ALL (the default): all of them; 0 = layer by layer."""
         self.check(self.lib.sr_debug_set_fused(self.h, int(mask), int(max_workgroups)))
 
     def set_alloc_cap(self, nbytes):

@@ -9,7 +9,7 @@ import torch
 
 from oracle import models as M
 from oracle import ops as O
-from sr355 import Model
+from sr355 import Context, Model
 from sr355.weights import bf16_rounded, init_weights, round_to_bf16
 
 pytestmark = pytest.mark.gpu
@@ -54,7 +54,8 @@ def oracle_of_case(case, x, w, nb):
 
 
 @pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("mask", [1, 2, 3, 32, 35])       # bit 5: conv1 of every dense block on the streaming kernel
+@pytest.mark.parametrize("mask", [Context.FUSED_DENSE_TAIL, Context.FUSED_DENSE_MID, Context.FUSED_DENSE_TAIL | Context.FUSED_DENSE_MID,
+                                  Context.FUSED_CONV1_STREAM, Context.FUSED_TWO_UP])       # FUSED_CONV1_STREAM: conv1 of every dense block on the streaming kernel
 def test_fused_pairs_match_layer_by_layer_and_oracle(fused_ctx, case, mask):
     ctx = fused_ctx
     B, H, cap = case
@@ -112,7 +113,7 @@ def test_fused_tail_exact_integers(fused_ctx):
     names = ["rrdb_0_dense1_conv2", "rrdb_0_dense1_conv3", "rrdb_0_dense1_conv5", "rrdb_0_dense2_conv5", "rrdb_0_dense3_conv5"]
     ctx.set_fused(0, 0)
     _, t0 = m.forward_with_taps(xd, names + ["rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"])
-    ctx.set_fused(35, 2)
+    ctx.set_fused(ctx.FUSED_TWO_UP, 2)
     _, t1 = m.forward_with_taps(xd, names + ["rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"])
     for n in ("rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"):                  # the streaming conv1 kernel: integers again for dense1, same roundings for dense2
         a, b = t0[n].cpu().numpy(), t1[n].cpu().numpy()
@@ -164,7 +165,7 @@ def test_two_up_packed_24_wide_patches_match_layer_by_layer_and_oracle(fused_ctx
     m.set_weights(w)
     x = round_to_bf16(np.random.default_rng(B * 10 + H).uniform(-1, 1, (B, H, 24, 3)).astype(np.float32))
     xd = ctx.to_device(x, torch.bfloat16)
-    dense = ctx.FUSED_ALL & ~35
+    dense = ctx.FUSED_ALL & ~ctx.FUSED_TWO_UP
     ctx.set_fused(dense, 0)
     ctx.profile_begin()
     y0 = m.forward(xd)
@@ -280,7 +281,7 @@ def test_cell_packed_dense_blocks_on_the_tile_kernels(fused_ctx, growth, shape):
     m = Model("esrgan_g", compute_dtype="bf16", scale_factor=2, num_blocks=nb, growth_channels=growth, use_attention=False, ctx=ctx)
     w = bf16_rounded(init_weights(m.layer_shapes(), seed=3800 + growth))
     m.set_weights(w)
-    ctx.set_fused(ctx.FUSED_ALL & ~35, 0)                                     # G = 32 at 24 wide would otherwise ride two-up on the fused kernels
+    ctx.set_fused(ctx.FUSED_ALL & ~ctx.FUSED_TWO_UP, 0)                     # G = 32 at 24 wide would otherwise ride two-up on the fused kernels
 
     def both(B, seed):
         x = round_to_bf16(np.random.default_rng(seed).uniform(-1, 1, (B, H, W, 3)).astype(np.float32))
@@ -302,3 +303,11 @@ def test_cell_packed_dense_blocks_on_the_tile_kernels(fused_ctx, growth, shape):
     m.forward(ctx.to_device(x48, torch.bfloat16))                              # a plain forward at another size re-allocates / overwrites
     x2, y2 = both(37, 1)
     assert torch.equal(y2, y)
+    # packed forwards at other batches on the same grid shape (gx = 16: four rows of cells, then three, then four again) with nothing in between: the
+    # buffers are not cleared, and the separators are still zeros
+    xs = [ctx.to_device(round_to_bf16(np.random.default_rng(s).uniform(-1, 1, (b, H, W, 3)).astype(np.float32)), torch.bfloat16)
+          for b, s in ((64, 7), (48, 8), (64, 9))]
+    ys = [m.forward(xd) for xd in xs]
+    for xd, yp in zip(xs, ys):
+        yt, _ = m.forward_with_taps(xd, ["trunk_conv"])
+        assert torch.equal(yp, yt), (xd.shape[0], float((yp.float() - yt.float()).abs().max()))

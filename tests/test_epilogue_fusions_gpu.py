@@ -52,9 +52,9 @@ def test_rgb_tail_matches_two_kernel_path_and_oracle(fused_ctx, case, io):
     m.set_weights(w)
     x = round_to_bf16(np.random.default_rng(17 * H + W).uniform(-1, 1, (B, H, W, C)).astype(np.float32))
     xd = ctx.to_device(x, torch.float32 if io == "f32" else torch.bfloat16)
-    ctx.set_fused(3, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID, 0)
     y0, k0 = kernels_of(ctx, lambda: m.forward(xd))
-    ctx.set_fused(7, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL, 0)
     y1, k1 = kernels_of(ctx, lambda: m.forward(xd))
     assert not any("rgbtail" in k for k in k0)
     assert any(k.startswith("conv_rows_rgbtail") for k in k1) and "rgbtail_finish" in k1, k1      # the fused path is the one that ran
@@ -111,9 +111,9 @@ def test_rgb_tail_exact_integers(fused_ctx):
     ref = M.esrgan_g_forward(x, w, 2, 0, dtype=np.float64, attention=False, bf16_storage=True, bf16_output=False, parts=parts)
     h = parts["final_conv1"]
     assert np.array_equal(h, np.round(h)) and 0 < h.max() < 256, float(h.max())   # the premise: exact in bf16, and not all zeros
-    ctx.set_fused(3, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID, 0)
     y0 = m.forward(xd).cpu().numpy()
-    ctx.set_fused(7, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL, 0)
     y1, k1 = kernels_of(ctx, lambda: m.forward(xd))
     assert any(k.startswith("conv_rows_rgbtail") for k in k1)
     y1 = y1.cpu().numpy()
@@ -157,9 +157,9 @@ def test_attention_projections_in_the_producing_conv(fused_ctx, case):
     x = round_to_bf16(np.random.default_rng(H * W).uniform(-1, 1, (B, H, W, 3)).astype(np.float32))
     xd = ctx.to_device(x, torch.bfloat16)
     taps = ["self_attention_trunk_f", "self_attention_upsample_0_f", "trunk_conv", "upsample_0_conv"]
-    ctx.set_fused(7, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL, 0)
     (y0, t0), k0 = kernels_of(ctx, lambda: m.forward_with_taps(xd, taps))
-    ctx.set_fused(15, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL | ctx.FUSED_ATTN_PROJ, 0)
     (y1, t1), k1 = kernels_of(ctx, lambda: m.forward_with_taps(xd, taps))
     assert not any(k.startswith("conv_rows_proj") for k in k0) and any(k.startswith("conv_pw<bf16,k1,kg1,nt3>") for k in k0), k0
     assert any(k.startswith("conv_rows_proj") for k in k1) and not any(k.startswith("conv_pw<bf16,k1,kg1,nt3>") for k in k1), k1
@@ -197,20 +197,20 @@ def test_vgg16_block5_packed_batches(fused_ctx, patch):
     m.set_weights(w)
     rng = np.random.default_rng(patch)
     xs = [round_to_bf16(rng.uniform(0, 1, (n, patch, patch, 3)).astype(np.float32)) for n in (5, 2, 7, 1)]
-    ctx.set_fused(15, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL | ctx.FUSED_ATTN_PROJ, 0)
     want = [m.forward(ctx.to_device(x, torch.bfloat16)).clone() for x in xs]
-    ctx.set_fused(31, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL | ctx.FUSED_ATTN_PROJ | ctx.FUSED_CELLS, 0)
     got = [m.forward(ctx.to_device(x, torch.bfloat16)).clone() for x in xs]
     for a, b in zip(want, got):
         assert torch.equal(a, b), float((a.float() - b.float()).abs().max())
     # ... and with every block's MaxPooling2D computed in the epilogue of the conv in front of it (max of bf16 values is exact), alone and together with the packing
-    for mask in (64, 127):
+    for mask in (ctx.FUSED_POOL, ctx.FUSED_ALL & ~(ctx.FUSED_CONV_STREAM | ctx.FUSED_SRCNN_1X1)):
         ctx.set_fused(mask, 0)
         (y_p, ks) = kernels_of(ctx, lambda: m.forward(ctx.to_device(xs[0], torch.bfloat16)))
         assert any(k.startswith("conv_rows_pool") for k in ks), ks
         assert torch.equal(y_p, want[0]), (mask, float((y_p.float() - want[0].float()).abs().max()))
         assert torch.equal(m.forward(ctx.to_device(xs[2], torch.bfloat16)), want[2]), mask
-    ctx.set_fused(31, 0)
+    ctx.set_fused(ctx.FUSED_DENSE_TAIL | ctx.FUSED_DENSE_MID | ctx.FUSED_RGB_TAIL | ctx.FUSED_ATTN_PROJ | ctx.FUSED_CELLS, 0)
     y_t, taps = m.forward_with_taps(ctx.to_device(xs[0], torch.bfloat16), ["block5_conv3"])       # plain layout for this call
     assert torch.equal(y_t, want[0]) and taps["block5_conv3"].shape == (5, patch // 16, patch // 16, 512)
     assert torch.equal(m.forward(ctx.to_device(xs[2], torch.bfloat16)), want[2])                  # packed again

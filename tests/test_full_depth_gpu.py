@@ -63,7 +63,7 @@ def device_trace(ctx, dtype, w, x, nb=NB, stages=STAGES):
         # so the two bf16 images differ by that one rounding of a 64-channel tensor: output roundings flipped by an ulp (2^-8 at most on [-1, 1]) ...
         d = (y.float() - y2.float()).abs()
         assert float(d.max()) <= 2.0 ** -6 and float(d.mean()) <= 2.0 ** -9, (float(d.max()), float(d.mean()), float((d > 0).float().mean()))
-        ctx.set_fused(ctx.FUSED_ALL & ~4, 0)                 # ... and are the same image when that pair runs as two kernels in both
+        ctx.set_fused(ctx.FUSED_ALL & ~ctx.FUSED_RGB_TAIL, 0)                 # ... and are the same image when that pair runs as two kernels in both
         try:
             assert torch.equal(y, m.forward(ctx.to_device(x, td)))
         finally:

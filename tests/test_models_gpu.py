@@ -186,7 +186,7 @@ def test_srcnn_fused_1x1_matches_the_two_kernel_path_and_the_oracle(ctx, shape):
     x = np.random.default_rng(shape[2]).uniform(0, 1, shape).astype(np.float32)
     xd = ctx.to_device(x)
     try:
-        ctx.set_fused(ctx.FUSED_ALL & ~256, 0)
+        ctx.set_fused(ctx.FUSED_ALL & ~ctx.FUSED_SRCNN_1X1, 0)
         ctx.profile_begin()
         y0, t0 = m.forward_with_taps(xd, ["conv2d_1"])
         k0 = {r["kernel"] for r in ctx.profile_end()}
@@ -224,7 +224,7 @@ def test_srcnn_fused_1x1_exact_integers(ctx):
     x = rng.integers(0, 3, (2, 29, 37, 3)).astype(np.float32)
     xd = ctx.to_device(x)
     try:
-        ctx.set_fused(ctx.FUSED_ALL & ~256, 0)
+        ctx.set_fused(ctx.FUSED_ALL & ~ctx.FUSED_SRCNN_1X1, 0)
         y0, t0 = m.forward_with_taps(xd, ["conv2d_1"])
         ctx.set_fused(ctx.FUSED_ALL, 0)
         y1, t1 = m.forward_with_taps(xd, ["conv2d_1"])

@@ -9,7 +9,8 @@ for nb in (1, 2):
     w = bfw(init_weights(m.layer_shapes(), seed=3500)); m.set_weights(w)
     x = rb(np.random.default_rng(1).uniform(-1, 1, (8, 24, 24, 3)).astype(np.float32))
     perm = [1, 0] + list(range(2, 8))
-    for name, mask in (("unfused", ctx.FUSED_ALL & ~35), ("fused", ctx.FUSED_ALL), ("tail only", ctx.FUSED_ALL & ~34), ("pairs only", (ctx.FUSED_ALL & ~35) | 2 | 32), ("35 only", 35)):
+    for name, mask in (("unfused", ctx.FUSED_ALL & ~ctx.FUSED_TWO_UP), ("fused", ctx.FUSED_ALL), ("tail only", ctx.FUSED_ALL & ~(ctx.FUSED_DENSE_MID | ctx.FUSED_CONV1_STREAM)),
+                       ("pairs only", (ctx.FUSED_ALL & ~ctx.FUSED_TWO_UP) | ctx.FUSED_DENSE_MID | ctx.FUSED_CONV1_STREAM), ("two-up only", ctx.FUSED_TWO_UP)):
         ctx.set_fused(mask, 0)
         ctx.profile_begin()
         y1 = m.forward(ctx.to_device(x, torch.bfloat16)).float().cpu().numpy()
@@ -25,7 +26,7 @@ names = ["initial_conv"] + [f"rrdb_0_dense{d}_conv{c}" for d in (1, 2, 3) for c 
 ctx.set_fused(ctx.FUSED_ALL, 0)
 _, t1 = m.forward_with_taps(ctx.to_device(x, torch.bfloat16), names)
 _, t2 = m.forward_with_taps(ctx.to_device(x[perm], torch.bfloat16), names)
-ctx.set_fused(ctx.FUSED_ALL & ~35, 0)
+ctx.set_fused(ctx.FUSED_ALL & ~ctx.FUSED_TWO_UP, 0)
 _, t0 = m.forward_with_taps(ctx.to_device(x, torch.bfloat16), names)
 for n in names:
     a, b, u = t1[n].cpu().numpy()[1], t2[n].cpu().numpy()[0], t0[n].cpu().numpy()[1]
