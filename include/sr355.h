@@ -290,6 +290,33 @@ int  sr_edge_guided(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, int H
                     float* up_e_f32, void* stream);
 int  sr_freq_extrapolate(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, int H, int W, double* y_f64, void* stream);
 
+/* ---- the classical study's image-quality scores (profiling_methods.py:45-167 and skimage.metrics), B pairs of one shape ----
+ * sr_classic_scores: hr, sr DEVICE [B,H,W,C] (C 1: gray, 3: RGB), each SR_DTYPE_U8 or SR_DTYPE_F32 (hr_dtype, sr_dtype); H, W >= 7,
+ *   B <= 65535.  data_range_f64 DEVICE [B].  scores_f64 DEVICE [B,SR_NUM_SCORES], fp64, in SR_SCORE_* order:
+ *   psnr      skimage peak_signal_noise_ratio: 10 log10(dr^2 / mean((hr - sr)^2)), +inf for identical images;
+ *   ssim      skimage structural_similarity defaults: 7 x 7 uniform window, K1 0.01, K2 0.03, covariances x 49/48, S averaged over the
+ *             centres 3 pixels inside the border; RGB: the mean of the per-channel means;
+ *   mae       mean |hr - sr| over every channel (profiling_methods.py:45-47);
+ *   rmse      sqrt(mean((hr - sr)^2) + 1e-9) (:49-53);
+ *   grad_mse  mean((M_hr - M_sr)^2) (:79-85), M = sobel_mag (:58-77): ksize-3 Sobel magnitude, BORDER_REFLECT_101, of the gray image
+ *             divided by 255 when its own max > 1.5;
+ *   epi       (sum M_sr + 1e-9) / (sum M_hr + 1e-9) (:87-94);
+ *   hf_ratio  (sum_mask |F_sr| + 1e-9) / (sum_mask |F_hr| + 1e-9), F = fftshift(fft2(gray)) of the unscaled values, mask r >
+ *             hf_radius_frac (r_max + 1e-9) around (H / 2, W / 2) (:98-114);
+ *   kl_luma   sum P log(P / Q) of the 256-bin gray histograms (:116-137);
+ *   kl_color  the per-channel 64-bin form averaged over the channels (:139-167); NaN for C = 1.
+ *   Histograms bin as np.histogram(range=(0, 255), density=True) + 1e-12: uint8 values as they are, float as clip(x, 0, 1) * 255.
+ *   The gray image is the image itself for C = 1 and OpenCV's fixed-point COLOR_RGB2GRAY, (4899 R + 9617 G + 1868 B + 8192) >> 14, for
+ *   uint8 RGB; for RGB with a float image columns grad_mse .. kl_luma are NaN.
+ *   Optional raw outputs (NULL: not written; written only where the gray columns are defined): gray_f32 [B,2,H,W] the unscaled gray
+ *   images (hr, sr), sobel_f32 [B,2,H,W] their M, hist_luma_i32 [B,2,256] and hist_color_i32 [B,2,3,64] (C = 3) the counts.
+ *   Every reduction runs in a fixed order: a pair's scores are bitwise the same on every run and for any B. */
+enum { SR_SCORE_PSNR = 0, SR_SCORE_SSIM, SR_SCORE_MAE, SR_SCORE_RMSE, SR_SCORE_GRAD_MSE, SR_SCORE_EPI, SR_SCORE_HF_RATIO,
+       SR_SCORE_KL_LUMA, SR_SCORE_KL_COLOR, SR_NUM_SCORES };
+int  sr_classic_scores(sr_ctx* ctx, const void* hr, int hr_dtype, const void* sr, int sr_dtype, int B, int H, int W, int C,
+                       const double* data_range_f64, double hf_radius_frac, double* scores_f64, float* gray_f32, float* sobel_f32,
+                       int* hist_luma_i32, int* hist_color_i32, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

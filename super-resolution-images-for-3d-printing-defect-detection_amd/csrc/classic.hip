@@ -4,6 +4,7 @@
 //   frequency-domain zero-padding (as a separable fp64 DFT operator).
 // The resize steps reuse imgops.hip's tap tables (resize_taps_kernel) with sr_resize's rules, so every resize here is the one
 // sr_resize computes.
+#include "cgemm_f64.h"
 #include "common.h"
 
 #include <cmath>
@@ -327,80 +328,6 @@ __global__ void u8_to_f64_kernel(const uint8_t* x, int64_t n, double* y) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) y[i] = (double)x[i];
 }
 
-// C[b] (M x N, row-major, batch stride scb) = A[b] (M x K) . B[b] (K x N) with element strides (sa_m, sa_k), (sb_k, sb_n) and batch strides
-// sab, sbb (0: shared).  Complex where AI / BI say the operand has an imaginary part; ABS writes |C| to cr only.  64 x 64 tile per
-// 256-thread workgroup, 4 x 4 outputs per thread (rows tr + 16 i, cols tc + 16 j), K in steps of 16 through LDS.
-constexpr int GT = 64, GK = 16;
-
-template <bool AI, bool BI, bool ABS>
-__global__ void __launch_bounds__(256) cgemm_f64_kernel(int M, int N, int K, const double* ar, const double* ai, int64_t sa_m, int64_t sa_k, int64_t sab,
-                                                        const double* br, const double* bi, int64_t sb_k, int64_t sb_n, int64_t sbb,
-                                                        double* cr, double* ci, int64_t scb) {
-    constexpr bool CPLX = AI || BI;
-    __shared__ double Ar[GK][GT + 1], Ai[AI ? GK : 1][GT + 1], Br[GK][GT + 1], Bi[BI ? GK : 1][GT + 1];
-    const int64_t b = blockIdx.z;
-    const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT;
-    const int tr = threadIdx.x >> 4, tc = threadIdx.x & 15;
-    ar += b * sab; br += b * sbb;
-    if (AI) ai += b * sab;
-    if (BI) bi += b * sbb;
-    double accr[4][4] = {}, acci[4][4] = {};
-    for (int k0 = 0; k0 < K; k0 += GK) {
-        for (int q = threadIdx.x; q < GT * GK; q += 256) {
-            const int kk = q & (GK - 1), mm = q >> 4;                 // A tile: (m0 + mm, k0 + kk)
-            const int gm = m0 + mm, gk = k0 + kk;
-            const bool ok = gm < M && gk < K;
-            const int64_t off = (int64_t)gm * sa_m + (int64_t)gk * sa_k;
-            Ar[kk][mm] = ok ? ar[off] : 0.0;
-            if (AI) Ai[kk][mm] = ok ? ai[off] : 0.0;
-            const int nn = q & (GT - 1), kb = q >> 6;                  // B tile: (k0 + kb, n0 + nn)
-            const int gn = n0 + nn, gkb = k0 + kb;
-            const bool okb = gn < N && gkb < K;
-            const int64_t offb = (int64_t)gkb * sb_k + (int64_t)gn * sb_n;
-            Br[kb][nn] = okb ? br[offb] : 0.0;
-            if (BI) Bi[kb][nn] = okb ? bi[offb] : 0.0;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < GK; ++kk) {
-            double a_r[4], a_i[4], b_r[4], b_i[4];
-            for (int u = 0; u < 4; ++u) {
-                a_r[u] = Ar[kk][tr + 16 * u]; a_i[u] = AI ? Ai[kk][tr + 16 * u] : 0.0;
-                b_r[u] = Br[kk][tc + 16 * u]; b_i[u] = BI ? Bi[kk][tc + 16 * u] : 0.0;
-            }
-            for (int u = 0; u < 4; ++u)
-                for (int v = 0; v < 4; ++v) {
-                    accr[u][v] = fma(a_r[u], b_r[v], accr[u][v]);
-                    if (AI && BI) accr[u][v] = fma(-a_i[u], b_i[v], accr[u][v]);
-                    if (BI) acci[u][v] = fma(a_r[u], b_i[v], acci[u][v]);
-                    if (AI) acci[u][v] = fma(a_i[u], b_r[v], acci[u][v]);
-                }
-        }
-        __syncthreads();
-    }
-    for (int u = 0; u < 4; ++u)
-        for (int v = 0; v < 4; ++v) {
-            const int gm = m0 + tr + 16 * u, gn = n0 + tc + 16 * v;
-            if (gm >= M || gn >= N) continue;
-            const int64_t o = b * scb + (int64_t)gm * N + gn;
-            if (ABS) cr[o] = CPLX ? hypot(accr[u][v], acci[u][v]) : fabs(accr[u][v]);
-            else {
-                cr[o] = accr[u][v];
-                if (CPLX) ci[o] = acci[u][v];
-            }
-        }
-}
-
-template <bool ABS>
-void cgemm_dispatch(bool a_im, bool b_im, dim3 grid, hipStream_t st, int M, int N, int K, const double* ar, const double* ai, int64_t sa_m, int64_t sa_k,
-                    int64_t sab, const double* br, const double* bi, int64_t sb_k, int64_t sb_n, int64_t sbb, double* cr, double* ci, int64_t scb) {
-#define SR_CGEMM(AI_, BI_) hipLaunchKernelGGL((cgemm_f64_kernel<AI_, BI_, ABS>), grid, dim3(256), 0, st, M, N, K, ar, ai, sa_m, sa_k, sab, br, bi, sb_k, sb_n, sbb, cr, ci, scb)
-    if (a_im && b_im) SR_CGEMM(true, true);
-    else if (a_im) SR_CGEMM(true, false);
-    else if (b_im) SR_CGEMM(false, true);
-    else SR_CGEMM(false, false);
-#undef SR_CGEMM
-}
-
 // A_{N,n} of one shape: [N][n] real parts, then (n even) [N][n] imaginary parts; built once per context and shape
 int dft_operator(sr_ctx* ctx, int N, int n, hipStream_t st, const double** re, const double** im) {
     const int64_t key = ((int64_t)N << 32) | (uint32_t)n;
@@ -547,10 +474,10 @@ int sr_freq_extrapolate(sr_ctx* ctx, const uint8_t* x_u8, int B, int h, int w, i
     double* ti = t_cplx ? tr + nt : nullptr;
     hipLaunchKernelGGL(u8_to_f64_kernel, dim3(cls_grid(nx)), dim3(256), 0, st, x_u8, nx, xd);
     // T = X . A_W^T  (M = h, K = w, N = W; B(k, j) = A_W[j][k])
-    cgemm_dispatch<false>(false, t_cplx, dim3((W + GT - 1) / GT, (h + GT - 1) / GT, B), st, h, W, w, xd, nullptr, w, 1, (int64_t)h * w, awr, awi, 1, w, 0,
+    cgemm_dispatch<CG_STORE>(false, t_cplx, dim3((W + GT - 1) / GT, (h + GT - 1) / GT, B), st, h, W, w, xd, nullptr, w, 1, (int64_t)h * w, awr, awi, 1, w, 0,
                           tr, ti, (int64_t)h * W);
     // Y = | A_H . T |  (M = H, K = h, N = W)
-    cgemm_dispatch<true>(ahi != nullptr, t_cplx, dim3((W + GT - 1) / GT, (H + GT - 1) / GT, B), st, H, W, h, ahr, ahi, h, 1, 0, tr, ti, W, 1, (int64_t)h * W,
+    cgemm_dispatch<CG_ABS>(ahi != nullptr, t_cplx, dim3((W + GT - 1) / GT, (H + GT - 1) / GT, B), st, H, W, h, ahr, ahi, h, 1, 0, tr, ti, W, 1, (int64_t)h * W,
                          y_f64, nullptr, (int64_t)H * W);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;

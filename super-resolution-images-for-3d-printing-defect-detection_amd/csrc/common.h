@@ -52,7 +52,9 @@ struct sr_ctx {
     Arena attn_kn;                // attention: per-key-group largest key norm (stream-ordered reuse)
     Arena dev_w, dev_b, dev_x;    // sr_conv2d_dev: packed weights / padded bias / padded input of the call in flight (stream-ordered reuse)
     Arena cls_tab, cls_work, cls_fft;   // classic.hip: tap tables, per-call work buffers, the DFT products' operands (stream-ordered reuse)
-    std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape
+    std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape;
+                                                    // metrics.hip: -N -> the N x N DFT exp(-2 pi i k x / N)
+    Arena met_work, met_fft;            // metrics.hip: flags / partials / histograms, the DFT chunk's operands (stream-ordered reuse)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
     struct PackKey {

@@ -103,7 +103,11 @@ SIGNATURES = {
     "sr_nl_means": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp]),
     "sr_edge_guided": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sr_freq_extrapolate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_classic_scores": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+
+# the columns of sr_classic_scores (SR_SCORE_* in include/sr355.h)
+SCORE_NAMES = ("psnr", "ssim", "mae", "rmse", "grad_mse", "epi", "hf_ratio", "kl_luma", "kl_color")
 
 _lib = None
 

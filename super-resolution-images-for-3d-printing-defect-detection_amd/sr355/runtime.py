@@ -309,6 +309,55 @@ class Context:
         return y
 
     # ------------------------------------------------------------------ channel-range views (the training tape's dense blocks: sr_*_views)
+    # ------------------------------------------------------------------ the classical study's image-quality scores (profiling_methods.py:45-167)
+    SCORE_NAMES = L.SCORE_NAMES
+
+    def _score_data_range(self, hr, data_range):
+        B = hr.shape[0]
+        if isinstance(data_range, str):
+            if data_range != "hr_span":
+                raise ValueError(f"classic_scores: data_range must be a number, a per-pair array or 'hr_span', not {data_range!r}")
+            flat = hr.reshape(B, -1)
+            span = (flat.amax(1) - flat.amin(1)).to(torch.float64)       # in hr's own dtype first, as the notebook's numpy scalars
+            return torch.where(span == 0, torch.full_like(span, 255.0), span).contiguous()
+        if isinstance(data_range, torch.Tensor):
+            dr = data_range.to(self.torch_device, torch.float64).reshape(-1)
+        else:
+            dr = torch.as_tensor(np.asarray(data_range, dtype=np.float64).reshape(-1), device=self.torch_device)
+        if dr.numel() == 1:
+            dr = dr.expand(B)
+        if dr.numel() != B:
+            raise ValueError(f"classic_scores: data_range has {dr.numel()} entries for {B} pairs")
+        return dr.contiguous()
+
+    def classic_scores(self, hr, sr, data_range=255.0, hf_radius_frac=0.6, raw=False):
+        """The nine scores of each pair (sr_classic_scores; columns SCORE_NAMES) -> float64 [B, 9] on the device.
+        hr, sr: [B,H,W] (gray) or [B,H,W,3] (RGB) device tensors, each uint8 or float32, H and W >= 7.  data_range: a number, a [B]
+        array / tensor, or 'hr_span' (max(hr) - min(hr) per pair, 255 where that is 0: the notebook's NL-means rule).
+        raw=True -> (scores, dict of the intermediates: 'gray' and 'sobel' float32 [B,2,H,W] (hr, sr), 'hist_luma' int32 [B,2,256],
+        'hist_color' int32 [B,2,3,64] for RGB).  For float RGB pairs the gray-derived columns are NaN and the gray intermediates unset."""
+        _check_tensor(self, hr, "classic_scores hr", (torch.uint8, torch.float32))
+        _check_tensor(self, sr, "classic_scores sr", (torch.uint8, torch.float32))
+        if hr.shape != sr.shape or hr.dim() not in (3, 4) or (hr.dim() == 4 and hr.shape[3] not in (1, 3)):
+            raise ValueError(f"classic_scores: expected two [B,H,W] or [B,H,W,3] batches of one shape, got {tuple(hr.shape)} and {tuple(sr.shape)}")
+        B, H, W = hr.shape[:3]
+        Cx = hr.shape[3] if hr.dim() == 4 else 1
+        if H < 7 or W < 7:
+            raise ValueError(f"classic_scores: images of {H} x {W} are smaller than the 7 x 7 SSIM window")
+        dr = self._score_data_range(hr, data_range)
+        out = self.empty((B, len(self.SCORE_NAMES)), torch.float64)
+        inter = None
+        if raw:
+            inter = {"gray": self.empty((B, 2, H, W)), "sobel": self.empty((B, 2, H, W)),
+                     "hist_luma": self.empty((B, 2, 256), torch.int32)}
+            if Cx == 3:
+                inter["hist_color"] = self.empty((B, 2, 3, 64), torch.int32)
+        ptr = (lambda k: None if inter is None or k not in inter else inter[k].data_ptr())
+        self.check(self.lib.sr_classic_scores(self.h, hr.data_ptr(), dtype_code(hr.dtype), sr.data_ptr(), dtype_code(sr.dtype), B, H, W, Cx,
+                                              dr.data_ptr(), float(hf_radius_frac), out.data_ptr(), ptr("gray"), ptr("sobel"),
+                                              ptr("hist_luma"), ptr("hist_color"), self.stream()))
+        return (out, inter) if raw else out
+
     @staticmethod
     def _view(t, coff, c):
         """(tensor [B,H,W,Cbuf] fp32 contiguous, first channel, channels) -> sr_view."""
