@@ -9,7 +9,12 @@ N>1 default = SURVEY.md 8(e)'s partition: the 16-tile batch is split B/g over th
 GPU at 1/2/4/8); --scaling weak gives every rank its own 16 tiles.  value = SR output megapixels of all ranks / wall time
 (max over ranks).
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Everything else the bench measures or checks
+(the HIP-event per-kernel pass and its roofline, the all-zero DVFS step, the clock reading, cpu_baseline, parity, parity_trained_like and
+the other BASELINE rows) runs after the timed steps under --full only; the --no-* options thin a --full run.
+
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full              (+ roofline, kernels, cpu_baseline, parity, rows)
     python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR     (+ the last timed step's outputs as DIR/*.npy, see dump_outputs)
     python bench.py --gpus N ...          (no torchrun environment: bench.py starts the N ranks itself, see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -316,22 +321,25 @@ def main():
     ap.add_argument("--tiles-per-call", type=int, default=16,
                     help="LR tiles whose patches share the generator launches (16 = the whole per-GPU batch: 7056 patches, ~115 GB of workspace)")
     ap.add_argument("--streams", type=int, default=1, help="independent HIP streams (one generator instance each) the tiles are dealt to")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the HIP-event per-kernel pass (no roofline object)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline does not need: the HIP-event per-kernel pass (roofline, kernels), the clock reading "
+                         "and, at N = 1, the all-zero DVFS step, cpu_baseline, parity, parity_trained_like and the other BASELINE rows; the --no-* options skip parts of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the HIP-event per-kernel pass (no roofline object)")
     ap.add_argument("--no-attention", action="store_true", help="non-reference graph, kernel tuning only")
     ap.add_argument("--scaling", choices=("strong", "weak"), default=None,
                     help="N>1: strong (default) = the 16-tile batch split over the ranks (SURVEY.md 8e); weak = 16 tiles per rank")
     ap.add_argument("--tiles", type=int, default=TILES_PER_GPU, help="tiles this rank processes at N=1 (profiles/: 2/4/8/16 = what a rank sees at N=8/4/2/1)")
     ap.add_argument("--raw-glorot", action="store_true",
                     help="round 1's weights: glorot without conditioning the attention logits (sr355.weights.condition_attention)")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity objects")
     ap.add_argument("--zero-data", action="store_true",
                     help="DIAGNOSTIC, not a result: all-zero weights and tiles -- the same launches with no bit toggling in the operands (MI355X_MICROARCH.md DVFS item 1): what the "
                          "kernels' times become when the chip does not give clock back to data-dependent power; the line says so in `data`")
     ap.add_argument("--no-zero-step", action="store_true",
-                    help="skip the in-run DVFS diagnostic (one extra pair of steps on all-zero operands): for the rocprofv3 --stats collection, whose per-kernel averages "
+                    help="--full: skip the in-run DVFS diagnostic (one extra pair of steps on all-zero operands): for the rocprofv3 --stats collection, whose per-kernel averages "
                          "then cover real-data launches only and are directly comparable with roofline.avg_launch_ms")
-    ap.add_argument("--no-rows", action="store_true", help="skip the other BASELINE rows (cfg3 training step, cfg4 streaming) that the N = 1 line carries beside the headline")
+    ap.add_argument("--no-rows", action="store_true", help="--full: skip the other BASELINE rows (cfg3 training step, cfg4 streaming) that the N = 1 line carries beside the headline")
     ap.add_argument("--fused", type=int, default=511,
                     help="dense-block conv pairs run as one fused kernel: bit 0 conv4+conv5, bit 1 conv2+conv3, bit 2 final_conv2 inside final_conv1, bit 3 attention projections inside the producing conv (0 = layer by layer, for A/B runs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -344,6 +352,7 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    profile = args.full and not args.no_profile
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -467,10 +476,10 @@ def main():
     del last
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    # the same K steps again with a HIP-event pair around every hot-kernel launch (on the launching stream):
+    # --full: the same K steps again with a HIP-event pair around every hot-kernel launch (on the launching stream):
     # per-kernel durations for the roofline object.  `value` comes from the un-instrumented pass above.
     prof, elapsed_prof = [], None
-    if not args.no_profile:
+    if profile:
         ctx.profile_begin()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -478,11 +487,11 @@ def main():
         fence()
         elapsed_prof = time.perf_counter() - t1
         prof = ctx.profile_end()
-    # DVFS diagnostic inside the run (MI355X_MICROARCH.md "DVFS give-back" item 1; N = 1 only, outside the timed region): the same launches once more on
+    # --full: DVFS diagnostic inside the run (MI355X_MICROARCH.md "DVFS give-back" item 1; N = 1 only, outside the timed region): the same launches once more on
     # all-zero weights and tiles -- what the dominant kernel's instruction stream sustains when no operand bit toggles and the chip keeps its clock
     zero_prof = None
     res = out.cpu().numpy()                      # the metric sums of the measured steps (the diagnostic below overwrites the device tensor)
-    if not args.no_profile and world == 1 and not args.zero_data and not args.no_zero_step and n_mine:
+    if profile and world == 1 and not args.zero_data and not args.no_zero_step and n_mine:
         zw = {n: (np.zeros_like(k), np.zeros_like(b)) for n, (k, b) in weights.items()}
         lr_keep = lr
         for m_ in models:
@@ -502,7 +511,7 @@ def main():
 
     if rank == 0:
         mpix = global_tiles * (LR * SCALE) ** 2 / 1e6
-        clock_mhz = None if args.no_profile else ctx.measure_clock_mhz()
+        clock_mhz = ctx.measure_clock_mhz() if profile else None
         roof = None
         if prof:
             prof.sort(key=lambda r: -r["total_ms"])
@@ -530,7 +539,7 @@ def main():
             "config": {"workload": f"BASELINE configs[2]: ESRGAN-RRDB x4 (NB=23,G=32,2xSelfAttention) on a batch of {global_tiles} LR tiles 512x512, "
                                    "reference patch mode p=48 s=24 (441 patches/tile)" + (" [NO-ATTENTION tuning variant]" if args.no_attention else ""),
                        "tiles_this_rank": n_mine, "global_batch": global_tiles, "patches_per_forward": min(args.chunk, 441 * max(n_mine, 1)),
-                       "tiles_per_call": args.tiles_per_call, "fused_dense_pairs_mask": args.fused,
+                       "tiles_per_call": args.tiles_per_call, "fused_dense_pairs_mask": args.fused, "full": args.full,
                        "fused_mask_bits": "1 conv4+conv5, 2 conv2+conv3, 4 final_conv2 inside final_conv1, 8 attention projections inside the producing conv, 16 packed small-image batches (classifier), 32 conv1 of a dense block on the streaming kernel, 64 max-pool inside the conv in front of it (classifier), 128 64-input-channel 3x3 convs on the persistent kernel, 256 SRCNN's 1x1 conv inside the 9x9 head's epilogue",
                        "distinct_tiles": 4, "tile_of_batch_index": "batch tile t is synthetic tile t % 4 (4 distinct 512x512 tiles, each 4 times; nothing is cached between tiles)",
                        "world_size_env": world, "world_size_process_group": group_world, "dist_backend": (torch.distributed.get_backend() if world > 1 else None),
@@ -547,9 +556,10 @@ def main():
         if dumped is not None:
             line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         kept = {}
-        if world == 1 and not args.no_cpu_baseline:
+        full_n1 = args.full and world == 1
+        if full_n1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(weights, lr4[0], keep=kept)
-        if world == 1 and not args.no_parity and not args.no_attention and not args.zero_data:
+        if full_n1 and not args.no_parity and not args.no_attention and not args.zero_data:
             line["parity"] = parity_object(ctx, model, weights, lr4[0], hr4[0], kept.get("fp32_reference_graph"))
             line["parity"]["weights"] = "the timed step's: seeded glorot-uniform (PSNR vs HR ~9.6 dB: the generator's output is noise relative to HR)"
             # the same figures where they can fail: a generator whose output resembles HR
@@ -558,7 +568,7 @@ def main():
             except Exception as e:      # noqa: BLE001 -- reported in the line, the headline stands
                 line["parity_trained_like"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             model.set_weights(weights)
-        if world == 1 and not args.no_rows and not args.no_attention and not args.zero_data:
+        if full_n1 and not args.no_rows and not args.no_attention and not args.zero_data:
             # BASELINE configs[3] and configs[4] beside the headline, outside its timed region (~25 s): so that the driver's record carries them.
             # A failure here must not cost the headline line.
             from sr355 import bench_rows as BR

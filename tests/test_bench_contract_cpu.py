@@ -81,6 +81,24 @@ def test_main_self_launches_for_gpus_gt_1_without_torchrun_env_and_relays_the_ex
     assert e.value.code == 7 and seen == {"n": 2, "argv": ["--gpus", "2", "--steps", "1"]}
 
 
+def test_full_is_an_option_of_its_own_and_reaches_every_rank(bench, monkeypatch):
+    """--full (what the line carries beyond the headline) parses, is off by default, and goes to the self-launched ranks unchanged."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "2", "--steps", "1", "--full", "--no-rows"])
+    seen = {}
+
+    def fake_launch(n, argv):
+        seen["argv"] = list(argv)
+        return 0
+    monkeypatch.setattr(bench, "launch_ranks", fake_launch)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and seen["argv"] == ["--gpus", "2", "--steps", "1", "--full", "--no-rows"]
+    monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--full", "--steps", "0"])       # parsed, then refused for --steps alone
+    with pytest.raises(SystemExit, match="--steps must be"):
+        bench.main()
+
+
 def test_main_rejects_a_world_size_that_disagrees_with_gpus(bench, monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "4")
     monkeypatch.setattr(bench.sys, "argv", ["bench.py", "--gpus", "2"])

@@ -38,3 +38,20 @@ def test_dump_outputs_are_the_timed_steps_results_and_reproducible(tmp_path):
     _bench(tmp_path / "b")
     for n in names:
         assert np.array_equal(a[n], np.load(tmp_path / "b" / f"{n}.npy")), n
+
+
+def test_plain_run_carries_the_headline_and_nothing_that_needs_runs_of_its_own():
+    """Without --full the line holds the headline and what the timed steps give anyway; the per-kernel pass, the clock reading, the CPU baseline,
+    the parity objects and the other BASELINE rows are --full's."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--tiles", "2", "--tiles-per-call", "2"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "4x-SR MPix/s on 512x512 LR batch" and line["unit"] == "MPix/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(2 * 2048 * 2048 / 1e6 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["config"]["full"] is False and line["roofline"] is None and line["kernels"] == []
+    assert not {"cpu_baseline", "parity", "parity_trained_like", "rows", "dump_outputs"} & set(line)

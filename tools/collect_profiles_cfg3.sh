@@ -17,7 +17,7 @@ cp "$(find "$OUT/train" -name "*kernel_stats.csv" | head -1)" "$OUT/${TAG}_cfg3_
 rm -rf "$OUT/train"
 echo "cfg3 done"
 fi
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o bench -- python3 bench.py --steps 2 --warmup 1 --no-rows --no-parity --no-zero-step > "$OUT/${TAG}_bench.tmp" 2> "$OUT/bench.err" || { echo "bench profile failed"; tail -5 "$OUT/bench.err"; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench" -o bench -- python3 bench.py --steps 2 --warmup 1 --full --no-rows --no-parity --no-zero-step > "$OUT/${TAG}_bench.tmp" 2> "$OUT/bench.err" || { echo "bench profile failed"; tail -5 "$OUT/bench.err"; exit 1; }
 tail -1 "$OUT/${TAG}_bench.tmp" > "$OUT/${TAG}_bench.json"; rm -f "$OUT/${TAG}_bench.tmp"
 cp "$(find "$OUT/bench" -name "*kernel_stats.csv" | head -1)" "$OUT/${TAG}_bench_kernel_stats.csv"
 rm -rf "$OUT/bench"
