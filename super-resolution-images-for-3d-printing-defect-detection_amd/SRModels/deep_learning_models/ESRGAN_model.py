@@ -137,7 +137,7 @@ class ESRGAN(DeviceModelMixin):
         (round 3 left the trainer on the old parameters without an error)."""
         super().set_weights(weights, trained)
         tr = getattr(self, "_trainer", None)
-        if tr is not None and weights is not tr._gw:
+        if tr is not None and weights is not tr.g_params.arrays:
             tr.load_generator_weights(self.weights)
 
     def _sync_from_trainer(self):

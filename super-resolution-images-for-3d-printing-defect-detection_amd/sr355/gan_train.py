@@ -15,11 +15,13 @@ Tiny vectors -- the discriminator's [B,256] dense head, BCE on [B,1], spectral-n
 Parameters are uploaded once per step and packed into MFMA fragment order on the device per layer call (sr_conv2d_dev); the
 optimisers and the tape bookkeeping stay on the host.  cfg3's throughput is recorded by tools/bench_train.py, not yet a bench line.
 """
+import contextlib
+
 import numpy as np
 import torch
 
 from . import _lib as L
-from .train import Adam, DeviceAdam, _rot
+from .train import Adam, DeviceAdam, ParamBucket, _rot
 
 
 # ----------------------------------------------------------------------------------------------------------------- tape
@@ -345,22 +347,16 @@ class ESRGANTrainer:
         # the per-layer tensors the tape multiplies with are views of it, the gradients are gathered into a bucket of the same order, and
         # the optimiser is one fused kernel (round 2: NumPy Adam on the host, 65 ms of a 258 ms step, plus 70 MB each way over PCIe).
         # `self.gw` stays available as host arrays: they are refreshed from the device when somebody reads them.
-        self._gw = {n: (np.array(k, np.float32), np.array(b, np.float32)) for n, (k, b) in g_weights.items()}
-        arrs = [a for pair in self._gw.values() for a in pair]
-        self._gflat = ctx.to_device(np.concatenate([a.ravel() for a in arrs]))
-        self._gdev, o = {}, 0
-        for a in arrs:
-            self._gdev[id(a)] = (a, self._gflat[o:o + a.size].view(tuple(a.shape)))
-            o += a.size
-        self._g_host_stale = False
+        self.g_params = ParamBucket(ctx, g_weights)
         # d_weights / vgg_weights None: a generator-only trainer (pixel_step: sr355.recipes' L1 fit); train_step then refuses
         self.dw = None if d_weights is None else {n: (np.asarray(k, np.float32), np.asarray(b, np.float32)) for n, (k, b) in d_weights.items()}
         self.vw = vgg_weights
+        self._vgg = self._vgg_src = None                   # the frozen VGG19 on the device (a bucket of self.vw), uploaded by train_step
         rng = np.random.default_rng(u_seed)               # tfa initialises u ~ TruncatedNormal(stddev 0.02), shape [1, Cout]
         self.u = None if self.dw is None else {n: np.clip(rng.normal(0, 0.02, (1, self.dw[n][0].shape[-1])), -0.04, 0.04).astype(np.float32)
                                                for n in DISC_LAYERS}
         self.g_lr0, self.d_lr0 = g_lr, d_lr
-        self.g_opt = DeviceAdam(ctx, self._gflat, g_lr, epsilon=1e-7)
+        self.g_opt = DeviceAdam(ctx, self.g_params.flat, g_lr, epsilon=1e-7)
         self.d_opt = None if self.dw is None else Adam(self.dw, d_lr, epsilon=1e-7)
         self.step = 0
         # data parallel: `allreduce` = callable(dict of host grads) -> averaged dict (the discriminator's, whose spectral normalisation lives on
@@ -370,35 +366,28 @@ class ESRGANTrainer:
         self._last = None
         self._packs = {}
 
-    def _prepack(self, with_vgg):
-        """Pack every generator (and VGG19) conv's weights for its forward and its input-gradient use by ONE launch (sr_conv_prepack; ~700 of a step's ~800 per-use
-        packs, 3.5 ms of 53).  The discriminator's kernels are renormalised inside the step and keep packing per use.  The list lives until `_unpack`, which every
-        step calls before it returns: nobody else on this context may meet a pack older than the weights."""
+    @contextlib.contextmanager
+    def _prepacked(self, with_vgg):
+        """Pack every generator (and VGG19) conv's weights for its forward and its input-gradient use by ONE launch (sr_conv_prepack; ~700 of a step's ~800
+        per-use packs, 3.5 ms of 53) for the duration of the block.  The discriminator's kernels are renormalised inside the step and keep packing per use.
+        The list is dropped when the block ends: nobody else on this context may meet a pack older than the weights."""
         if with_vgg not in self._packs:
             uses = []
-            devs = [(self._gw, self._gdev)] + ([(self.vw, self._vggc)] if with_vgg else [])
-            for w, dev in devs:
-                for k, b in w.values():
-                    if getattr(k, "ndim", 0) == 4 and k.shape[0] == k.shape[1] and k.shape[0] in (1, 3) and id(k) in dev and id(b) in dev:
-                        kd, bd = dev[id(k)][1], dev[id(b)][1]
+            for params in [self.g_params] + ([self._vgg] if with_vgg else []):
+                for kd, bd in params.dev.values():
+                    if kd.dim() == 4 and kd.shape[0] == kd.shape[1] and kd.shape[0] in (1, 3):
                         uses += [(kd, bd, False), (kd, None, True)]
             self._packs[with_vgg] = self.ctx.pack_list(uses)
         self.ctx.conv_prepack(self._packs[with_vgg])
-
-    def _unpack(self):
-        self.ctx.conv_prepack(None)
+        try:
+            yield
+        finally:
+            self.ctx.conv_prepack(None)
 
     @property
     def gw(self):
         """{layer: (kernel, bias)} host copies of the generator's parameters (refreshed from the device bucket when it has moved on)."""
-        if self._g_host_stale:
-            flat, o = self._gflat.cpu().numpy(), 0
-            for pair in self._gw.values():
-                for a in pair:
-                    np.copyto(a, flat[o:o + a.size].reshape(a.shape))
-                    o += a.size
-            self._g_host_stale = False
-        return self._gw
+        return self.g_params.host()
 
     @gw.setter
     def gw(self, weights):
@@ -407,49 +396,15 @@ class ESRGANTrainer:
     def load_generator_weights(self, weights, reset_optimizer=True):
         """Replace the generator's parameters (ESRGAN.set_weights / load after the trainer exists): copies into the device bucket in
         parameter order; by default Adam's moments and step count start over, as a freshly compiled Keras model's would."""
-        if set(weights) != set(self._gw):
-            raise ValueError("generator weights: layer names differ from the trainer's graph")
-        parts = []
-        for n, pair in self._gw.items():
-            for a, new in zip(pair, weights[n]):
-                new = np.asarray(new, np.float32)
-                if new.shape != a.shape:
-                    raise ValueError(f"{n}: shape {new.shape} != {a.shape}")
-                np.copyto(a, new)
-                parts.append(a.ravel())
-        self._gflat.copy_(self.ctx.to_device(np.concatenate(parts)))
-        self._g_host_stale = False
+        self.g_params.load(weights)
         if reset_optimizer:
             self.g_opt.m.zero_()
             self.g_opt.v.zero_()
             self.g_opt.t = 0
 
-    def _bucket_to_dict(self, flat):
-        """flat host array in parameter order -> {layer: (dk, db)} views"""
-        out, o = {}, 0
-        for n, pair in self._gw.items():
-            pr = []
-            for a in pair:
-                pr.append(flat[o:o + a.size].reshape(a.shape))
-                o += a.size
-            out[n] = tuple(pr)
-        return out
-
-    def _gather_grads(self, grads):
-        """{layer: [dk, db]} device tensors of the generator's tape -> one flat device bucket in parameter order (zeros where the loss does
-        not reach a variable: its moments and value then stay put, as Keras' skipping of None gradients leaves them)."""
-        parts = []
-        for n, pair in self._gw.items():
-            g = grads.get(n)
-            for s_, a in enumerate(pair):
-                t = None if g is None else g[s_]
-                parts.append(torch.zeros(a.size, dtype=torch.float32, device=self._gflat.device) if t is None else
-                             (t if isinstance(t, torch.Tensor) else self.ctx.to_device(np.asarray(t, np.float32))).reshape(-1))
-        return torch.cat(parts)
-
     def generator_tape(self, wgrad=True):
         """A tape over the generator's device-resident parameters (no upload, no host copy)."""
-        return Tape(self.ctx, self._gw, wgrad=wgrad, devcache=dict(self._gdev))
+        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache))
 
     @property
     def last_grads(self):
@@ -457,9 +412,22 @@ class ESRGANTrainer:
         if self._last is None:
             return None
         if "g" not in self._last:
-            full = self._bucket_to_dict(self._last.pop("g_flat").cpu().numpy())
+            full = self.g_params.split(self._last.pop("g_flat").cpu().numpy())
             self._last["g"] = {n: full[n] for n in full if n in self._last["g_names"]}     # only the variables the loss reaches, as Keras reports them
         return self._last
+
+    def _update_generator(self, grads):
+        """The generator's Adam step from its tape's gradients (averaged over the ranks first when data parallel) -> the flat gradient applied."""
+        g_flat = self.g_params.gather(grads)
+        if self.allreduce_flat is not None:
+            g_flat = self.allreduce_flat(g_flat)
+        elif self.allreduce is not None:                   # dict route (host): the 2-rank gloo tests
+            g_flat = self.ctx.to_device(self.g_params.flatten(self.allreduce(self.g_params.split(g_flat.cpu().numpy()))))
+        self.g_opt.lr = staircase_lr(self.g_lr0, self.step)
+        self.g_opt.apply(self.g_params.flat, g_flat)
+        self.g_params.stale = True
+        self.step += 1
+        return g_flat
 
     def _host(self, grads):
         """{layer: [dk, db]} (device tensors, or host arrays for the discriminator's dense head) -> host fp32 arrays; the device ones
@@ -479,62 +447,37 @@ class ESRGANTrainer:
                     out[n][s] = np.asarray(pair[s], np.float32)
         return {n: (a, b) for n, (a, b) in out.items()}
 
-    def _upload(self, weights, cache):
-        """All arrays of a parameter dict in one host-to-device copy; `cache` (Tape.devcache) then maps every array to its view."""
-        arrs = [a for pair in weights.values() for a in pair]
-        flat = self.ctx.to_device(np.concatenate([np.asarray(a, np.float32).ravel() for a in arrs]))
-        o = 0
-        for a in arrs:
-            cache[id(a)] = (a, flat[o:o + a.size].view(tuple(a.shape)))
-            o += a.size
-
     def pixel_step(self, lr_images, hr_images):
         """One generator update on the pixel loss alone (mean |hr - G(lr)|, ESRGAN_model.py:433-445; the generator half of _train_step,
         :506-531, without the adversarial / perceptual / spectral terms): sr355.recipes' fit.  -> the L1 value before the update."""
         ctx = self.ctx
         lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
-        tg = Tape(ctx, self._gw, devcache=dict(self._gdev))
-        self._prepack(False)
-        try:
+        tg = self.generator_tape()
+        with self._prepacked(False):
             y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
             pix = float(ctx.l1(hr_t, y.v).item())
             y.g = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 1.0 / y.v.numel(), 0.0)
             tg.backward()
-        finally:
-            self._unpack()
-        g_flat = self._gather_grads(tg.grads)
-        if self.allreduce_flat is not None:
-            g_flat = self.allreduce_flat(g_flat)
-        self.g_opt.lr = staircase_lr(self.g_lr0, self.step)
-        self.g_opt.apply(self._gflat, g_flat)
-        self._g_host_stale = True
-        self.step += 1
+        self._update_generator(tg.grads)
         return pix
 
     def train_step(self, lr_images, hr_images):
         """-> {'g_loss', 'd_loss', parts...}; weights, u, optimiser states advance in place (ESRGAN_model.py:475-533)."""
         if self.dw is None or self.vw is None:
             raise RuntimeError("ESRGANTrainer was built without discriminator / VGG19 weights: only pixel_step is available")
-        if not hasattr(self, "_vggc"):
-            self._vggc = {}                                # the frozen VGG19 stays on the device
-            self._upload(self.vw, self._vggc)
-        self._prepack(True)                                # the generator's weights change only in the step's last line, VGG19's never
-        try:
+        if self._vgg_src is not self.vw:                  # the first step, or ESRGAN.set_loss_network_weights has replaced the VGG19 weights
+            self._vgg, self._vgg_src = ParamBucket(self.ctx, self.vw), self.vw
+            self._packs.pop(True, None)
+        with self._prepacked(True):                        # the generator's weights change only in the step's last lines, VGG19's never
             return self._train_step(lr_images, hr_images)
-        finally:
-            self._unpack()
 
     def _train_step(self, lr_images, hr_images):
         ctx = self.ctx
         lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
-        devc = {}                                          # device copies of this step's parameter arrays (one upload per array)
-        if not hasattr(self, "_vggc"):
-            self._vggc = {}                                # the frozen VGG19 stays on the device
-            self._upload(self.vw, self._vggc)
-        devc.update(self._gdev)                            # the generator's parameters are already there (views of the flat bucket)
         # The reference runs the generator twice per step, once under each tape (ESRGAN_model.py:490, :508); its weights do not change
         # in between (the discriminator is updated first), so both runs are the same tensor: one taped forward serves both.
-        tg = Tape(ctx, self._gw, devcache=devc)
+        tg = self.generator_tape()
+        devc = tg.dev                                      # the discriminator's tapes add this step's uploads of its arrays (one per array)
         collect = getattr(self, "collect_masks", False)           # tests: the activation branches of this step's forward passes (oracle/train.py _masked_act)
         self.last_masks = {"g": {}, "d_real": {}, "d_fake": {}} if collect else None
         if collect:
@@ -571,7 +514,7 @@ class ESRGANTrainer:
         adv, dp = bce_mean(np.ones_like(p), p)
         seed(dp)
         td3.backward()
-        tv = Tape(ctx, self.vw, wgrad=False, devcache=self._vggc)
+        tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
         fr = vgg19_features(tv, Var(hr_t, need=False))
         tv.ops = []
         yv2 = Var(y.v)
@@ -588,17 +531,7 @@ class ESRGANTrainer:
         y.g = dy
         self.last_dy = dy
         tg.backward()
-        g_flat = self._gather_grads(tg.grads)
-        if self.allreduce_flat is not None:
-            g_flat = self.allreduce_flat(g_flat)
-        elif self.allreduce is not None:                   # dict route (host): the 2-rank gloo tests
-            avg = self.allreduce(self._bucket_to_dict(g_flat.cpu().numpy()))
-            g_flat = ctx.to_device(np.concatenate([np.asarray(a, np.float32).ravel() for n in self._gw for a in avg[n]]))
-        self.g_opt.lr = staircase_lr(self.g_lr0, self.step)
-        self.g_opt.apply(self._gflat, g_flat)
-        self._g_host_stale = True
-        self.step += 1
-        self._last = {"g_flat": g_flat, "g_names": set(tg.grads), "d": d_grads}
+        self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads), "d": d_grads}
         self.last_fake = fake
         return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
                 "pixel": pix, "spectral": spec}

@@ -22,26 +22,83 @@ def _rot(w):
     return np.ascontiguousarray(w[::-1, ::-1].transpose(0, 1, 3, 2))
 
 
-class DevWeights:
-    """A parameter dict on the device for one optimiser step: one flat upload, per-array views; conv / dgrad run on them through
-    sr_conv2d_dev (packed into MFMA fragment order by a device kernel, no host re-pack per call)."""
+class ParamBucket:
+    """A parameter dict {layer: (kernel, bias)} on the device as ONE flat fp32 tensor `flat` in parameter order -- every layer's kernel then
+    its bias, in dict order -- with views of it per array: `dev[layer][slot]`, and `devcache` (id(host array) -> (host array, view)) for a
+    Tape.  The host arrays `arrays` are views of one host buffer; whoever writes `flat` sets `stale`, and `host()` downloads it on the next
+    read.  conv / dgrad run on the views through sr_conv2d_dev (packed into MFMA fragment order by a device kernel, no host re-pack per call)."""
 
-    def __init__(self, ctx, w):
+    def __init__(self, ctx, weights):
         self.ctx = ctx
-        arrs = [(n, s, np.asarray(a, np.float32)) for n, pair in w.items() for s, a in enumerate(pair)]
-        flat = ctx.to_device(np.concatenate([a.ravel() for _, _, a in arrs]))
-        self.t, o = {}, 0
-        for n, s, a in arrs:
-            self.t[(n, s)] = flat[o:o + a.size].view(tuple(a.shape))
-            o += a.size
+        weights = {n: [np.asarray(a, np.float32) for a in pair] for n, pair in weights.items()}
+        self.shapes = {n: [a.shape for a in pair] for n, pair in weights.items()}
+        self._hflat = self.flatten(weights)
+        self.flat = ctx.to_device(self._hflat)
+        self.arrays, self.dev = self.split(self._hflat), self.split(self.flat)
+        self.devcache = {id(a): (a, v) for n in self.dev for a, v in zip(self.arrays[n], self.dev[n])}
+        self.stale = False
+
+    def flatten(self, weights):
+        """{layer: (kernel, bias)} with this bucket's layer names and shapes -> one fp32 host array in parameter order."""
+        if set(weights) != set(self.shapes):
+            raise ValueError("parameter dict: layer names differ from the bucket's")
+        parts = []
+        for n, shapes in self.shapes.items():
+            for a, shape in zip(weights[n], shapes):
+                a = np.asarray(a, np.float32)
+                if a.shape != shape:
+                    raise ValueError(f"{n}: shape {a.shape} != {shape}")
+                parts.append(a.ravel())
+        return np.concatenate(parts)
+
+    def split(self, flat):
+        """A flat host array or device tensor in parameter order -> {layer: (kernel, bias)} of views into it."""
+        out, o = {}, 0
+        for n, shapes in self.shapes.items():
+            pair = []
+            for shape in shapes:
+                size = int(np.prod(shape))
+                pair.append(flat[o:o + size].reshape(shape))
+                o += size
+            out[n] = tuple(pair)
+        return out
+
+    def host(self):
+        """`arrays`, refreshed from the device first when `flat` has moved on."""
+        if self.stale:
+            self._hflat[:] = self.flat.cpu().numpy()
+            self.stale = False
+        return self.arrays
+
+    def load(self, weights):
+        """New values for every array (same layer names and shapes), on the host and on the device."""
+        self._hflat[:] = self.flatten(weights)
+        self.flat.copy_(self.ctx.to_device(self._hflat))
+        self.stale = False
+
+    def gather(self, grads):
+        """{layer: [dk, db]} device tensors -> one flat device tensor in parameter order (zeros where the loss does not reach a variable:
+        its moments and value then stay put, as Keras' skipping of None gradients leaves them)."""
+        parts = []
+        for n, views in self.dev.items():
+            g = grads.get(n)
+            for s, v in enumerate(views):
+                parts.append(torch.zeros(v.numel(), dtype=torch.float32, device=v.device) if g is None or g[s] is None else g[s].reshape(-1))
+        return torch.cat(parts)
 
     def conv(self, x, name, **kw):
-        k = self.t[(name, 0)]
-        return self.ctx.conv2d_dev(x, k, self.t[(name, 1)], k.shape[3], **kw)
+        k, b = self.dev[name]
+        return self.ctx.conv2d_dev(x, k, b, k.shape[3], **kw)
 
     def dgrad(self, dy, name):
-        k = self.t[(name, 0)]
+        k = self.dev[name][0]
         return self.ctx.conv2d_dev(dy, k, None, k.shape[2], rot=True)
+
+
+def _next_lr_t(opt):
+    """Advance an Adam's step count -> that step's bias-corrected rate lr sqrt(1 - b2^t) / (1 - b1^t) in fp32 (both Adams below)."""
+    opt.t += 1
+    return np.float32(opt.lr * np.sqrt(1.0 - opt.b2 ** opt.t) / (1.0 - opt.b1 ** opt.t))
 
 
 class Adam:
@@ -54,8 +111,7 @@ class Adam:
         self.v = {n: [np.zeros_like(k), np.zeros_like(b)] for n, (k, b) in weights.items()}
 
     def apply(self, weights, grads):
-        self.t += 1
-        lr_t = np.float32(self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t))
+        lr_t = _next_lr_t(self)
         out = {}
         for n, (k, b) in weights.items():
             if n not in grads:                                     # a variable the loss does not reach: Keras skips None gradients
@@ -81,21 +137,18 @@ class DeviceAdam:
     (the kernel rounds every operation separately, in NumPy's order)."""
 
     def __init__(self, ctx, flat_weights, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        import torch
         self.ctx, self.lr, self.b1, self.b2, self.eps = ctx, float(learning_rate), beta_1, beta_2, epsilon
         self.t = 0
         self.m, self.v = torch.zeros_like(flat_weights), torch.zeros_like(flat_weights)
 
     def apply(self, flat_weights, flat_grads, grad_scale=1.0):
-        self.t += 1
-        lr_t = np.float32(self.lr * np.sqrt(1.0 - self.b2 ** self.t) / (1.0 - self.b1 ** self.t))
-        self.ctx.adam_step(flat_weights, flat_grads, self.m, self.v, lr_t, self.b1, self.b2, self.eps, grad_scale)
+        self.ctx.adam_step(flat_weights, flat_grads, self.m, self.v, _next_lr_t(self), self.b1, self.b2, self.eps, grad_scale)
 
 
 # ---------------------------------------------------------------------------------------------------------------- graphs
 def srcnn_loss_and_grads(ctx, w, x, t):
     """SRCNN_model.py:48-53 + mean_squared_error.  x, t device fp32 [B,H,W,3].  -> (prediction, loss tensor [1], {layer: (dw, db)})."""
-    dw = DevWeights(ctx, w)
+    dw = ParamBucket(ctx, w)
     a1 = dw.conv(x, "conv2d", act="relu")
     a2 = dw.conv(a1, "conv2d_1", act="relu")
     y = dw.conv(a2, "conv2d_2")
@@ -115,7 +168,7 @@ def edsr_loss_and_grads(ctx, w, x, t, scale=2, num_res_blocks=16, res_scaling=0.
     names = ["conv2d"] + [f"conv2d_{i}" for i in range(1, 2 * num_res_blocks + 5)]
     it = iter(names)
     n_head = next(it)
-    dw = DevWeights(ctx, w)
+    dw = ParamBucket(ctx, w)
     h0 = dw.conv(x, n_head)
     cur, blocks = h0, []
     for _ in range(num_res_blocks):
@@ -161,35 +214,19 @@ def edsr_loss_and_grads(ctx, w, x, t, scale=2, num_res_blocks=16, res_scaling=0.
 
 # ---------------------------------------------------------------------------------------------------------------- fit
 class History:
-    def __init__(self):
-        self.history = {}
+    def __init__(self, keys):
+        self.history = {k: [] for k in keys}
         self.epoch = []
 
 
-class EpochTimeRecord:
-    """EpochTimeCallback's record (callbacks.py:21-42)."""
+class EpochTimeTracker:
+    """EpochTimeCallback (callbacks.py:21-42); the custom ESRGAN loop's manual tracker (callbacks.py:104-121)."""
     def __init__(self):
         self.epoch_times_sec = []
+        self._t0 = None
 
     def mean_time_value(self):
         return float(np.mean(self.epoch_times_sec))
-
-
-class EpochMemoryRecord:
-    """EpochMemoryCallback's record (callbacks.py:44-): device memory held by libsr355, MB."""
-    def __init__(self):
-        self.gpu_mean_current_mb = []
-        self.gpu_peak_mb = []
-
-    def as_dict(self):
-        return {"gpu_mean_current_mb": float(np.mean(self.gpu_mean_current_mb)), "gpu_peak_mb": float(np.max(self.gpu_peak_mb))}
-
-
-class EpochTimeTracker(EpochTimeRecord):
-    """Manual tracker of the custom ESRGAN loop (callbacks.py:104-121)."""
-    def __init__(self):
-        super().__init__()
-        self._t0 = None
 
     def begin_epoch(self):
         self._t0 = time.perf_counter()
@@ -200,11 +237,16 @@ class EpochTimeTracker(EpochTimeRecord):
             self._t0 = None
 
 
-class EpochMemoryTracker(EpochMemoryRecord):
-    """callbacks.py:123-176 with libsr355's allocator counters in place of tf.config.experimental.get_memory_info."""
+class EpochMemoryTracker:
+    """EpochMemoryCallback (callbacks.py:44-, 123-176): device memory held by libsr355, MB, from its allocator counters in place of
+    tf.config.experimental.get_memory_info."""
     def __init__(self, ctx):
-        super().__init__()
+        self.gpu_mean_current_mb = []
+        self.gpu_peak_mb = []
         self.ctx, self._begin = ctx, None
+
+    def as_dict(self):
+        return {"gpu_mean_current_mb": float(np.mean(self.gpu_mean_current_mb)), "gpu_peak_mb": float(np.max(self.gpu_peak_mb))}
 
     def begin_epoch(self):
         self._begin = self.ctx.mem_info()
@@ -216,22 +258,54 @@ class EpochMemoryTracker(EpochMemoryRecord):
         self._begin = None
 
 
+class PlateauCallbacks:
+    """The two callbacks on val_loss that change a fit's result, in Keras' order at the end of an epoch: ReduceLROnPlateau(factor, lr_patience,
+    min_lr; mode min, min_delta 1e-4, cooldown 0) on `optimizer.lr`, then EarlyStopping(es_patience, min_delta 0, restore_best_weights=True)."""
+
+    def __init__(self, optimizer, es_patience, lr_patience, lr_factor, min_lr, verbose):
+        self.opt, self.es_patience, self.verbose = optimizer, es_patience, verbose
+        self.lr_patience, self.lr_factor, self.min_lr = lr_patience, lr_factor, min_lr
+        self.best, self.best_w, self.es_wait, self.lr_wait, self.lr_best = np.inf, None, 0, 0, np.inf
+
+    def end_epoch(self, ep, val_loss, weights):
+        """-> None to go on, or the weights to stop with (a copy of the best epoch's)."""
+        if val_loss < self.lr_best - 1e-4:
+            self.lr_best, self.lr_wait = val_loss, 0
+        else:
+            self.lr_wait += 1
+            if self.lr_wait >= self.lr_patience and self.opt.lr > self.min_lr:
+                self.opt.lr = max(self.opt.lr * self.lr_factor, self.min_lr)
+                self.lr_wait = 0
+                if self.verbose:
+                    print(f"Epoch {ep + 1}: ReduceLROnPlateau reducing learning rate to {self.opt.lr}.")
+        if self.best_w is None:  # Keras snapshots the weights at the first epoch even when val_loss is NaN / never improves (ADVICE r2)
+            self.best_w = {n: (a.copy(), b.copy()) for n, (a, b) in weights.items()}
+        if val_loss < self.best:
+            self.best, self.es_wait = val_loss, 0
+            self.best_w = {n: (a.copy(), b.copy()) for n, (a, b) in weights.items()}
+            return None
+        self.es_wait += 1
+        if self.es_wait < self.es_patience:
+            return None
+        if self.verbose:
+            print(f"Epoch {ep + 1}: early stopping; restoring model weights from the end of the best epoch.")
+        return self.best_w
+
+
 def fit(ctx, weights, loss_and_grads, predict, optimizer, X_train, Y_train, X_val, Y_val, batch_size=16, epochs=50, es_patience=3,
         lr_patience=2, lr_factor=0.5, min_lr=1e-7, shuffle=True, seed=42, verbose=True):
     """model.fit(X, Y, batch_size, epochs, validation_data, callbacks=[EarlyStopping(val_loss, patience, restore_best_weights=True),
     ReduceLROnPlateau(val_loss, factor, patience, min_lr), EpochTimeCallback, EpochMemoryCallback]).
-    weights: {layer: (kernel, bias)} host fp32 (updated copy returned).  -> (weights, History, EpochTimeRecord, EpochMemoryRecord)."""
+    weights: {layer: (kernel, bias)} host fp32 (updated copy returned).  -> (weights, History, EpochTimeTracker, EpochMemoryTracker)."""
     X_train, Y_train = np.asarray(X_train, np.float32), np.asarray(Y_train, np.float32)
     X_val, Y_val = np.asarray(X_val, np.float32), np.asarray(Y_val, np.float32)
-    hist, tcb, mcb = History(), EpochTimeRecord(), EpochMemoryRecord()
-    for k in ("loss", "psnr", "ssim", "val_loss", "val_psnr", "val_ssim", "lr"):
-        hist.history[k] = []
+    hist, tcb, mcb = History(("loss", "psnr", "ssim", "val_loss", "val_psnr", "val_ssim", "lr")), EpochTimeTracker(), EpochMemoryTracker(ctx)
+    callbacks = PlateauCallbacks(optimizer, es_patience, lr_patience, lr_factor, min_lr, verbose)
     rng = np.random.default_rng(seed)
-    best, best_w, es_wait, lr_wait, lr_best = np.inf, None, 0, 0, np.inf
     n = len(X_train)
     for ep in range(epochs):
-        mem0 = ctx.mem_info()
-        t0 = time.perf_counter()
+        mcb.begin_epoch()
+        tcb.begin_epoch()
         order = rng.permutation(n) if shuffle else np.arange(n)
         tot = np.zeros(3, np.float64)
         for i in range(0, n, batch_size):
@@ -253,36 +327,15 @@ def fit(ctx, weights, loss_and_grads, predict, optimizer, X_train, Y_train, X_va
             hist.history[key].append(float(val))
         hist.history["lr"].append(optimizer.lr)
         hist.epoch.append(ep)
-        tcb.epoch_times_sec.append(time.perf_counter() - t0)
-        mem1 = ctx.mem_info()
-        mcb.gpu_mean_current_mb.append((mem0["current"] + mem1["current"]) / 2.0 / (1024.0 * 1024.0))
-        mcb.gpu_peak_mb.append(max(mem0["peak"], mem1["peak"]) / (1024.0 * 1024.0))
+        tcb.end_epoch()
+        mcb.end_epoch()
         if verbose:
             print(f"Epoch {ep + 1}/{epochs} - loss: {tr[0]:.4f} - psnr: {tr[1]:.4f} - ssim: {tr[2]:.4f} - val_loss: {va[0]:.4f} - "
                   f"val_psnr: {va[1]:.4f} - val_ssim: {va[2]:.4f} - lr: {optimizer.lr:.2e}")
-        # ReduceLROnPlateau(monitor="val_loss", mode min, min_delta 1e-4, cooldown 0)
-        if va[0] < lr_best - 1e-4:
-            lr_best, lr_wait = va[0], 0
-        else:
-            lr_wait += 1
-            if lr_wait >= lr_patience and optimizer.lr > min_lr:
-                optimizer.lr = max(optimizer.lr * lr_factor, min_lr)
-                lr_wait = 0
-                if verbose:
-                    print(f"Epoch {ep + 1}: ReduceLROnPlateau reducing learning rate to {optimizer.lr}.")
-        # EarlyStopping(monitor="val_loss", min_delta 0, restore_best_weights=True)
-        if best_w is None:       # Keras snapshots the weights at the first epoch even when val_loss is NaN / never improves
-            best_w = {k2: (a.copy(), b.copy()) for k2, (a, b) in weights.items()}
-        if va[0] < best:
-            best, es_wait = va[0], 0
-            best_w = {k2: (a.copy(), b.copy()) for k2, (a, b) in weights.items()}
-        else:
-            es_wait += 1
-            if es_wait >= es_patience:
-                weights = best_w
-                if verbose:
-                    print(f"Epoch {ep + 1}: early stopping; restoring model weights from the end of the best epoch.")
-                break
+        best_w = callbacks.end_epoch(ep, va[0], weights)
+        if best_w is not None:
+            weights = best_w
+            break
     return weights, hist, tcb, mcb
 
 
@@ -342,11 +395,9 @@ def fit_head(features, w, X_train_batches, y_train, X_val, y_val, learning_rate=
     head = {n: (np.asarray(w[n][0], np.float32), np.asarray(w[n][1], np.float32)) for n in ("dense", "predictions")}
     opt = Adam(head, learning_rate, epsilon=1e-7)
     rng = np.random.default_rng(seed)
-    hist = History()
-    for k in ("loss", "accuracy", "val_loss", "val_accuracy", "lr"):
-        hist.history[k] = []
+    hist = History(("loss", "accuracy", "val_loss", "val_accuracy", "lr"))
+    callbacks = PlateauCallbacks(opt, 3, 2, 0.5, 1e-7, verbose)
     g_val = features(X_val)
-    best, best_w, es_wait, lr_wait, lr_best = np.inf, None, 0, 0, np.inf
     for ep in range(epochs):
         tot, n_seen = np.zeros(2, np.float64), 0
         for xb, yb in X_train_batches(ep):
@@ -369,25 +420,8 @@ def fit_head(features, w, X_train_batches, y_train, X_val, y_val, learning_rate=
         hist.epoch.append(ep)
         if verbose:
             print(f"Epoch {ep + 1}/{epochs} - loss: {tr[0]:.4f} - accuracy: {tr[1]:.4f} - val_loss: {vl:.4f} - val_accuracy: {va:.4f} - lr: {opt.lr:.2e}")
-        if vl < lr_best - 1e-4:
-            lr_best, lr_wait = vl, 0
-        else:
-            lr_wait += 1
-            if lr_wait >= 2 and opt.lr > 1e-7:
-                opt.lr = max(opt.lr * 0.5, 1e-7)
-                lr_wait = 0
-                if verbose:
-                    print(f"Epoch {ep + 1}: ReduceLROnPlateau reducing learning rate to {opt.lr}.")
-        if best_w is None:       # as above: the first epoch's weights are the fallback of restore_best_weights
-            best_w = {n: (a.copy(), b.copy()) for n, (a, b) in head.items()}
-        if vl < best:
-            best, es_wait = vl, 0
-            best_w = {n: (a.copy(), b.copy()) for n, (a, b) in head.items()}
-        else:
-            es_wait += 1
-            if es_wait >= 3:
-                head = best_w
-                if verbose:
-                    print(f"Epoch {ep + 1}: early stopping; restoring model weights from the end of the best epoch.")
-                break
+        best_w = callbacks.end_epoch(ep, vl, head)
+        if best_w is not None:
+            head = best_w
+            break
     return head, hist

@@ -148,3 +148,56 @@ def test_classifier_head_gradients_against_autograd():
             assert np.abs(gr[n][s] - tw[n][s].grad.numpy()).max() <= 1e-12
     pd, cd = T.head_forward(g, w, training=True, dropout_rate=0.5, rng=np.random.default_rng(3))
     assert set(np.unique(np.round(cd[0][g != 0] / g[g != 0], 6))) <= {0.0, 2.0} and np.allclose(pd.sum(axis=1), 1.0)
+
+
+def test_plateau_callbacks_on_a_scripted_val_loss(capsys):
+    """sr355.train.PlateauCallbacks (the ReduceLROnPlateau + EarlyStopping(restore_best_weights) of fit and fit_head) fed val_loss by hand:
+    the rate halves after every epoch without an improvement of min_delta 1e-4 until it reaches min_lr and stays there, and after
+    es_patience epochs without an improvement the fit stops with a copy of the first epoch's weights (the best ones here)."""
+    from types import SimpleNamespace
+    from sr355 import train as T
+    opt = SimpleNamespace(lr=1.0)
+    cb = T.PlateauCallbacks(opt, es_patience=4, lr_patience=1, lr_factor=0.5, min_lr=0.3, verbose=True)
+    w = {"conv": (np.zeros((3, 3, 1, 2), np.float32), np.zeros(2, np.float32))}
+    lrs, stops = [], []
+    for ep, vl in enumerate([1.0, 1.5, 1.0, 1.2, np.nan]):
+        w["conv"][0][...], w["conv"][1][...] = ep + 1, -(ep + 1)        # the optimiser updates the weights in place
+        stops.append(cb.end_epoch(ep, vl, w))
+        lrs.append(opt.lr)
+    assert lrs == [1.0, 0.5, 0.3, 0.3, 0.3]
+    assert stops[:4] == [None] * 4 and set(stops[4]) == {"conv"}
+    assert np.array_equal(stops[4]["conv"][0], np.full((3, 3, 1, 2), 1, np.float32)) and np.array_equal(stops[4]["conv"][1], np.full(2, -1, np.float32))
+    assert capsys.readouterr().out.splitlines() == ["Epoch 2: ReduceLROnPlateau reducing learning rate to 0.5.",
+                                                    "Epoch 3: ReduceLROnPlateau reducing learning rate to 0.3.",
+                                                    "Epoch 5: early stopping; restoring model weights from the end of the best epoch."]
+    # a val_loss that is NaN from the start never improves: the first epoch's snapshot is what comes back (ADVICE r2)
+    cb = T.PlateauCallbacks(SimpleNamespace(lr=1.0), es_patience=2, lr_patience=9, lr_factor=0.5, min_lr=0.0, verbose=False)
+    w0, w1 = {"a": (np.zeros(2), np.zeros(1))}, {"a": (np.ones(2), np.ones(1))}
+    assert cb.end_epoch(0, np.nan, w0) is None
+    back = cb.end_epoch(1, np.nan, w1)
+    assert np.array_equal(back["a"][0], w0["a"][0]) and back["a"][0] is not w0["a"][0]
+
+
+def test_fit_head_on_host_features():
+    """sr355.train.fit_head with a deterministic host `features` (a fixed projection of the images) and no dropout: the first epochs'
+    history is the torch-autograd oracle's; with a learning rate that overshoots, ReduceLROnPlateau halves it, EarlyStopping stops before
+    the last epoch and the head it returns is the best epoch's (its validation loss is the minimum of the history)."""
+    from oracle import train as OT
+    from sr355 import train as T
+    rng = np.random.default_rng(4)
+    proj = rng.standard_normal((48, 512)) / 7.0
+    features = lambda a: np.asarray(a, np.float64).reshape(len(a), -1) @ proj
+    X, y = rng.uniform(0, 1, (24, 4, 4, 3)), rng.integers(0, 3, 24)
+    Xv, yv = rng.uniform(0, 1, (10, 4, 4, 3)), rng.integers(0, 3, 10)
+    w = {"dense": (rng.standard_normal((512, 256)) * 0.05, np.zeros(256)), "predictions": (rng.standard_normal((256, 3)) * 0.1, np.zeros(3))}
+    batches = lambda ep: ((X[i:i + 8], y[i:i + 8]) for i in range(0, 24, 8))
+    head, hist = T.fit_head(features, w, batches, y, Xv, yv, learning_rate=1e-3, epochs=2, dropout_rate=0.0, verbose=False)
+    _, ref = OT.vgg16_head_fit_ref([[(features(a), b) for a, b in batches(ep)] for ep in range(2)], features(Xv), yv, w, lr=1e-3)
+    for k in ("loss", "val_loss"):
+        assert np.allclose(hist.history[k], ref[k], rtol=1e-4), (k, hist.history[k], ref[k])
+    assert hist.history["accuracy"] == pytest.approx(ref["accuracy"]) and hist.history["lr"] == [1e-3, 1e-3]
+    head, hist = T.fit_head(features, w, batches, y, Xv, yv, learning_rate=0.5, epochs=30, dropout_rate=0.0, verbose=False)
+    h = hist.history
+    assert len(h["val_loss"]) < 30 and min(h["lr"]) < 0.5
+    p, _ = T.head_forward(features(Xv).astype(np.float32), head)
+    assert T.sparse_cce(p, yv)[0] == min(h["val_loss"])

@@ -292,6 +292,24 @@ def test_device_adam_is_the_host_adam_bit_for_bit(ctx):
         ctx.adam_step(wd, wd[:5].contiguous(), dev.m, dev.v, 1e-4)
 
 
+def test_pixel_step_averages_through_the_dict_allreduce(ctx):
+    """A trainer given only the dict `allreduce` hook (no flat one) averages the generator's gradient through it in pixel_step as in
+    train_step: a hook that hands back zeros makes Adam's step a no-op, so the generator's flat tensor stays the same bit for bit."""
+    from sr355 import gan_train as GT
+    gw = init_weights(M.esrgan_g_layers(2, 8, 1), seed=3000)
+    seen = []
+
+    def zero_allreduce(grads):
+        seen.append(set(grads))
+        return {n: tuple(np.zeros_like(a) for a in pair) for n, pair in grads.items()}
+    tr = GT.ESRGANTrainer(ctx, gw, None, None, 2, 1, attention=True, allreduce=zero_allreduce)
+    before = tr.g_params.flat.cpu().numpy().copy()
+    rng = np.random.default_rng(5)
+    tr.pixel_step(rng.uniform(-1, 1, (2, 12, 12, 3)).astype(np.float32), rng.uniform(-1, 1, (2, 24, 24, 3)).astype(np.float32))
+    assert seen == [set(gw)] and tr.step == 1 and tr.g_opt.t == 1
+    assert np.array_equal(tr.g_params.flat.cpu().numpy(), before)
+
+
 def test_esrgan_train_step_at_the_baseline_configuration(ctx):
     """BASELINE configs[3] at its stated size: x4, NB = 23, G = 32, both SelfAttention layers, 16 LR patches
     24x24 -> 96x96 per GPU, fp32 (ESRGAN_model.py:475-533 with the defaults of :108-112).  Shapes and the parameter bucket

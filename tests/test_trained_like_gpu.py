@@ -83,7 +83,7 @@ def test_recipe_is_deterministic(ctx):
     assert any(not np.array_equal(a[n][0], w0[n][0]) for n in a)
 
 
-def test_set_weights_reaches_a_live_trainer(ctx):
+def test_set_weights_reaches_a_live_trainers_bucket(ctx):
     """ESRGAN.set_weights after the trainer exists must move the trainer's device-resident parameter bucket too."""
     from sr355.gan_train import ESRGANTrainer
     from sr355.weights import init_weights
@@ -96,7 +96,7 @@ def test_set_weights_reaches_a_live_trainer(ctx):
     tr.gw = w1                                                               # the round-2 spelling: a plain attribute then, a setter now
     assert tr.g_opt.t == 0 and float(tr.g_opt.m.abs().max()) == 0.0
     flat = np.concatenate([a.ravel() for pair in w1.values() for a in pair])
-    assert np.array_equal(tr._gflat.cpu().numpy(), flat)
+    assert np.array_equal(tr.g_params.flat.cpu().numpy(), flat)
     l1 = tr.pixel_step(x, y)
     tr2 = ESRGANTrainer(ctx, w1, None, None, 2, 1, attention=True)
     assert l1 == tr2.pixel_step(x, y)

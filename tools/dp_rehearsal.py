@@ -34,9 +34,10 @@ def main():
         lo, hi = D.shard_range(BATCH, rank, world)
         losses.append(m._train_step(lr[lo:hi], hr[lo:hi]))
     tr = m._trainer
-    state = [tr._gflat, tr.g_opt.m, tr.g_opt.v]
-    state += [torch.from_numpy(np.concatenate([np.asarray(a, np.float32).ravel() for n in sorted(tr.dw) for a in tr.dw[n]])).to(tr._gflat.device)]
-    state += [torch.from_numpy(np.concatenate([tr.u[n].ravel() for n in sorted(tr.u)])).to(tr._gflat.device)]
+    g_flat = tr.g_params.flat
+    state = [g_flat, tr.g_opt.m, tr.g_opt.v]
+    state += [torch.from_numpy(np.concatenate([np.asarray(a, np.float32).ravel() for n in sorted(tr.dw) for a in tr.dw[n]])).to(g_flat.device)]
+    state += [torch.from_numpy(np.concatenate([tr.u[n].ravel() for n in sorted(tr.u)])).to(g_flat.device)]
     identical = True
     for t in state:
         hi_, lo_ = t.clone(), (-t).clone()
@@ -46,7 +47,7 @@ def main():
     flat = torch.cat([t.reshape(-1).float() for t in state]).cpu().numpy()
     if rank == 0:
         print(json.dumps({"world": world, "replicas_bit_identical": identical, "sha256": hashlib.sha256(flat.tobytes()).hexdigest(),
-                          "g_weights_head": [float(x) for x in flat[:4]], "g_abs_sum": float(np.abs(tr._gflat.cpu().numpy()).sum()),
+                          "g_weights_head": [float(x) for x in flat[:4]], "g_abs_sum": float(np.abs(g_flat.cpu().numpy()).sum()),
                           "d_abs_sum": float(np.abs(state[3].cpu().numpy()).sum()), "losses_rank0": [{k: float(v) for k, v in l.items()} for l in losses]}), flush=True)
         np.save(os.environ["DP_REHEARSAL_OUT"], flat) if os.environ.get("DP_REHEARSAL_OUT") else None
     if world > 1:
