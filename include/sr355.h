@@ -317,6 +317,28 @@ int  sr_classic_scores(sr_ctx* ctx, const void* hr, int hr_dtype, const void* sr
                        const double* data_range_f64, double hf_radius_frac, double* scores_f64, float* gray_f32, float* sobel_f32,
                        int* hist_luma_i32, int* hist_color_i32, void* stream);
 
+/* ---- FineTunedVGG16.fit's per-batch work besides the frozen base (reference VGG16_model.py:111-157), csrc/head_train.hip ----
+ * sr_affine_warp: the ImageDataGenerator transform of VGG16_model.py:129-134 as FineTunedVGG16._augment computes it (scipy
+ *   affine_transform order=1, mode="nearest", per channel, then the flip), with the batch's gather fused in.  x DEVICE fp32 [N,H,W,C];
+ *   idx DEVICE int32 [n], rows of x; params DEVICE fp32 [n,16] per image: the fp64 values a00 a01 a10 a11 o0 o1 split into fp32 hi [0..5]
+ *   and lo = x - hi [6..11], flip flag [12] (non-zero: mirror the columns after the warp), [13..15] unused.  Output pixel (oy, ox) samples
+ *   (a00 oy + a01 ox + o0, a10 oy + a11 ox + o1) bilinearly, every tap index clamped to the image.  y DEVICE fp32 [n,H,W,C].  An index
+ *   outside [0, N) writes NaN for that image and reads nothing.  An integer sample point (identity, flip, integer shift) copies bits.
+ * sr_dense_head_step: one step of the head GAP -> Dropout -> Dense(in_dim=512 -> hidden=256, ReLU) -> Dropout -> Dense(num_classes) softmax
+ *   with mean sparse categorical CE + l2_reg sum(dense kernel^2) (VGG16_model.py:84-97; the host reference is sr355/train.py head_forward /
+ *   head_backward / sparse_cce).  feats DEVICE fp32 [n,512], labels DEVICE int32 [n], params DEVICE fp32: the flat head bucket dense kernel
+ *   [512,256], dense bias [256], predictions kernel [256,C], predictions bias [C].  keep0 [n,512] / keep1 [n,256] DEVICE uint8 dropout
+ *   keep masks (both or neither, training only); kept values are multiplied by keep_scale = 1 / (1 - rate).  grads DEVICE fp32, the bucket's
+ *   layout: training step when non-NULL, inference (no dropout) when NULL.  stats DEVICE fp64 [3]: sum over rows of -log(clip(p[y], 1e-7,
+ *   1 - 1e-7)), number of rows whose argmax is y, sum of the dense kernel's squares.  work: sr_dense_head_workspace_bytes(n, C) bytes of
+ *   DEVICE memory.  Launches only; every sum runs in a fixed order (no float atomics): the same inputs give the same bits. */
+int  sr_affine_warp(sr_ctx* ctx, const float* x, int N, int H, int W, int C, const int32_t* idx, int n, const float* params, float* y,
+                    void* stream);
+int64_t sr_dense_head_workspace_bytes(int n, int num_classes);
+int  sr_dense_head_step(sr_ctx* ctx, const float* feats, int n, int in_dim, int hidden, int num_classes, const int32_t* labels,
+                        const uint8_t* keep0, const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads,
+                        double* stats, void* work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

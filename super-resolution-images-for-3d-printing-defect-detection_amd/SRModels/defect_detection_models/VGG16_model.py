@@ -62,63 +62,96 @@ class FineTunedVGG16(DeviceModelMixin):
         return int(sum(np.asarray(k).size + np.asarray(b).size for k, b in (self.weights[n] for n in names)))
 
     # ------------------------------------------------------------------ training of the head on the frozen base (VGG16_model.py:111-166)
-    def _gap_features(self, images, batch_size=256):
-        """[n,H,W,3] in [0,1] -> [n,512]: the frozen conv base on the device (tap after block5_conv3), max-pool and GAP kernels."""
+    def _gap_device(self, x):
+        """[n,H,W,3] device tensor (fp32, or the compute dtype) -> fp32 device [n,512]: the frozen conv base (tap after block5_conv3),
+        max-pool and GAP kernels."""
         from sr355 import _lib as L
+        _, taps = self.model.forward_with_taps(x, ["block5_conv3"])
+        return self.ctx.spatial_op(L.SP_GAP, self.ctx.spatial_op(L.SP_MAXPOOL2, taps["block5_conv3"]))
+
+    def _gap_features(self, images, batch_size=256):
+        """[n,H,W,3] in [0,1] -> [n,512] host features (the host reference path of fit): _gap_device per chunk, downloaded."""
         out = []
         for i in range(0, len(images), batch_size):
             x = self.ctx.to_device(np.asarray(images[i:i + batch_size], np.float32),
                                    torch.bfloat16 if self.compute_dtype == "bf16" else torch.float32)
-            _, taps = self.model.forward_with_taps(x, ["block5_conv3"])
-            f = self.ctx.spatial_op(L.SP_MAXPOOL2, taps["block5_conv3"])
-            out.append(self.ctx.spatial_op(L.SP_GAP, f).cpu().numpy().reshape(len(x), -1))
+            out.append(self._gap_device(x).cpu().numpy().reshape(len(x), -1))
         return np.concatenate(out) if out else np.zeros((0, 512), np.float32)
+
+    @staticmethod
+    def _augment_params(rng, n, h, w, rotation_range=20, width_shift_range=0.2, height_shift_range=0.2, horizontal_flip=True):
+        """The random draws of _augment for n images of h x w, in its order (per image: angle, ty, tx, then the flip's random()) ->
+        (rot [n,2,2], offset [n,2], flip [n]): output pixel o samples input rot @ o + offset, then the columns are mirrored where flip."""
+        rot, offset, flip = np.empty((n, 2, 2)), np.empty((n, 2)), np.zeros(n, bool)
+        centre = np.array([(h - 1) / 2.0, (w - 1) / 2.0])
+        for i in range(n):
+            th = np.deg2rad(rng.uniform(-rotation_range, rotation_range))
+            ty, tx = rng.uniform(-height_shift_range, height_shift_range) * h, rng.uniform(-width_shift_range, width_shift_range) * w
+            c, s_ = np.cos(th), np.sin(th)
+            rot[i] = np.array([[c, -s_], [s_, c]])
+            offset[i] = centre - rot[i] @ centre + np.array([ty, tx])
+            flip[i] = horizontal_flip and rng.random() < 0.5
+        return rot, offset, flip
 
     @staticmethod
     def _augment(x, rng, rotation_range=20, width_shift_range=0.2, height_shift_range=0.2, horizontal_flip=True):
         """One draw of keras ImageDataGenerator(rotation_range=20, width_shift_range=0.2, height_shift_range=0.2,
         horizontal_flip=True) per image (VGG16_model.py:129-134): random rotation about the centre, random shifts as fractions of
-        the size, fill_mode 'nearest', bilinear interpolation, random flip.  A CPU step in the reference as well (NumPy / SciPy)."""
+        the size, fill_mode 'nearest', bilinear interpolation, random flip.  The host reference (NumPy / SciPy) of the device's
+        sr_affine_warp, which fit runs on the same parameters (_augment_params)."""
         from scipy import ndimage
         out = np.empty_like(x)
         h, w = x.shape[1:3]
+        rot, offset, flip = FineTunedVGG16._augment_params(rng, len(x), h, w, rotation_range, width_shift_range, height_shift_range, horizontal_flip)
         for i, img in enumerate(x):
-            th = np.deg2rad(rng.uniform(-rotation_range, rotation_range))
-            ty, tx = rng.uniform(-height_shift_range, height_shift_range) * h, rng.uniform(-width_shift_range, width_shift_range) * w
-            c, s_ = np.cos(th), np.sin(th)
-            rot = np.array([[c, -s_], [s_, c]])
-            centre = np.array([(h - 1) / 2.0, (w - 1) / 2.0])
-            offset = centre - rot @ centre + np.array([ty, tx])          # output pixel o samples input rot @ o + offset
             for ch in range(img.shape[2]):
-                out[i, :, :, ch] = ndimage.affine_transform(img[:, :, ch], rot, offset=offset, order=1, mode="nearest")
-            if horizontal_flip and rng.random() < 0.5:
+                out[i, :, :, ch] = ndimage.affine_transform(img[:, :, ch], rot[i], offset=offset[i], order=1, mode="nearest")
+            if flip[i]:
                 out[i] = out[i, :, ::-1]
         return out
 
     def fit(self, X_train, y_train, X_val, y_val, batch_size=32, epochs=50, use_augmentation=True, seed=42):
-        """FineTunedVGG16.fit (VGG16_model.py:111-157): the conv base runs on the device per batch, the two Dense layers train on the
-        host (Adam, sparse CCE, Dropout, EarlyStopping / ReduceLROnPlateau).  The base is frozen with and without base_trainable,
-        as in the reference (setup_model).  With augmentation the batches are 32 images, as the reference's
-        datagen.flow(..., batch_size=32) hard-codes."""
-        from sr355.train import fit_head
+        """FineTunedVGG16.fit (VGG16_model.py:111-157), every per-batch step on the device: the batch's gather and augmentation
+        (sr_affine_warp), the frozen conv base, and the two Dense layers' step (sr_dense_head_step + DeviceAdam, sparse CCE, Dropout,
+        EarlyStopping / ReduceLROnPlateau: train.fit_head_device).  X_train and X_val are uploaded once per fit as fp32: the device holds
+        4 N_train H W 3 bytes of training images for the whole fit, and 4 N_val H W 3 bytes of validation images only while their GAP
+        features (2 KiB per image, kept) are computed, once.  The random draws stay
+        the host's, draw for draw those of the host path (_augment / fit_head): per epoch the permutation and the augmentation parameters on
+        this generator, uploaded with the dropout masks in one copy.  The base is frozen with and without base_trainable, as in the reference
+        (setup_model).  With augmentation the batches are 32 images, as the reference's datagen.flow(..., batch_size=32) hard-codes."""
+        from sr355.train import fit_head_device
         if self.model is None:
             raise ValueError("Model is not built yet.")
         X_train, y_train = np.asarray(X_train, np.float32), np.asarray(y_train, np.int64).reshape(-1)
+        X_val, y_val = np.asarray(X_val, np.float32), np.asarray(y_val, np.int64).reshape(-1)
+        nc = int(np.asarray(self.weights["predictions"][0]).shape[-1])
+        if len(y_train) != len(X_train) or (len(y_train) and (y_train.min() < 0 or y_train.max() >= nc)):
+            raise ValueError(f"y_train: one label in [0, {nc}) per training image")
         rng = np.random.default_rng(seed)
         bs = 32 if use_augmentation else int(batch_size)
+        n, (h, w) = len(X_train), X_train.shape[1:3]
+        Xd = self.ctx.to_device(X_train)
+        Xv = self.ctx.to_device(X_val)
+        g_val = [self._gap_device(Xv[i:i + 256]) for i in range(0, len(X_val), 256)]
+        g_val = g_val[0] if len(g_val) == 1 else (torch.cat(g_val) if g_val else self.ctx.empty((0, 512)))
+        del Xv
 
-        def batches(epoch):
-            order = rng.permutation(len(X_train))
-            for i in range(0, len(order), bs):
-                idx = order[i:i + bs]
-                xb = X_train[idx]
-                yield (self._augment(xb, rng) if use_augmentation else xb), y_train[idx]
+        def draw_epoch(epoch):
+            order = rng.permutation(n)
+            if use_augmentation:
+                rot, off, flip = self._augment_params(rng, n, h, w)
+            else:
+                rot, off, flip = np.broadcast_to(np.eye(2), (n, 2, 2)), np.zeros((n, 2)), np.zeros(n, bool)
+            return {"idx": order.astype(np.int32), "labels": y_train[order].astype(np.int32), "warp": self.ctx.warp_params(rot, off, flip)}
 
-        head, history = fit_head(self._gap_features, self.weights, batches, y_train, np.asarray(X_val, np.float32), np.asarray(y_val, np.int64).reshape(-1),
-                                 learning_rate=self.learning_rate, batch_size=bs, epochs=epochs, dropout_rate=self.dropout_rate, l2_reg=self.l2_reg, seed=seed)
-        w = dict(self.weights)
-        w.update(head)
-        self.set_weights(w)
+        def features(dev, i, j):
+            return self._gap_device(self.ctx.affine_warp(Xd, dev["idx"][i:j], dev["warp"][i:j]))
+
+        head, history = fit_head_device(self.ctx, features, self.weights, draw_epoch, n, g_val, y_val, learning_rate=self.learning_rate, batch_size=bs,
+                                        epochs=epochs, dropout_rate=self.dropout_rate, l2_reg=self.l2_reg, seed=seed)
+        w_ = dict(self.weights)
+        w_.update(head)
+        self.set_weights(w_)
         self.trained = True
         return history
 

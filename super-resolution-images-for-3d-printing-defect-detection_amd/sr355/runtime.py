@@ -495,6 +495,87 @@ class Context:
         self.check(self.lib.sr_matmul(self.h, a.data_ptr(), b.data_ptr(), c.data_ptr(), a.shape[0], M, N, K, int(trans_a), int(trans_b), float(alpha), self.stream()))
         return c
 
+    # ------------------------------------------------------------------ classifier training (FineTunedVGG16.fit, VGG16_model.py:111-157)
+    @staticmethod
+    def warp_params(rot, offset, flip):
+        """Per-image affine parameters for affine_warp: rot [n,2,2], offset [n,2] (fp64: output pixel o samples rot @ o + offset) and
+        flip [n] (mirror the columns after the warp) -> fp32 [n,16] as sr_affine_warp reads them (fp64 values split into hi + lo)."""
+        rot, offset = np.asarray(rot, np.float64).reshape(-1, 4), np.asarray(offset, np.float64).reshape(-1, 2)
+        flip = np.asarray(flip, bool).reshape(-1)
+        if not len(rot) == len(offset) == len(flip):
+            raise ValueError("warp_params: rot, offset and flip must describe the same number of images")
+        v = np.concatenate([rot, offset], axis=1)
+        hi = v.astype(np.float32)
+        out = np.zeros((len(v), 16), np.float32)
+        out[:, :6], out[:, 6:12], out[:, 12] = hi, (v - hi).astype(np.float32), flip
+        return out
+
+    def affine_warp(self, x, idx, params, out=None):
+        """Augmented batch of a device-resident image set (sr_affine_warp): x fp32 [N,H,W,C]; idx int32 [n] rows of x and params fp32 [n,16]
+        (warp_params), each a device tensor or a host array (host indices are range-checked before the upload) -> fp32 [n,H,W,C]."""
+        _check_tensor(self, x, "affine_warp images")
+        if x.dim() != 4:
+            raise ValueError("affine_warp: images must be [N,H,W,C]")
+        N, H, W, Cx = x.shape
+        if not isinstance(idx, torch.Tensor):
+            idx = np.asarray(idx)
+            if idx.ndim != 1 or not np.issubdtype(idx.dtype, np.integer) or (len(idx) and (idx.min() < 0 or idx.max() >= N)):
+                raise ValueError(f"affine_warp: indices must be integers in [0, {N})")
+            idx = self.to_device(idx.astype(np.int32))
+        if not isinstance(params, torch.Tensor):
+            params = self.to_device(np.asarray(params, np.float32))
+        _check_tensor(self, idx, "affine_warp indices", (torch.int32,))
+        _check_tensor(self, params, "affine_warp params")
+        n = idx.numel()
+        if idx.dim() != 1 or tuple(params.shape) != (n, 16):
+            raise ValueError(f"affine_warp: indices [n] and params [n,16] expected, got {tuple(idx.shape)} and {tuple(params.shape)}")
+        y = self.empty((n, H, W, Cx)) if out is None else out
+        _check_tensor(self, y, "affine_warp out")
+        if tuple(y.shape) != (n, H, W, Cx):
+            raise ValueError("affine_warp: out has the wrong shape")
+        self.check(self.lib.sr_affine_warp(self.h, x.data_ptr(), N, H, W, Cx, idx.data_ptr(), n, params.data_ptr(), y.data_ptr(), self.stream()))
+        return y
+
+    def dense_head_workspace(self, n, num_classes):
+        """Device workspace of dense_head_step for up to n rows (allocate once, before the loop)."""
+        nb = self.lib.sr_dense_head_workspace_bytes(int(n), int(num_classes))
+        if nb < 0:
+            raise ValueError("dense_head_workspace: need n >= 1 and num_classes >= 2")
+        return self.empty((nb,), torch.uint8)
+
+    def dense_head_step(self, feats, labels, params, num_classes, stats, work, grads=None, keep0=None, keep1=None, keep_scale=1.0, l2_reg=0.0):
+        """One step of the classifier head (sr_dense_head_step): feats fp32 [n,512], labels int32 [n], params the flat fp32 head bucket; with
+        grads (fp32, same size) a training step that writes the gradient of mean sparse CCE + l2_reg sum(k1^2), with uint8 dropout keep masks
+        keep0 [n,512] / keep1 [n,256] (optional), else an inference pass.  stats fp64 [3] receives (loss sum, correct rows, sum k1^2)."""
+        C_ = int(num_classes)
+        _check_tensor(self, feats, "dense_head feats")
+        _check_tensor(self, labels, "dense_head labels", (torch.int32,))
+        _check_tensor(self, params, "dense_head params")
+        _check_tensor(self, stats, "dense_head stats", (torch.float64,))
+        _check_tensor(self, work, "dense_head workspace", (torch.uint8,))
+        if feats.dim() != 2 or feats.shape[1] != 512 or feats.shape[0] < 1:
+            raise ValueError(f"dense_head_step: features must be [n,512], got {tuple(feats.shape)}")
+        n = feats.shape[0]
+        nparam = 512 * 256 + 256 + 256 * C_ + C_
+        if C_ < 2 or params.numel() != nparam:
+            raise ValueError(f"dense_head_step: params must be the flat head bucket of {nparam} values (num_classes >= 2)")
+        if labels.shape != (n,) or stats.numel() != 3:
+            raise ValueError("dense_head_step: labels [n] and stats [3] expected")
+        if grads is not None:
+            _check_tensor(self, grads, "dense_head grads")
+            if grads.numel() != nparam:
+                raise ValueError("dense_head_step: grads must match params")
+        if (keep0 is None) != (keep1 is None) or (keep0 is not None and grads is None):
+            raise ValueError("dense_head_step: dropout masks come in pairs, in training steps only")
+        if keep0 is not None:
+            _check_tensor(self, keep0, "dense_head keep0", (torch.uint8,))
+            _check_tensor(self, keep1, "dense_head keep1", (torch.uint8,))
+            if keep0.shape != (n, 512) or keep1.shape != (n, 256):
+                raise ValueError("dense_head_step: keep masks must be [n,512] and [n,256]")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self.check(self.lib.sr_dense_head_step(self.h, feats.data_ptr(), n, 512, 256, C_, labels.data_ptr(), ptr(keep0), ptr(keep1), float(keep_scale),
+                                               params.data_ptr(), float(l2_reg), ptr(grads), stats.data_ptr(), work.data_ptr(), work.numel(), self.stream()))
+
     def softmax_rows_(self, s):
         """softmax over the last axis, in place."""
         _check_tensor(self, s, "softmax input")

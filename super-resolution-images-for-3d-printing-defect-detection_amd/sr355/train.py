@@ -425,3 +425,88 @@ def fit_head(features, w, X_train_batches, y_train, X_val, y_val, learning_rate=
             head = best_w
             break
     return head, hist
+
+
+_NP2TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}
+
+
+def upload_packed(ctx, arrays):
+    """{name: host array (fp32 / int32 / uint8)} -> {name: device tensor} through ONE host-to-device copy: the arrays are packed into one
+    byte buffer (256-byte aligned sections) and the device tensors are typed views of its upload."""
+    arrays = {k: np.ascontiguousarray(a) for k, a in arrays.items()}
+    offs, o = {}, 0
+    for k, a in arrays.items():
+        offs[k] = o
+        o += (a.nbytes + 255) // 256 * 256
+    buf = np.zeros(max(o, 256), np.uint8)
+    for k, a in arrays.items():
+        buf[offs[k]:offs[k] + a.nbytes] = a.reshape(-1).view(np.uint8)
+    dev = ctx.to_device(buf)
+    return {k: dev[offs[k]:offs[k] + a.nbytes].view(_NP2TORCH[a.dtype]).reshape(a.shape) for k, a in arrays.items()}
+
+
+def fit_head_device(ctx, features, w, draw_epoch, n_train, g_val, y_val, learning_rate=1e-3, batch_size=32, epochs=50, dropout_rate=0.2,
+                    l2_reg=0.0, seed=42, verbose=True):
+    """fit_head on the device: the same fit (VGG16_model.py:111-157), history, print lines and callbacks, with the head in one flat device
+    bucket (ParamBucket) trained by sr_dense_head_step + DeviceAdam.  draw_epoch(ep) -> {name: host array} of the epoch, one row per training
+    sample in the epoch's order, with at least "labels" (int32); the dropout keep masks are drawn here on fit_head's own generator, in its order
+    (m0 [n_b,512] then m1 [n_b,256] per batch), and everything goes up in one copy per epoch.  features(dev, i, j) -> fp32 device [j-i,512] GAP
+    features of the epoch's samples i..j-1 (dev: the uploaded arrays).  g_val fp32 device [n_val,512].  The host reads the per-batch statistics
+    and the head (131 842 parameters at two classes, for EarlyStopping) once per epoch.  -> (head weights, History)."""
+    head = {n: (np.asarray(w[n][0], np.float32), np.asarray(w[n][1], np.float32)) for n in ("dense", "predictions")}
+    num_classes = head["predictions"][0].shape[1]
+    y_val = np.asarray(y_val, np.int64).reshape(-1)
+    if len(y_val) and (y_val.min() < 0 or y_val.max() >= num_classes):
+        raise ValueError(f"labels must lie in [0, {num_classes})")
+    bucket = ParamBucket(ctx, head)
+    opt = DeviceAdam(ctx, bucket.flat, learning_rate, epsilon=1e-7)
+    grads = torch.empty_like(bucket.flat)
+    rng = np.random.default_rng(seed)
+    hist = History(("loss", "accuracy", "val_loss", "val_accuracy", "lr"))
+    callbacks = PlateauCallbacks(opt, 3, 2, 0.5, 1e-7, verbose)
+    keep = 1.0 - dropout_rate
+    spans = [(i, min(i + batch_size, n_train)) for i in range(0, n_train, batch_size)]
+    n_val = int(g_val.shape[0])
+    yv = ctx.to_device(y_val.astype(np.int32))
+    stats = ctx.empty((len(spans) + 1, 3), torch.float64)
+    work = ctx.dense_head_workspace(max(batch_size, n_val, 1), num_classes)
+    for ep in range(epochs):
+        plan = dict(draw_epoch(ep))
+        if dropout_rate > 0:
+            m0, m1 = [], []
+            for i, j in spans:
+                m0.append(rng.random((j - i, 512)) < keep)
+                m1.append(rng.random((j - i, 256)) < keep)
+            plan["keep0"], plan["keep1"] = np.concatenate(m0).astype(np.uint8), np.concatenate(m1).astype(np.uint8)
+        dev = upload_packed(ctx, plan)
+        for s, (i, j) in enumerate(spans):
+            k0, k1 = (dev["keep0"][i:j], dev["keep1"][i:j]) if dropout_rate > 0 else (None, None)
+            ctx.dense_head_step(features(dev, i, j), dev["labels"][i:j], bucket.flat, num_classes, stats[s], work, grads, k0, k1, 1.0 / keep, l2_reg)
+            opt.apply(bucket.flat, grads)
+        if n_val:
+            ctx.dense_head_step(g_val, yv, bucket.flat, num_classes, stats[len(spans)], work)
+        bucket.stale = True
+        weights = bucket.host()
+        st = stats.cpu().numpy()
+        tot, n_seen = np.zeros(2, np.float64), 0
+        for s, (i, j) in enumerate(spans):
+            nb = j - i
+            loss, acc = st[s, 0] / nb, st[s, 1] / nb
+            if l2_reg > 0:
+                loss += l2_reg * st[s, 2]
+            tot += [loss * nb, acc * nb]
+            n_seen += nb
+        vl, va = (st[-1, 0] / n_val, st[-1, 1] / n_val) if n_val else (np.nan, np.nan)
+        if l2_reg > 0:
+            vl += l2_reg * st[-1, 2]
+        tr = tot / max(n_seen, 1)
+        for key, val in zip(("loss", "accuracy", "val_loss", "val_accuracy", "lr"), (tr[0], tr[1], vl, va, opt.lr)):
+            hist.history[key].append(float(val))
+        hist.epoch.append(ep)
+        if verbose:
+            print(f"Epoch {ep + 1}/{epochs} - loss: {tr[0]:.4f} - accuracy: {tr[1]:.4f} - val_loss: {vl:.4f} - val_accuracy: {va:.4f} - lr: {opt.lr:.2e}")
+        best_w = callbacks.end_epoch(ep, vl, weights)
+        if best_w is not None:
+            bucket.load(best_w)
+            break
+    return {n: (k.copy(), b.copy()) for n, (k, b) in bucket.host().items()}, hist
