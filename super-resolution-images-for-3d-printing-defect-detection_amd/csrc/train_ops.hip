@@ -417,11 +417,13 @@ __global__ void __launch_bounds__(256) spectral_wc_bwd_kernel(const float* a, co
             float* g = im ? gb : ga;
             const float x0 = r[3 * k], x1 = r[3 * k + 1], x2 = r[3 * k + 2];
             g[6 * k + 0] = x0 + x1 + x2;        g[6 * k + 1] = 0.f;
-            g[6 * k + 2] = x0 + c3 * (x1 + x2); g[6 * k + 3] = -s3 * (x1 - x2);
-            g[6 * k + 4] = x0 + c3 * (x1 + x2); g[6 * k + 5] = s3 * (x1 - x2);
+            g[6 * k + 2] = fmaf(c3, x1 + x2, x0); g[6 * k + 3] = -s3 * (x1 - x2);
+            g[6 * k + 4] = fmaf(c3, x1 + x2, x0); g[6 * k + 5] = s3 * (x1 - x2);
         }
     }
     __syncthreads();
+    // a and b take the same explicitly rounded operations (fmaf, nothing left to the compiler's contraction, which had fused the two sides
+    // differently): at a == b the magnitudes are then equal bit for bit, the sign 0 and the gradient exactly 0, as the reference's abs has it
     for (int o = threadIdx.x; o < 3 * W; o += blockDim.x) {
         const int u = o / 3, v = o - 3 * u;
         float are = 0.f, aim = 0.f, bre = 0.f, bim = 0.f;
@@ -429,11 +431,11 @@ __global__ void __launch_bounds__(256) spectral_wc_bwd_kernel(const float* a, co
         for (int w = 0; w < W; ++w) {
             const float tc = tw[2 * k], ts = -tw[2 * k + 1];                 // exp(-i theta)
             const float gar = ga[6 * w + 2 * v], gai = ga[6 * w + 2 * v + 1], gbr = gb[6 * w + 2 * v], gbi = gb[6 * w + 2 * v + 1];
-            are += gar * tc - gai * ts; aim += gar * ts + gai * tc;
-            bre += gbr * tc - gbi * ts; bim += gbr * ts + gbi * tc;
+            are += fmaf(gar, tc, -(gai * ts)); aim += fmaf(gar, ts, gai * tc);
+            bre += fmaf(gbr, tc, -(gbi * ts)); bim += fmaf(gbr, ts, gbi * tc);
             k += u; if (k >= W) k -= W;
         }
-        const float ma = sqrtf(are * are + aim * aim), mb = sqrtf(bre * bre + bim * bim);
+        const float ma = sqrtf(fmaf(are, are, aim * aim)), mb = sqrtf(fmaf(bre, bre, bim * bim));
         const float sg = ma > mb ? 1.f : (ma < mb ? -1.f : 0.f);
         const float inv = ma > 0.f ? sg / ma : 0.f;
         G[6 * u + 2 * v] = are * inv; G[6 * u + 2 * v + 1] = aim * inv;
