@@ -117,6 +117,10 @@ enum { SR_FUSE_DENSE_TAIL = 1, SR_FUSE_DENSE_MID = 2, SR_FUSE_RGB_TAIL = 4, SR_F
 /* Test hook: device allocations through this ctx fail (SR_ERR_OOM) once the bytes it holds would exceed `bytes`
  * (0 = no cap).  Lets the tests walk the out-of-memory path of sr_forward without filling a 288 GB card. */
 int  sr_debug_set_alloc_cap(sr_ctx* ctx, int64_t bytes);
+/* Test hook: the kernel variant every conv launch on this ctx runs, one name per line (e.g. "wide<f32,k3,kg2,nt2>/sk", "pw<bf16,nb3,nch2>",
+ * "rows<bf16,nb4>/skip_lds").  Copies the names logged since the previous call into `text` (NUL-terminated; SR_ERR_CAPACITY, nothing cleared,
+ * when `cap` bytes do not hold them; text NULL: discarded), clears the log, and logs the launches that follow iff `enable`.  Off by default. */
+int  sr_debug_conv_routes(sr_ctx* ctx, int enable, char* text, int64_t cap);
 int  sr_profile_begin(sr_ctx* ctx);
 int  sr_profile_end(sr_ctx* ctx, char* json, int64_t cap);
 

@@ -742,6 +742,15 @@ int sr_debug_set_alloc_cap(sr_ctx* ctx, int64_t bytes) {
     return SR_OK;
 }
 
+int sr_debug_conv_routes(sr_ctx* ctx, int enable, char* text, int64_t cap) {
+    if (!ctx) return SR_ERR_INVALID;
+    if (text && cap <= (int64_t)ctx->route_text.size()) return ctx->fail(SR_ERR_CAPACITY, "sr_debug_conv_routes: the text buffer is too small");
+    if (text) memcpy(text, ctx->route_text.c_str(), ctx->route_text.size() + 1);
+    ctx->route_text.clear();
+    ctx->route_log = enable != 0;
+    return SR_OK;
+}
+
 int sr_profile_begin(sr_ctx* ctx) {
     if (!ctx) return SR_ERR_INVALID;
     for (auto& r : ctx->prof_recs) { ctx->ev_pool.push_back(r.e0); ctx->ev_pool.push_back(r.e1); }
@@ -1156,8 +1165,11 @@ int sr_conv2d(sr_ctx* ctx, const void* x, int dtype, int B, int H, int W, int Ci
         ConvEpilogue ep;
         ep.act = act; ep.alpha = alpha; ep.clip01 = clip01; ep.d2s_r = d2s_r < 1 ? 1 : d2s_r;
         ep.allow_splitk = 1;                                      // a single op, like sr_conv2d_dev (same kernel choice: the two agree bit for bit); model forwards do not set it
-        if (skip1) { ep.skip1 = {skip1, Cout, 0}; ep.beta1 = beta1; }
-        if (skip2) { ep.skip2 = {skip2, Cout, 0}; ep.beta2 = beta2; }
+        // a skip that IS the input (a dense-block tail y = alpha * conv(x) + beta * x) is read from the padded copy the conv reads, so that the kernel
+        // sees the alias the way a model forward presents it (conv_rows then takes that skip from its LDS tile)
+        auto skip_view = [&](const void* s) { return (s == x && Cout == Cin) ? TensorView{xp, Cp, 0} : TensorView{s, Cout, 0}; };
+        if (skip1) { ep.skip1 = skip_view(skip1); ep.beta1 = beta1; }
+        if (skip2) { ep.skip2 = skip_view(skip2); ep.beta2 = beta2; }
         const int r = ep.d2s_r;
         rc = conv_launch(ctx, cw, TensorView{xp, Cp, 0}, B, H, W, y, Cout / (r * r), 0, ep, st);
     }

@@ -78,6 +78,8 @@ struct sr_ctx {
     int chain_mask = 511;          // SR_FUSE_* bits (include/sr355.h): which fused / persistent paths sr_forward may take (sr_debug_set_fused; default all)
     int chain_max_wgs = 0;        // test hook: cap the persistent grid so that small batches still give several images per workgroup
     int64_t alloc_cap = 0;        // test hook (sr_debug_set_alloc_cap): dalloc fails once cur_bytes would exceed it; 0 = none
+    bool route_log = false;       // test hook (sr_debug_conv_routes): conv_launch appends the name of the kernel it runs to route_text
+    std::string route_text;
 
     void* dalloc(size_t bytes);   // nullptr on failure (err set)
     void dfree(void* p);

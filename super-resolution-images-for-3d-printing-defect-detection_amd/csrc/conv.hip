@@ -451,20 +451,35 @@ int launch_wide_mt(sr_ctx* ctx, const ConvParams& p0, int nct, hipStream_t st) {
     return SR_OK;
 }
 
+// Which kernel a conv runs (conv_route, below).  conv_launch and the launch helpers switch on this instead of re-deriving the choice,
+// and sr_debug_conv_routes reports it by name, so that the tests can assert which variant a shape reached.
+enum ConvFamily { CF_FEW, CF_THIN, CF_WIDE, CF_PW, CF_ROWS, CF_STREAM };
+enum ConvSub {
+    CS_NONE,
+    CS_SK, CS_MT1, CS_MT3,                  // wide: split-K 2 x 16 tiles, 8 x 16 tiles, 24 x 16 tiles
+    CS_LDS, CS_DIRECT,                      // few: the whole channel depth staged in LDS, or 4 channels at a time
+    CS_PW2,                                 // thin: the fp32 9x9 RGB head with its 1x1 successor in the epilogue
+    CS_SKIP_LDS, CS_RGBTAIL, CS_POOL, CS_PROJ   // rows: a skip read from the staged input, or one of the fused epilogues
+};
+struct ConvRoute {
+    int fam = CF_WIDE, dtype = SR_DTYPE_F32, KS = 3;
+    int KGPT = 0;      // wide: k-groups per tap per stage; pw: 32-channel input chunks (NCH)
+    int NT = 1;        // 32-cout blocks per workgroup; rows, pw, stream: 16-cout blocks (NB16)
+    int NV = 4;        // thin fp32: channels of the 16-byte slice that are multiplied
+    int sub = CS_NONE;
+};
+
 template <typename T, int KS, int KGPT, int NT>
-int launch_wide(sr_ctx* ctx, const ConvParams& p0, int nct, hipStream_t st) {
+int launch_wide(sr_ctx* ctx, const ConvParams& p0, int nct, int sub, hipStream_t st) {
     // Small fp32 problems (the training step's 16 x 24 x 24 batches: 9216 pixels) give the 24 x 16 tiling 32 workgroups per cout tile on
     // 256 CUs -- a launch then takes as long as one workgroup's whole K loop (round 2: 146 us for 0.85 GFLOP).  8 x 16 tiles give three
-    // times the workgroups and a third of the serial work each.  (bf16 inference never gets here with so few pixels.)
+    // times the workgroups and a third of the serial work each; split K (conv_wide_sk_kernel) four times that again.  conv_route picks.
     if constexpr (std::is_same<T, float>::value) {
-        const int64_t wgs3 = (int64_t)((p0.W + 15) / 16) * ((p0.H + 8 * MT_DEFAULT - 1) / (8 * MT_DEFAULT)) * p0.B * nct;
-        if constexpr (KS == 3 && KGPT == 2) {
-            // still fewer than one 8 x 16 tile per CU: split K inside the workgroup (conv_wide_sk_kernel) -- 4 x the workgroups, a quarter of the chain each
-            const int64_t wgs1 = (int64_t)((p0.W + 15) / 16) * ((p0.H + 7) / 8) * p0.B * nct;
-            if (p0.splitk_ok && wgs1 < ctx->cu_count()) return launch_wide_sk<KS, KGPT, NT>(ctx, p0, nct, st);
-        }
-        if (wgs3 < 2 * ctx->cu_count()) return launch_wide_mt<T, KS, KGPT, NT, 1>(ctx, p0, nct, st);
+        if constexpr (KS == 3 && KGPT == 2)
+            if (sub == CS_SK) return launch_wide_sk<KS, KGPT, NT>(ctx, p0, nct, st);
+        if (sub == CS_MT1) return launch_wide_mt<T, KS, KGPT, NT, 1>(ctx, p0, nct, st);
     }
+    if (sub != CS_MT3) return ctx->fail(SR_ERR_INVALID, "conv: this wide tiling is not built for the dtype / kernel size");
     return launch_wide_mt<T, KS, KGPT, NT, MT_DEFAULT>(ctx, p0, nct, st);
 }
 
@@ -486,52 +501,43 @@ int launch_thin(sr_ctx* ctx, const ConvParams& p0, int nct, hipStream_t st) {
 }
 
 template <typename T, int KS, int KGPT>
-int dispatch_wide_nt(sr_ctx* ctx, const ConvParams& p, int NT, int nct, hipStream_t st) {
-    switch (NT) {
-        case 1: return launch_wide<T, KS, KGPT, 1>(ctx, p, nct, st);
-        case 2: return launch_wide<T, KS, KGPT, 2>(ctx, p, nct, st);
-        case 3: return launch_wide<T, KS, KGPT, 3>(ctx, p, nct, st);
-    }
-    return ctx->fail(SR_ERR_INVALID, "conv: unsupported NT");
-}
-template <typename T, int KS>
-int dispatch_thin_nt(sr_ctx* ctx, const ConvParams& p, int NT, int nct, hipStream_t st) {
-    switch (NT) {
-        case 1: return launch_thin<T, KS, 1>(ctx, p, nct, st);
-        case 2: return launch_thin<T, KS, 2>(ctx, p, nct, st);
-        case 3: return launch_thin<T, KS, 3>(ctx, p, nct, st);
+int dispatch_wide_nt(sr_ctx* ctx, const ConvParams& p, const ConvRoute& rt, int nct, hipStream_t st) {
+    switch (rt.NT) {
+        case 1: return launch_wide<T, KS, KGPT, 1>(ctx, p, nct, rt.sub, st);
+        case 2: return launch_wide<T, KS, KGPT, 2>(ctx, p, nct, rt.sub, st);
+        case 3: return launch_wide<T, KS, KGPT, 3>(ctx, p, nct, rt.sub, st);
     }
     return ctx->fail(SR_ERR_INVALID, "conv: unsupported NT");
 }
 
 template <typename T>
-int dispatch(sr_ctx* ctx, const ConvWeights& w, const ConvParams& p, int nct, hipStream_t st) {
+int dispatch(sr_ctx* ctx, const ConvRoute& rt, const ConvParams& p, int nct, hipStream_t st) {
     if constexpr (std::is_same<T, float>::value) {
         // SRCNN's head (SRCNN_model.py:50): 9x9 on an RGB image to 96 channels, optionally with the 1x1 that follows it in the epilogue
         // (the packed weights of a thin conv are [cout tile of 32][k-group][lane][4]: NT = 1 with three cout tiles per pixel tile when the head runs alone --
         // three waves per SIMD, which beat one wave per SIMD at NT = 3 by 1.8x in round 1 --; the fused variant needs all 96 couts of a pixel in one
         // workgroup and reads the same bytes as [k-group][cout tile] through a stride: see the weight stage)
-        if (w.thin && w.KS == 9 && w.Cin == 3 && w.CoutP == 96) {
-            // tile height / weight-stage depth measured on 4 x 1024 x 1024 images (round 4, same box): 8 x 16 tiles with 8 k-groups per stage 2.04 ms,
-            // 4 per stage 2.09, 16 x 16 tiles 2.32-2.35, 24 x 16 tiles (one wave per SIMD) 3.05 -- occupancy, not weight traffic, is what this kernel wants
-            if (p.pw2w) return launch_thin<T, 9, 3, 3, true, 1, 8>(ctx, p, 1, st);
-            return launch_thin<T, 9, 1, 3, false>(ctx, p, nct, st);
-        }
+        // tile height / weight-stage depth measured on 4 x 1024 x 1024 images (round 4, same box): 8 x 16 tiles with 8 k-groups per stage 2.04 ms,
+        // 4 per stage 2.09, 16 x 16 tiles 2.32-2.35, 24 x 16 tiles (one wave per SIMD) 3.05 -- occupancy, not weight traffic, is what this kernel wants
+        if (rt.fam == CF_THIN && rt.sub == CS_PW2) return launch_thin<T, 9, 3, 3, true, 1, 8>(ctx, p, 1, st);
+        if (rt.fam == CF_THIN && rt.NV == 3) return launch_thin<T, 9, 1, 3, false>(ctx, p, nct, st);
     }
     if (p.pw2w) return ctx->fail(SR_ERR_INVALID, "conv: the fused 1x1 follows the fp32 9x9 RGB head only");
-    if (w.thin) {
-        switch (w.KS) {
-            case 3: return dispatch_thin_nt<T, 3>(ctx, p, w.NT, nct, st);
-            case 5: return dispatch_thin_nt<T, 5>(ctx, p, w.NT, nct, st);      // input gradient of SRCNN's 5x5 32 -> 3 conv (3 -> 32 on dy)
-            case 9: return dispatch_thin_nt<T, 9>(ctx, p, w.NT, nct, st);
+    if (rt.fam == CF_THIN) {
+        // conv_pack_weights gives every thin conv one 32-cout block per workgroup (NT = 1); only the fused head above owns more
+        if (rt.NT != 1) return ctx->fail(SR_ERR_INVALID, "conv: a thin conv takes one 32-cout block per workgroup");
+        switch (rt.KS) {
+            case 3: return launch_thin<T, 3, 1>(ctx, p, nct, st);
+            case 5: return launch_thin<T, 5, 1>(ctx, p, nct, st);      // input gradient of SRCNN's 5x5 32 -> 3 conv (3 -> 32 on dy)
+            case 9: return launch_thin<T, 9, 1>(ctx, p, nct, st);
         }
     } else {
-        if (w.KS == 1 && w.KGPT == 4) return dispatch_wide_nt<T, 1, 4>(ctx, p, w.NT, nct, st);
-        if (w.KS == 1 && w.KGPT == 2) return dispatch_wide_nt<T, 1, 2>(ctx, p, w.NT, nct, st);
-        if (w.KS == 3 && w.KGPT == 2) return dispatch_wide_nt<T, 3, 2>(ctx, p, w.NT, nct, st);
-        if (w.KS == 5 && w.KGPT == 2 && w.NT == 1) return launch_wide<T, 5, 2, 1>(ctx, p, nct, st);
+        if (rt.KS == 1 && rt.KGPT == 4) return dispatch_wide_nt<T, 1, 4>(ctx, p, rt, nct, st);
+        if (rt.KS == 1 && rt.KGPT == 2) return dispatch_wide_nt<T, 1, 2>(ctx, p, rt, nct, st);
+        if (rt.KS == 3 && rt.KGPT == 2) return dispatch_wide_nt<T, 3, 2>(ctx, p, rt, nct, st);
+        if (rt.KS == 5 && rt.KGPT == 2 && rt.NT == 1) return launch_wide<T, 5, 2, 1>(ctx, p, nct, rt.sub, st);
     }
-    return ctx->fail(SR_ERR_INVALID, "conv: unsupported kernel size " + std::to_string(w.KS));
+    return ctx->fail(SR_ERR_INVALID, "conv: unsupported kernel size " + std::to_string(rt.KS));
 }
 
 inline uint16_t f32_to_bf16_host(float f) {
@@ -649,13 +655,17 @@ __global__ void __launch_bounds__(256) conv_fewcout_full_kernel(ConvParams p) {
     if (oy < H && ox < W) epilogue4<float>(p, b, oy, ox, 0, a4);
 }
 
+// LDS bytes of conv_fewcout_full_kernel: the halo tile at its padded pixel stride and all the layer's weights
+static int fewcout_full_lds(int KS, int nchunks) {
+    const int PS = 16 + KS - 1;
+    return PS * PS * (nchunks * 4 + 4) * 4 + nchunks * KS * KS * 16 * 4;
+}
+
 template <int KS>
-int launch_fewcout(sr_ctx* ctx, const ConvParams& p, hipStream_t st) {
+int launch_fewcout(sr_ctx* ctx, const ConvParams& p, int sub, hipStream_t st) {
     if (p.B > 65535 || (p.H + 15) / 16 > 65535) return ctx->fail(SR_ERR_INVALID, "conv: too many tiles for one launch");
-    constexpr int PS = 16 + KS - 1;
-    const int CinP = p.nchunks * 4;
-    const int lds = PS * PS * (CinP + 4) * 4 + p.nchunks * KS * KS * 16 * 4;
-    if (lds <= 80 * 1024 && (p.in_cs & 3) == 0 && (p.in_coff & 3) == 0) {      // two workgroups per CU
+    if (sub == CS_LDS) {
+        const int lds = fewcout_full_lds(KS, p.nchunks);
         auto kern = conv_fewcout_full_kernel<KS>;
         if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
         hipLaunchKernelGGL(kern, dim3((p.W + 15) / 16, (p.H + 15) / 16, p.B), dim3(256), lds, st, p);
@@ -670,6 +680,60 @@ int launch_fewcout(sr_ctx* ctx, const ConvParams& p, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+// The kernel a conv_launch runs, from the packed weights and the launch's parameters (after skip_lds / the fused epilogues are set)
+static ConvRoute conv_route(sr_ctx* ctx, const ConvWeights& w, const ConvParams& p, int nct) {
+    ConvRoute rt;
+    rt.dtype = w.dtype; rt.KS = w.KS; rt.KGPT = w.KGPT; rt.NT = w.NT;
+    if (w.few) {
+        rt.fam = CF_FEW;
+        // two workgroups per CU with the whole channel depth staged; the 4-channel kernel otherwise
+        rt.sub = (fewcout_full_lds(w.KS, p.nchunks) <= 80 * 1024 && (p.in_cs & 3) == 0 && (p.in_coff & 3) == 0) ? CS_LDS : CS_DIRECT;
+    } else if ((ctx->chain_mask & SR_FUSE_CONV_STREAM) != 0 && conv_stream_supported(w, p)) {
+        rt.fam = CF_STREAM;
+    } else if (w.rows) {
+        rt.fam = CF_ROWS;
+        rt.sub = p.f2w ? CS_RGBTAIL : p.plout ? CS_POOL : p.pjw ? CS_PROJ : (p.skip_lds && w.NT == 4) ? CS_SKIP_LDS : CS_NONE;
+    } else if (w.pw) {
+        rt.fam = CF_PW;
+        rt.KGPT = w.nchunks;
+    } else if (w.thin) {
+        rt.fam = CF_THIN;
+        if (w.dtype == SR_DTYPE_F32 && w.KS == 9 && w.Cin == 3 && w.CoutP == 96) {      // SRCNN's head: the padding channel's MFMA is skipped
+            rt.NV = 3;
+            if (p.pw2w) { rt.NT = 3; rt.sub = CS_PW2; }
+        }
+    } else {
+        rt.fam = CF_WIDE;
+        rt.sub = CS_MT3;
+        if (w.dtype == SR_DTYPE_F32) {
+            // 24 x 16 tiles give fewer than two workgroups per CU: 8 x 16 tiles; fewer than one 8 x 16 tile per CU for a single op's 3x3: split K as well
+            const int64_t px16 = (int64_t)((p.W + 15) / 16) * p.B * nct;
+            const int64_t wgs3 = px16 * ((p.H + 8 * MT_DEFAULT - 1) / (8 * MT_DEFAULT)), wgs1 = px16 * ((p.H + 7) / 8);
+            if (w.KS == 3 && w.KGPT == 2 && p.splitk_ok && wgs1 < ctx->cu_count()) rt.sub = CS_SK;
+            else if (wgs3 < 2 * ctx->cu_count()) rt.sub = CS_MT1;
+        }
+    }
+    return rt;
+}
+
+// e.g. "wide<f32,k3,kg2,nt2>/sk", "pw<bf16,nb3,nch2>", "rows<bf16,nb4>/skip_lds", "few<f32,k5>/direct", "thin<f32,k9,nt1,nv3>"
+static std::string conv_route_name(const ConvRoute& rt) {
+    static const char* fams[] = {"few", "thin", "wide", "pw", "rows", "stream"};
+    static const char* subs[] = {"", "sk", "mt1", "mt3", "lds", "direct", "pw2", "skip_lds", "rgbtail", "pool", "proj"};
+    const char* dt = rt.dtype == SR_DTYPE_BF16 ? "bf16" : "f32";
+    char nm[96];
+    switch (rt.fam) {
+        case CF_FEW: snprintf(nm, sizeof nm, "few<%s,k%d>", dt, rt.KS); break;
+        case CF_THIN: snprintf(nm, sizeof nm, "thin<%s,k%d,nt%d,nv%d>", dt, rt.KS, rt.NT, rt.NV); break;
+        case CF_WIDE: snprintf(nm, sizeof nm, "wide<%s,k%d,kg%d,nt%d>", dt, rt.KS, rt.KGPT, rt.NT); break;
+        case CF_PW: snprintf(nm, sizeof nm, "pw<%s,nb%d,nch%d>", dt, rt.NT, rt.KGPT); break;
+        default: snprintf(nm, sizeof nm, "%s<%s,nb%d>", fams[rt.fam], dt, rt.NT); break;
+    }
+    std::string s = nm;
+    if (rt.sub != CS_NONE) s += std::string("/") + subs[rt.sub];
+    return s;
+}
+
 int conv_pack_weights(sr_ctx* ctx, const float* hwio, const float* bias, int KS, int Cin, int Cout, int dtype,
                       ConvWeights* out, int rows_head) {
     if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return ctx->fail(SR_ERR_INVALID, "conv: dtype must be f32 or bf16");
@@ -682,10 +746,11 @@ int conv_pack_weights(sr_ctx* ctx, const float* hwio, const float* bias, int KS,
     w.NT = (nb % 2 == 0) ? 2 : (nb % 3 == 0 ? 3 : 1);
     if (KS == 5 && !(Cin <= E)) w.NT = 1;   // 25 taps of weights: keep the LDS stage small
     const bool as_rows = rows_head && dtype == SR_DTYPE_BF16 && KS == 3;
-    if (Cin <= E && !as_rows) w.NT = 1;      // thin (RGB) inputs: one 32-cout block per workgroup (112 + 48 registers, 3 waves/SIMD);
+    // thin (RGB) inputs pair two taps in a k-group; a 1x1 has no second tap and takes the wide / 1x1 kernels on zero-padded channels instead
+    w.thin = Cin <= E && !as_rows && KS != 1;
+    if (w.thin) w.NT = 1;                    // thin: one 32-cout block per workgroup (112 + 48 registers, 3 waves/SIMD);
                                              // re-reading the 3-channel input per cout block is cheap, 1 wave/SIMD at NT=3 was not (9x9: 1.8x)
     const int nct = nb / w.NT, ntap = KS * KS;
-    w.thin = Cin <= E && !as_rows;
     // fp32, <= 4 couts, not thin: the VALU kernel (conv_fewcout_f32_kernel), weights [tap][CinP][4]
     w.few = (dtype == SR_DTYPE_F32 && Cout <= 4 && !w.thin && (KS == 3 || KS == 5)) ? 1 : 0;
     w.rows = (dtype == SR_DTYPE_BF16 && KS == 3 && !w.thin) ? 1 : 0;
@@ -846,9 +911,9 @@ static int conv_plan_f32(sr_ctx* ctx, int KS, int Cin, int Cout, int rot, ConvWe
     const int nb = w.CoutP / 32;
     w.NT = (nb % 2 == 0) ? 2 : (nb % 3 == 0 ? 3 : 1);
     if (KS == 5 && !(Cin <= E)) w.NT = 1;
-    if (Cin <= E) w.NT = 1;
+    w.thin = Cin <= E && KS != 1;                                    // as conv_pack_weights
+    if (w.thin) w.NT = 1;
     const int nct = nb / w.NT;
-    w.thin = Cin <= E;
     w.few = (Cout <= 4 && !w.thin && (KS == 3 || KS == 5)) ? 1 : 0;
     w.rows = 0; w.pw = 0;
     if (!w.thin && KS == 9) return ctx->fail(SR_ERR_INVALID, "conv: 9x9 supported for <= one 16-byte channel slice only");
@@ -1049,7 +1114,9 @@ int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, i
         p.f2w = static_cast<const char*>(ep.f2->a); p.f2part = ep.f2_part; p.f2c = ep.f2->c2;
     }
     const int nct = w.CoutP / 32 / w.NT;
-    const bool stream = (ctx->chain_mask & SR_FUSE_CONV_STREAM) != 0 && conv_stream_supported(w, p);
+    const ConvRoute rt = conv_route(ctx, w, p, nct);
+    const bool stream = rt.fam == CF_STREAM;
+    if (ctx->route_log) ctx->route_text += conv_route_name(rt) + "\n";
     int rec = -1;
     if (ctx->prof && ep.f2) {
         const double px = (double)B * H * W;
@@ -1076,9 +1143,14 @@ int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, i
         if (p.s2) bytes += px * w.Cout * esz;
         rec = ctx->prof_open(nm, 2.0 * px * w.KS * w.KS * w.Cin * w.Cout, bytes, st);
     }
-    const int rc = w.few ? (w.KS == 3 ? launch_fewcout<3>(ctx, p, st) : launch_fewcout<5>(ctx, p, st))
-                   : stream ? conv_stream_launch(ctx, w, p, st) : w.rows ? conv_rows_launch(ctx, w, p, st) : w.pw ? conv_pw_launch(ctx, w, p, st)
-                          : ((w.dtype == SR_DTYPE_BF16) ? dispatch<bf16_t>(ctx, w, p, nct, st) : dispatch<float>(ctx, w, p, nct, st));
+    int rc;
+    switch (rt.fam) {
+        case CF_FEW: rc = w.KS == 3 ? launch_fewcout<3>(ctx, p, rt.sub, st) : launch_fewcout<5>(ctx, p, rt.sub, st); break;
+        case CF_STREAM: rc = conv_stream_launch(ctx, w, p, st); break;
+        case CF_ROWS: rc = conv_rows_launch(ctx, w, p, st); break;
+        case CF_PW: rc = conv_pw_launch(ctx, w, p, st); break;
+        default: rc = (w.dtype == SR_DTYPE_BF16) ? dispatch<bf16_t>(ctx, rt, p, nct, st) : dispatch<float>(ctx, rt, p, nct, st); break;
+    }
     ctx->prof_close(rec, st);
     return rc;
 }

@@ -57,6 +57,7 @@ SIGNATURES = {
     "sr_debug_set_chain_stamp_buffer": (_i, [_vp, _vp, _i64]),
     "sr_debug_set_fused": (_i, [_vp, _i, _i]),
     "sr_debug_set_alloc_cap": (_i, [_vp, _i64]),
+    "sr_debug_conv_routes": (_i, [_vp, _i, C.c_char_p, _i64]),
     "sr_profile_begin": (_i, [_vp]),
     "sr_profile_end": (_i, [_vp, C.c_char_p, _i64]),
     "sr_model_create": (_i, [_vp, _i, C.POINTER(ModelCfg), C.POINTER(_vp)]),

@@ -132,6 +132,13 @@ class Context:
         """Test hook: allocations through this context fail once it would hold more than nbytes (0 = no cap)."""
         self.check(self.lib.sr_debug_set_alloc_cap(self.h, int(nbytes)))
 
+    def conv_routes(self, enable=True):
+        """Test hook: the kernel variants (e.g. 'wide<f32,k3,kg2,nt2>/sk') of the conv launches since the previous call, in launch order;
+        conv launches after this call are logged iff `enable` (sr_debug_conv_routes)."""
+        buf = C.create_string_buffer(1 << 16)
+        self.check(self.lib.sr_debug_conv_routes(self.h, int(bool(enable)), buf, len(buf)))
+        return buf.value.decode().split()
+
     def profile_begin(self):
         self.check(self.lib.sr_profile_begin(self.h))
 

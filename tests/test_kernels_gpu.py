@@ -132,17 +132,21 @@ def test_conv2d_skip_is_own_input(ctx, hw, which):
     b = rng.uniform(-0.1, 0.1, 64).astype(np.float32)
     xd, od = _dev(ctx, x, torch.bfloat16), _dev(ctx, other, torch.bfloat16)
     conv = O.conv2d(x, w, b, dtype=np.float64)
+    ctx.conv_routes(True)
     if which == 1:      # x is skip 1, alone
         ref = 0.2 * conv + x
         got = ctx.conv2d(xd, w, b, alpha=0.2, skip1=xd, beta1=1.0)
     else:               # RRDB tail: another tensor is skip 1, x is skip 2
         ref = 0.04 * conv + other + 0.2 * x
         got = ctx.conv2d(xd, w, b, alpha=0.04, skip1=od, beta1=1.0, skip2=xd, beta2=0.2)
+    assert ctx.conv_routes(True) == ["rows<bf16,nb4>/skip_lds"]
     assert_bf16_close(got.float().cpu().numpy(), ref)
     # and against the same op with the skip passed as a separate copy (HBM path): equal up to one bf16 ulp of fp32 re-association
     xc = xd.clone()
     got2 = ctx.conv2d(xd, w, b, alpha=0.2, skip1=xc, beta1=1.0) if which == 1 else \
         ctx.conv2d(xd, w, b, alpha=0.04, skip1=od, beta1=1.0, skip2=xc, beta2=0.2)
+    hbm = ctx.conv_routes(False)
+    assert len(hbm) == 1 and hbm[0] in ("rows<bf16,nb4>", "stream<bf16,nb4>"), hbm
     d = (got.float() - got2.float()).abs().max().item()
     assert d <= 2 ** -6 * max(1.0, float(np.abs(ref).max())), d
 
