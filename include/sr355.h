@@ -321,6 +321,63 @@ int  sr_classic_scores(sr_ctx* ctx, const void* hr, int hr_dtype, const void* sr
                        const double* data_range_f64, double hf_radius_frac, double* scores_f64, float* gray_f32, float* sobel_f32,
                        int* hist_luma_i32, int* hist_color_i32, void* stream);
 
+/* ---- the dataset EDA's per-pair image statistics and global accumulators (reference data/EDA.ipynb: ImageDatasetAnalyzer, cell
+ * 87582ba8; MetricsAggregator.collect, cell eb5cc926), csrc/eda.hip.  B aligned pairs of one shape, lr_u8 and hr_u8 DEVICE uint8
+ * [B,H,W,3] in BGR order (lr already resized to hr's size); 7 <= H, W <= 4096, H W <= 2^22, B <= 32767 (anything else: SR_ERR_INVALID).
+ * The 8-bit OpenCV paths are restated from OpenCV's documented behaviour (cv2 is not installed where this project runs, so they are
+ * not pinned against cv2 itself):
+ *   gray    COLOR_BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14 (imgproc/src/color_yuv, the 14-bit RGB2Gray coefficients);
+ *   blurs   GaussianBlur (3,3) / (5,5) with sigma 0: the fixed taps (1 2 1) / 4 and (1 4 6 4 1) / 16 (getGaussianKernel's small-kernel
+ *           table), separable, the exact integer sum rounded half up once, (s + 8) >> 4 / (s + 128) >> 8, BORDER_REFLECT_101;
+ *   HSV     COLOR_BGR2HSV's V = max(B, G, R) and S = ((V - min) sdiv[V] + 2^11) >> 12, sdiv[v] = round(255 2^12 / v), sdiv[0] = 0
+ *           (color_hsv's RGB2HSV_b tables); H is not computed;
+ *   Canny   (gray, 100, 200), aperture 3, L1 magnitude |gx| + |gy| of the 3 x 3 Sobel pair with replicated borders; a pixel with
+ *           magnitude m > 100 survives when, with x = |gx|, y = |gy| 2^15: y < 13573 x: m > left and m >= right; y > 13573 x + x 2^16:
+ *           m > above and m >= below; otherwise, s = -1 where gx and gy differ in sign, else 1: m > (above, column - s) and
+ *           m > (below, column + s) (imgproc/src/canny.cpp).  A survivor is strong when m > 200; an edge is a survivor that is strong or
+ *           8-connected to a strong one through survivors.  The outermost rows and columns are never edges and carry no connection
+ *           (their magnitudes still take part in their neighbours' suppression).  The other reading of canny.cpp: it pads its
+ *           magnitude and label buffers by one pixel and runs the same test on border pixels against zero magnitude outside, so
+ *           border pixels could be edges; the project's contract fixes the first reading;
+ *   dilate  5 x 5 ones, centred anchor, pixels outside the image ignored.
+ * sr_eda_pair_stats: stats_f64 DEVICE [B,SR_NUM_EDA_STATS] in SR_EDA_* order, _LR / _HR of the pair's two images:
+ *   psnr, ssim        sr_classic_scores' columns for (hr, lr), data range 255 (skimage, channel_axis=2);
+ *   glcm_*            glcm_features on lr's gray: quantised to glcm_levels (64 or 256) as (uint8)(float32(g) / 255 * (levels - 1)),
+ *                     graycomatrix(distance 1, symmetric, normed) for the angles of angle_mask (bit 0: 0, 1: 45, 2: 90, 3: 135 deg;
+ *                     offsets (row, col) (0,1), (1,1), (1,0), (1,-1)), graycoprops contrast / homogeneity / correlation (1 where the
+ *                     marginal variance is 0), mean over the angles;
+ *   rms_noise         sqrt(mean((gray - blur3(gray))^2));   lap_var  population variance of the 0 1 0 / 1 -4 1 / 0 1 0 Laplacian of
+ *                     gray, BORDER_REFLECT_101;
+ *   blocking          (mean|D[7::8, :]| + mean|D[:, 7::8]|) / 2, D the orthonormal 2-D DCT-II of gray in fp64 (NaN below 8 rows or columns);
+ *   color_noise       mean over the three channels of |img - blur5(img)|;
+ *   ringing           population std of gray over dilate(E) and not E, E = Canny's edges; 0 when that region is empty;
+ *   saturation_mean, brightness_mean   means of S and V;
+ *   edge_diff         sobel_mean_hr - sobel_mean_lr, skimage.filters.sobel: sqrt((h^2 + v^2) / 2) of the (1 2 1) x (1 0 -1) / 4 pair on
+ *                     gray / 255, edge pixels repeated;
+ *   chN_skew, chN_kurt, chN_mean, chN_std   per B, G, R channel: m3 / m2^1.5, m4 / m2^2 - 3 (NaN for a constant channel), mean,
+ *                     population std, the central moments formed exactly from integer power sums.
+ *   Optional raw outputs (NULL: not written): gray_u8, sat_u8, val_u8, blur3_u8 (of gray), edges_u8 (0 / 255) [B,2,H,W] (lr, hr);
+ *   blur5_u8 [B,2,H,W,3]; glcm_i32 [B,nangles,L,L] lr's counts before symmetrisation, angles in bit order; dct_f64 [B,2,H,W].
+ *   Every reduction is an integer sum or runs in a fixed order: a pair's row is bitwise the same on every run and for any B.
+ * sr_eda_accumulate: collect's global_data, added pair after pair into caller-owned DEVICE buffers: fft_lr_sum_f64, fft_hr_sum_f64
+ *   [H,W] += |fftshift(fft2(gray))|; grad_hr_sum_f64 [H,W] += hypot of hr gray's ksize-5 Sobel pair (1 4 6 4 1 x -1 -2 0 2 1,
+ *   BORDER_REFLECT_101); glcm_sum_f64 [256,256] += lr gray's 256-level, angle-0, symmetric normed matrix (integer counts divided in
+ *   fp64); sat_counts_i64 [2,50] (lr, hr) += np.histogram(S, linspace(0, 256, 51)).  One call on 3 pairs equals three calls. */
+enum { SR_EDA_PSNR = 0, SR_EDA_SSIM, SR_EDA_GLCM_CONTRAST, SR_EDA_GLCM_HOMOGENEITY, SR_EDA_GLCM_CORRELATION, SR_EDA_RMS_NOISE_LR,
+       SR_EDA_RMS_NOISE_HR, SR_EDA_LAP_VAR_LR, SR_EDA_LAP_VAR_HR, SR_EDA_BLOCKING_LR, SR_EDA_BLOCKING_HR, SR_EDA_COLOR_NOISE_LR,
+       SR_EDA_COLOR_NOISE_HR, SR_EDA_RINGING_LR, SR_EDA_RINGING_HR, SR_EDA_SATURATION_MEAN_LR, SR_EDA_SATURATION_MEAN_HR,
+       SR_EDA_BRIGHTNESS_MEAN_LR, SR_EDA_BRIGHTNESS_MEAN_HR, SR_EDA_EDGE_DIFF,
+       SR_EDA_CH0_SKEW_LR, SR_EDA_CH0_SKEW_HR, SR_EDA_CH1_SKEW_LR, SR_EDA_CH1_SKEW_HR, SR_EDA_CH2_SKEW_LR, SR_EDA_CH2_SKEW_HR,
+       SR_EDA_CH0_KURT_LR, SR_EDA_CH0_KURT_HR, SR_EDA_CH1_KURT_LR, SR_EDA_CH1_KURT_HR, SR_EDA_CH2_KURT_LR, SR_EDA_CH2_KURT_HR,
+       SR_EDA_SOBEL_MEAN_LR, SR_EDA_SOBEL_MEAN_HR,
+       SR_EDA_CH0_MEAN_LR, SR_EDA_CH0_MEAN_HR, SR_EDA_CH1_MEAN_LR, SR_EDA_CH1_MEAN_HR, SR_EDA_CH2_MEAN_LR, SR_EDA_CH2_MEAN_HR,
+       SR_EDA_CH0_STD_LR, SR_EDA_CH0_STD_HR, SR_EDA_CH1_STD_LR, SR_EDA_CH1_STD_HR, SR_EDA_CH2_STD_LR, SR_EDA_CH2_STD_HR, SR_NUM_EDA_STATS };
+int  sr_eda_pair_stats(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, int glcm_levels, int angle_mask,
+                       double* stats_f64, uint8_t* gray_u8, uint8_t* sat_u8, uint8_t* val_u8, uint8_t* blur3_u8, uint8_t* blur5_u8,
+                       uint8_t* edges_u8, int* glcm_i32, double* dct_f64, void* stream);
+int  sr_eda_accumulate(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, double* fft_lr_sum_f64,
+                       double* fft_hr_sum_f64, double* grad_hr_sum_f64, double* glcm_sum_f64, int64_t* sat_counts_i64, void* stream);
+
 /* ---- FineTunedVGG16.fit's per-batch work besides the frozen base (reference VGG16_model.py:111-157), csrc/head_train.hip ----
  * sr_affine_warp: the ImageDataGenerator transform of VGG16_model.py:129-134 as FineTunedVGG16._augment computes it (scipy
  *   affine_transform order=1, mode="nearest", per channel, then the flip), with the batch's gather fused in.  x DEVICE fp32 [N,H,W,C];

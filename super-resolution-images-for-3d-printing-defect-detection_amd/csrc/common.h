@@ -55,6 +55,8 @@ struct sr_ctx {
     std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape;
                                                     // metrics.hip: -N -> the N x N DFT exp(-2 pi i k x / N)
     Arena met_work, met_fft;            // metrics.hip: flags / partials / histograms, the DFT chunk's operands (stream-ordered reuse)
+    Arena eda_work, eda_dct;            // eda.hip: accumulators / label maps / co-occurrence counts, the DCT / DFT chunk's operands; its DCT operators sit in
+                                        // dft_ops under the keys -(2^32 + N)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
     struct PackKey {

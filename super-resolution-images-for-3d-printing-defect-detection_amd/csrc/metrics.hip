@@ -260,35 +260,7 @@ __global__ void gray_f64_kernel(const void* hr, int hr_dt, const void* sr, int s
     }
 }
 
-// A_N[k][x] = exp(-2 pi i k x / N), the phase reduced exactly in integers; [N][N] real parts, then [N][N] imaginary parts
-__global__ void dft_full_operator_kernel(int N, double* re, double* im) {
-    const int64_t total = (int64_t)N * N;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t m = ((i / N) * (i % N)) % N;
-        double sn, cs;
-        sincospi(2.0 * (double)m / (double)N, &sn, &cs);
-        re[i] = cs;
-        im[i] = -sn;
-    }
-}
-
-// the operator of one N, built once per context; its dft_ops key is -N (frequency extrapolation's keys (N << 32) | n are positive)
-int dft_full_operator(sr_ctx* ctx, int N, hipStream_t st, const double** re, const double** im) {
-    const int64_t key = -(int64_t)N;
-    auto it = ctx->dft_ops.find(key);
-    if (it == ctx->dft_ops.end()) {
-        const int64_t nel = (int64_t)N * N;
-        double* p = static_cast<double*>(ctx->dalloc(sizeof(double) * (size_t)nel * 2));
-        if (!p) return SR_ERR_OOM;
-        hipLaunchKernelGGL(dft_full_operator_kernel, dim3(met_grid(nel)), dim3(256), 0, st, N, p, p + nel);
-        SR_HIP(ctx, hipGetLastError());
-        SR_HIP(ctx, hipStreamSynchronize(st));      // once per size: later calls may come on other streams
-        it = ctx->dft_ops.emplace(key, p).first;
-    }
-    *re = it->second;
-    *im = it->second + (int64_t)N * N;
-    return SR_OK;
-}
+// (dft_full_operator, the cached N x N operator A_N[k][x] = exp(-2 pi i k x / N), lives in cgemm_f64.h: eda.hip shares it)
 
 // ------------------------------------------------------------------------------------------------
 // 4. finalize: one workgroup per pair -> out[b][9]

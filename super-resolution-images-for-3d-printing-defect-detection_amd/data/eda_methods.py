@@ -1,0 +1,332 @@
+"""The dataset EDA's metrics (reference: data/EDA.ipynb -- ImagePairLoader, ImageDatasetAnalyzer, ImagePairMetrics, MetricsAggregator,
+StatsReporter), with every per-pair statistic and global accumulator on the MI355X (csrc/eda.hip: sr_eda_pair_stats, sr_eda_accumulate)
+and the bookkeeping on the host in NumPy.  A notebook imports these names instead of defining the cells; cv2, scikit-image, scipy and
+pandas are not needed.
+
+Images are uint8 BGR [H, W, 3] as cv2.imread returns them (files are decoded through PIL and the channel order restored), gray images
+uint8 [H, W].  The single-image methods take NumPy arrays and return Python floats / dicts.  The device derives the gray and HSV planes
+from the BGR image itself, so the methods that the reference hands a precomputed plane (feature_distribution(img, hsv),
+detect_artifacts(img, gray)) check that plane against the device's and raise ValueError on a mismatch; rms_noise, laplacian_variance
+and glcm_features, which receive only a gray image, run on it as a BGR image with three equal channels (its COLOR_BGR2GRAY is itself).
+The OpenCV 8-bit semantics (gray, Gaussian blurs, HSV, Canny, dilation) are the contract stated in include/sr355.h.
+Each single-image method scores the pair (img, img) through the whole device pipeline (classic scores, Canny, GLCM, both DCTs) to
+return its one number or dict: fine for a notebook cell, wasteful in a loop -- collect / collect_arrays make one pass per batch and are
+the way to score a dataset.
+
+Out of scope: LPIPS (its AlexNet and LPIPS weights exist nowhere this project runs): the rows' lpips column is NaN, lpips_score raises
+NotImplementedError and nothing here sorts by LPIPS; every matplotlib / seaborn panel.  Importing this module and its host helpers
+(ImagePairLoader.iter_pairs, ImagePairMetrics, StatsReporter) needs no GPU."""
+import math
+import os
+
+import numpy as np
+
+ANGLES = (0.0, math.pi / 4, math.pi / 2, 3 * math.pi / 4)
+SAT_BINS = np.linspace(0, 256, 51)
+# OpenCV interpolation names the device resize does not offer for uint8 images
+_INTERP_KNOWN_NOT_OFFERED = ("INTER_LINEAR_EXACT", "INTER_NEAREST_EXACT", "INTER_BITS", "INTER_BITS2", "INTER_MAX")
+
+
+def _context():
+    from sr355 import Context                  # loaded on first use: the host helpers run without a GPU
+    return Context.get()
+
+
+def _row_columns():
+    from sr355 import _lib
+    return _lib.EDA_ROW_COLUMNS
+
+
+def _bgr(img, name):
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise NotImplementedError(f"{name}: expected a uint8 BGR image [H, W, 3], got {a.dtype} {a.shape} (the EDA reads 8-bit BGR files only)")
+    return np.ascontiguousarray(a)
+
+
+def _gray(gray, name):
+    a = np.asarray(gray)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise NotImplementedError(f"{name}: expected a uint8 gray image [H, W], got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _angle_indices(angles, multi_angle):
+    if angles is None:
+        return (0, 1, 2, 3) if multi_angle else (0,)
+    out = []
+    for a in angles:
+        hit = [i for i, s in enumerate(ANGLES) if abs(float(a) - s) < 1e-9]
+        if not hit:
+            raise NotImplementedError(f"glcm_features: angle {a!r} is not one of 0, pi/4, pi/2, 3 pi/4")
+        out.append(hit[0])
+    if len(set(out)) != len(out):
+        raise NotImplementedError("glcm_features: repeated angles are not offered")
+    return tuple(out)
+
+
+def _single(img, levels=64, angles=(0,), raw=False):
+    """One image scored as the pair (img, img): -> ({stat name: float}, raw dict of NumPy planes or None)."""
+    ctx = _context()
+    x = ctx.to_device(img[None])
+    res = ctx.eda_pair_stats(x, x, levels, angles, raw=raw)
+    stats, inter = res if raw else (res, None)
+    vals = dict(zip(ctx.EDA_STAT_NAMES, (float(v) for v in stats[0].cpu().numpy())))
+    return vals, (None if inter is None else {k: v[0].cpu().numpy() for k, v in inter.items()})
+
+
+class ImagePairLoader:
+    """Iterating and aligning LR / HR pairs."""
+
+    @staticmethod
+    def iter_pairs(lr_base, hr_base):
+        """Yields (lr_relpath, hr_relpath) for every .png / .jpg / .jpeg present under both trees, in lexicographic order."""
+        exts = (".png", ".jpg", ".jpeg")
+
+        def rel(base):
+            return {os.path.relpath(os.path.join(root, f), base) for root, _, files in os.walk(base) for f in files if f.lower().endswith(exts)}
+
+        common = sorted(rel(lr_base) & rel(hr_base))
+        if not common:
+            raise ValueError("No matching LR/HR image pairs were found under the provided directories.")
+        for r in common:
+            yield r, r
+
+    @staticmethod
+    def read_bgr(path):
+        """cv2.imread's array for an 8-bit colour file: uint8 [H, W, 3], BGR (decoded through PIL, channel order restored)."""
+        from PIL import Image
+        try:
+            with Image.open(path) as im:
+                return np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8)[..., ::-1])
+        except OSError as e:
+            raise ValueError(f"Failed reading {path}") from e
+
+    @staticmethod
+    def interpolation_for(lr_path, interp_map=None):
+        """The interpolation name load_and_align uses for this file: the map's entry when it is one the reference knows, else INTER_LINEAR."""
+        name = None if interp_map is None else interp_map.get(os.path.basename(lr_path))
+        if name in _INTERP_KNOWN_NOT_OFFERED:
+            raise NotImplementedError(f"interpolation {name} is not offered by the device resize for uint8 images")
+        return name if name in ("INTER_LINEAR", "INTER_CUBIC", "INTER_AREA", "INTER_LANCZOS4") else "INTER_LINEAR"
+
+    @staticmethod
+    def load_and_align(lr_path, hr_path, interp_map=None):
+        """Reads both images and resizes LR to HR's size on the device when they differ -> (lr, hr) uint8 BGR."""
+        lr, hr = ImagePairLoader.read_bgr(lr_path), ImagePairLoader.read_bgr(hr_path)
+        if lr.shape[:2] != hr.shape[:2]:
+            ctx = _context()
+            lr = ctx.resize(ctx.to_device(lr[None]), hr.shape[0], hr.shape[1], ImagePairLoader.interpolation_for(lr_path, interp_map))[0].cpu().numpy()
+        return lr, hr
+
+
+class ImageDatasetAnalyzer:
+    """The reference's static per-image metrics."""
+
+    @staticmethod
+    def lpips_score(lr_img, hr_img):
+        raise NotImplementedError("lpips_score: LPIPS needs AlexNet and LPIPS weights that are not available here; it is out of this port's scope "
+                                  "(the rows' lpips column is NaN)")
+
+    @staticmethod
+    def rms_noise(gray):
+        g = _gray(gray, "rms_noise")
+        return _single(np.repeat(g[..., None], 3, 2))[0]["rms_noise_lr"]
+
+    @staticmethod
+    def laplacian_variance(gray):
+        g = _gray(gray, "laplacian_variance")
+        return _single(np.repeat(g[..., None], 3, 2))[0]["lap_var_lr"]
+
+    @staticmethod
+    def psnr_metric(lr_img, hr_img):
+        ctx = _context()
+        lr, hr = _bgr(lr_img, "psnr_metric"), _bgr(hr_img, "psnr_metric")
+        return float(ctx.classic_scores(ctx.to_device(hr[None]), ctx.to_device(lr[None]), 255.0)[0, 0])
+
+    @staticmethod
+    def ssim_metric(lr_img, hr_img):
+        ctx = _context()
+        lr, hr = _bgr(lr_img, "ssim_metric"), _bgr(hr_img, "ssim_metric")
+        return float(ctx.classic_scores(ctx.to_device(hr[None]), ctx.to_device(lr[None]), 255.0)[0, 1])
+
+    @staticmethod
+    def glcm_features(gray, angles=None, levels=64, multi_angle=False):
+        g = _gray(gray, "glcm_features")
+        if levels not in (64, 256):
+            raise NotImplementedError(f"glcm_features: levels {levels} is not offered (64 or 256)")
+        v = _single(np.repeat(g[..., None], 3, 2), levels, _angle_indices(angles, multi_angle))[0]
+        return {k: v[k] for k in ("glcm_contrast", "glcm_homogeneity", "glcm_correlation")}
+
+    @staticmethod
+    def feature_distribution(img, hsv):
+        a = _bgr(img, "feature_distribution")
+        v, raw = _single(a, raw=True)
+        hsv = np.asarray(hsv)
+        if hsv.shape != a.shape or not (np.array_equal(hsv[..., 1], raw["sat"][0]) and np.array_equal(hsv[..., 2], raw["val"][0])):
+            raise ValueError("feature_distribution: hsv is not COLOR_BGR2HSV of img (its S / V planes differ from the device's)")
+        out = {}
+        for c in range(3):
+            for k in ("mean", "std", "skew", "kurt"):
+                out[f"ch{c}_{k}"] = v[f"ch{c}_{k}_lr"]
+        out["saturation_mean"] = v["saturation_mean_lr"]
+        out["brightness_mean"] = v["brightness_mean_lr"]
+        return out
+
+    @staticmethod
+    def detect_artifacts(img, gray):
+        a = _bgr(img, "detect_artifacts")
+        v, raw = _single(a, raw=True)
+        if not np.array_equal(np.asarray(gray), raw["gray"][0]):
+            raise ValueError("detect_artifacts: gray is not COLOR_BGR2GRAY of img (it differs from the device's plane)")
+        return {"blocking_score": v["blocking_lr"], "color_noise": v["color_noise_lr"], "ringing_artifact": v["ringing_lr"]}
+
+    @staticmethod
+    def color_planes(img):
+        """(gray, hsv) of a BGR image as the notebook's cv2.cvtColor calls give them, from the device; hsv's H plane is zero (never used)."""
+        a = _bgr(img, "color_planes")
+        _, raw = _single(a, raw=True)
+        return raw["gray"][0], np.stack([np.zeros_like(raw["sat"][0]), raw["sat"][0], raw["val"][0]], -1)
+
+
+class ImagePairMetrics:
+    """The metrics of one LR / HR pair."""
+    FIELDS = ("filename", "lpips", "psnr", "ssim", "glcm_contrast", "glcm_homogeneity", "glcm_correlation", "rms_noise_lr", "rms_noise_hr",
+              "lap_var_lr", "lap_var_hr", "blocking_lr", "blocking_hr", "color_noise_lr", "color_noise_hr", "ringing_lr", "ringing_hr",
+              "saturation_mean_lr", "saturation_mean_hr", "brightness_mean_lr", "brightness_mean_hr", "edge_diff",
+              "ch0_skew_lr", "ch0_skew_hr", "ch1_skew_lr", "ch1_skew_hr", "ch2_skew_lr", "ch2_skew_hr",
+              "ch0_kurt_lr", "ch0_kurt_hr", "ch1_kurt_lr", "ch1_kurt_hr", "ch2_kurt_lr", "ch2_kurt_hr")
+
+    def __init__(self, filename, lpips, psnr, ssim, glcm_contrast, glcm_homogeneity, glcm_correlation, rms_noise_lr, rms_noise_hr, lap_var_lr,
+                 lap_var_hr, blocking_lr, blocking_hr, color_noise_lr, color_noise_hr, ringing_lr, ringing_hr, saturation_mean_lr,
+                 saturation_mean_hr, brightness_mean_lr, brightness_mean_hr, edge_diff, ch0_skew_lr=None, ch0_skew_hr=None, ch1_skew_lr=None,
+                 ch1_skew_hr=None, ch2_skew_lr=None, ch2_skew_hr=None, ch0_kurt_lr=None, ch0_kurt_hr=None, ch1_kurt_lr=None, ch1_kurt_hr=None,
+                 ch2_kurt_lr=None, ch2_kurt_hr=None):
+        args = locals()
+        for k in self.FIELDS:
+            setattr(self, k, args[k])
+
+    def as_dict(self):
+        return self.__dict__.copy()
+
+
+class MetricsAggregator:
+    """Metric extraction for all pairs."""
+    BATCH = 32
+
+    @staticmethod
+    def new_global_data():
+        return {"count": 0, "lr_fft_sum": None, "hr_fft_sum": None, "grad_hr_sum": None, "glcm_sum": None,
+                "sat_lr_counts": np.zeros(50, np.float64), "sat_hr_counts": np.zeros(50, np.float64), "sat_bins": SAT_BINS.copy(), "noise_means_lr": []}
+
+    @staticmethod
+    def collect_arrays(lr_imgs, hr_imgs, glcm_multi_angle=False, glcm_levels=64, filenames=None, device_acc=None, finish=True):
+        """collect on aligned stacks [B, H, W, 3] uint8 BGR (NumPy arrays or device tensors) -> (rows, global_data).  device_acc / finish
+        let a caller run several batches of one image size into the same device accumulators: pass the returned global_data['_device']
+        back in and finish=True on the last batch, which downloads the sums once."""
+        import torch
+        ctx = _context()
+        to_dev = lambda a: a.contiguous() if isinstance(a, torch.Tensor) else ctx.to_device(np.ascontiguousarray(np.asarray(a)))
+        lr, hr = to_dev(lr_imgs), to_dev(hr_imgs)
+        B = int(lr.shape[0])
+        names = list(filenames) if filenames is not None else [str(i) for i in range(B)]
+        if len(names) != B:
+            raise ValueError(f"collect_arrays: {len(names)} file names for {B} pairs")
+        cols = _row_columns()
+        stats = ctx.eda_pair_stats(lr, hr, glcm_levels, (0, 1, 2, 3) if glcm_multi_angle else (0,))
+        acc = ctx.eda_accumulate(lr, hr, device_acc)
+        host = stats.cpu().numpy()
+        rows = [ImagePairMetrics(filename=names[i].replace("\\", "/"), lpips=math.nan, **{k: float(host[i, j]) for j, k in enumerate(cols)}) for i in range(B)]
+        g = MetricsAggregator.new_global_data()
+        g["count"] = B
+        g["noise_means_lr"] = [r.color_noise_lr for r in rows]
+        g["_device"] = acc
+        if finish:
+            MetricsAggregator._download(g)
+        return rows, g
+
+    @staticmethod
+    def _download(g):
+        acc = g.pop("_device")
+        for k in ("lr_fft_sum", "hr_fft_sum", "grad_hr_sum"):
+            g[k] = acc[k].cpu().numpy()
+        g["glcm_sum"] = acc["glcm_sum"].cpu().numpy().reshape(256, 256, 1, 1)
+        sat = acc["sat_counts"].cpu().numpy()
+        g["sat_lr_counts"], g["sat_hr_counts"] = sat[0].astype(np.float64), sat[1].astype(np.float64)
+
+    @staticmethod
+    def collect(lr_dir, hr_dir, glcm_multi_angle=False, glcm_levels=64, interp_map=None):
+        """Metrics of every pair under the two trees and the global accumulators -> (rows in pair order, global_data).  Pairs are read on
+        the host, LR is aligned to HR on the device, and pairs of one (LR shape, HR shape, interpolation) go through the device in batches.
+        The global sums need one image size, as in the reference (its += fails otherwise)."""
+        pairs = list(ImagePairLoader.iter_pairs(lr_dir, hr_dir))
+        ctx = _context()
+        groups = {}
+        for idx, (lf, hf) in enumerate(pairs):
+            lr, hr = ImagePairLoader.read_bgr(os.path.join(lr_dir, lf)), ImagePairLoader.read_bgr(os.path.join(hr_dir, hf))
+            interp = ImagePairLoader.interpolation_for(lf, interp_map) if lr.shape != hr.shape else None
+            groups.setdefault((lr.shape, hr.shape, interp), []).append((idx, lf, lr, hr))
+        sizes = {k[1] for k in groups}
+        if len(sizes) != 1:
+            raise ValueError(f"collect: the global accumulators need HR images of one size, found {sorted(sizes)}")
+        rows = [None] * len(pairs)
+        acc = None
+        for (_, hr_shape, interp), items in groups.items():
+            for s in range(0, len(items), MetricsAggregator.BATCH):
+                part = items[s:s + MetricsAggregator.BATCH]
+                lr = ctx.to_device(np.stack([p[2] for p in part]))
+                hr = ctx.to_device(np.stack([p[3] for p in part]))
+                if interp is not None:
+                    lr = ctx.resize(lr, hr_shape[0], hr_shape[1], interp)
+                r, g = MetricsAggregator.collect_arrays(lr, hr, glcm_multi_angle, glcm_levels, [p[1] for p in part], device_acc=acc, finish=False)
+                acc = g["_device"]
+                for p, row in zip(part, r):
+                    rows[p[0]] = row
+        g = MetricsAggregator.new_global_data()
+        g["count"] = len(rows)
+        g["noise_means_lr"] = [r.color_noise_lr for r in rows]
+        g["_device"] = acc
+        MetricsAggregator._download(g)
+        return rows, g
+
+
+class StatsReporter:
+    """The rows as columns, and their descriptive statistics (pandas is not a dependency: dicts of NumPy arrays instead of DataFrames)."""
+
+    @staticmethod
+    def dataframe(rows):
+        """{column: NumPy array, one entry per pair}, in the reference DataFrame's column order."""
+        dicts = [r.as_dict() for r in rows]
+        keys = list(dicts[0]) if dicts else list(ImagePairMetrics.FIELDS)
+        out = {}
+        for k in keys:
+            vals = [d[k] for d in dicts]
+            numeric = all(v is None or isinstance(v, (int, float, np.integer, np.floating)) for v in vals)
+            out[k] = np.array([math.nan if v is None else float(v) for v in vals], np.float64) if numeric else np.array(vals, dtype=object)
+        return out
+
+    @staticmethod
+    def summary(df):
+        """{column: {mean, std, 25%, 50%, 75%}} of the numeric columns as DataFrame.describe() computes them: NaN skipped, std with
+        ddof 1, quartiles by linear interpolation."""
+        out = {}
+        for k, col in df.items():
+            a = np.asarray(col)
+            if a.dtype.kind not in "fiu":
+                continue
+            a = np.sort(a.astype(np.float64)[~np.isnan(a.astype(np.float64))])
+            n = a.size
+            if n == 0:
+                out[k] = {s: math.nan for s in ("mean", "std", "25%", "50%", "75%")}
+                continue
+            mean = float(a.sum() / n)
+
+            def quantile(q):
+                pos = q * (n - 1)
+                lo = int(math.floor(pos))
+                hi = min(lo + 1, n - 1)
+                return float(a[lo] + (a[hi] - a[lo]) * (pos - lo))
+
+            std = math.sqrt(float(((a - mean) ** 2).sum()) / (n - 1)) if n > 1 else math.nan
+            out[k] = {"mean": mean, "std": std, "25%": quantile(0.25), "50%": quantile(0.5), "75%": quantile(0.75)}
+        return out

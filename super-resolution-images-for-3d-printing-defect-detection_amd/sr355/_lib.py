@@ -105,6 +105,8 @@ SIGNATURES = {
     "sr_edge_guided": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sr_freq_extrapolate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "sr_classic_scores": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_eda_pair_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_eda_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_affine_warp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_dense_head_workspace_bytes": (_i64, [_i, _i]),
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
@@ -112,6 +114,17 @@ SIGNATURES = {
 
 # the columns of sr_classic_scores (SR_SCORE_* in include/sr355.h)
 SCORE_NAMES = ("psnr", "ssim", "mae", "rmse", "grad_mse", "epi", "hf_ratio", "kl_luma", "kl_color")
+
+# the columns of sr_eda_pair_stats (SR_EDA_* in include/sr355.h): the 32 numeric columns of the EDA's row, then the two Sobel means behind
+# edge_diff and feature_distribution's channel means and stds
+EDA_STAT_NAMES = (("psnr", "ssim", "glcm_contrast", "glcm_homogeneity", "glcm_correlation")
+                  + tuple(f"{k}_{s}" for k in ("rms_noise", "lap_var", "blocking", "color_noise", "ringing", "saturation_mean", "brightness_mean")
+                          for s in ("lr", "hr"))
+                  + ("edge_diff",)
+                  + tuple(f"ch{c}_{k}_{s}" for k in ("skew", "kurt") for c in range(3) for s in ("lr", "hr"))
+                  + ("sobel_mean_lr", "sobel_mean_hr")
+                  + tuple(f"ch{c}_{k}_{s}" for k in ("mean", "std") for c in range(3) for s in ("lr", "hr")))
+EDA_ROW_COLUMNS = EDA_STAT_NAMES[:32]
 
 _lib = None
 

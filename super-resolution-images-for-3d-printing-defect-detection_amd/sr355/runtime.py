@@ -365,6 +365,53 @@ class Context:
                                               ptr("hist_luma"), ptr("hist_color"), self.stream()))
         return (out, inter) if raw else out
 
+    EDA_STAT_NAMES = L.EDA_STAT_NAMES
+
+    def _eda_pair(self, lr, hr, who):
+        _check_tensor(self, lr, f"{who} lr", (torch.uint8,))
+        _check_tensor(self, hr, f"{who} hr", (torch.uint8,))
+        if lr.shape != hr.shape or lr.dim() != 4 or lr.shape[3] != 3:
+            raise ValueError(f"{who}: expected two uint8 BGR batches [B,H,W,3] of one shape, got {tuple(lr.shape)} and {tuple(hr.shape)}")
+        return lr.shape[:3]
+
+    def eda_pair_stats(self, lr, hr, glcm_levels=64, angles=(0,), raw=False):
+        """The EDA's per-pair statistics (sr_eda_pair_stats; columns EDA_STAT_NAMES) -> float64 [B, 46] on the device.  lr, hr: uint8 BGR
+        device tensors [B,H,W,3] of one shape (lr aligned to hr).  glcm_levels 64 or 256; angles: indices into (0, 45, 90, 135 degrees).
+        raw=True -> (stats, dict of the intermediates: 'gray', 'sat', 'val', 'blur3', 'edges' uint8 [B,2,H,W] (lr, hr), 'blur5' uint8
+        [B,2,H,W,3], 'glcm' int32 [B,nangles,L,L] lr's counts before symmetrisation, 'dct' float64 [B,2,H,W])."""
+        B, H, W = self._eda_pair(lr, hr, "eda_pair_stats")
+        angles = sorted(set(int(a) for a in angles))
+        if not angles or angles[0] < 0 or angles[-1] > 3:
+            raise ValueError(f"eda_pair_stats: angles are indices 0..3 into (0, 45, 90, 135 degrees), got {angles}")
+        if glcm_levels not in (64, 256):
+            raise ValueError(f"eda_pair_stats: glcm_levels must be 64 or 256, got {glcm_levels}")
+        out = self.empty((B, len(self.EDA_STAT_NAMES)), torch.float64)
+        inter = {}
+        if raw:
+            inter = {k: self.empty((B, 2, H, W), torch.uint8) for k in ("gray", "sat", "val", "blur3", "edges")}
+            inter["blur5"] = self.empty((B, 2, H, W, 3), torch.uint8)
+            inter["glcm"] = self.empty((B, len(angles), glcm_levels, glcm_levels), torch.int32)
+            inter["dct"] = self.empty((B, 2, H, W), torch.float64)
+        ptr = (lambda k: inter[k].data_ptr() if k in inter else None)
+        self.check(self.lib.sr_eda_pair_stats(self.h, lr.data_ptr(), hr.data_ptr(), B, H, W, int(glcm_levels), sum(1 << a for a in angles), out.data_ptr(),
+                                              ptr("gray"), ptr("sat"), ptr("val"), ptr("blur3"), ptr("blur5"), ptr("edges"), ptr("glcm"), ptr("dct"),
+                                              self.stream()))
+        return (out, inter) if raw else out
+
+    def eda_accumulate(self, lr, hr, acc=None):
+        """Adds the pairs' global EDA data (sr_eda_accumulate) into `acc`, a dict of device buffers made on the first call and returned:
+        'lr_fft_sum', 'hr_fft_sum', 'grad_hr_sum' float64 [H,W], 'glcm_sum' float64 [256,256], 'sat_counts' int64 [2,50] (lr, hr)."""
+        B, H, W = self._eda_pair(lr, hr, "eda_accumulate")
+        if acc is None:
+            acc = {k: torch.zeros((H, W), dtype=torch.float64, device=self.torch_device) for k in ("lr_fft_sum", "hr_fft_sum", "grad_hr_sum")}
+            acc["glcm_sum"] = torch.zeros((256, 256), dtype=torch.float64, device=self.torch_device)
+            acc["sat_counts"] = torch.zeros((2, 50), dtype=torch.int64, device=self.torch_device)
+        if tuple(acc["lr_fft_sum"].shape) != (H, W):
+            raise ValueError(f"eda_accumulate: the accumulators hold {tuple(acc['lr_fft_sum'].shape)} images, the batch is {H} x {W}")
+        self.check(self.lib.sr_eda_accumulate(self.h, lr.data_ptr(), hr.data_ptr(), B, H, W, acc["lr_fft_sum"].data_ptr(), acc["hr_fft_sum"].data_ptr(),
+                                              acc["grad_hr_sum"].data_ptr(), acc["glcm_sum"].data_ptr(), acc["sat_counts"].data_ptr(), self.stream()))
+        return acc
+
     @staticmethod
     def _view(t, coff, c):
         """(tensor [B,H,W,Cbuf] fp32 contiguous, first channel, channels) -> sr_view."""
