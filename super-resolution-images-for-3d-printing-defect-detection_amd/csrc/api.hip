@@ -125,7 +125,7 @@ struct Op {
 };
 struct BufSpec { int C = 0; int mul = 1; int shift = 0; bool vec = false; int Cbuf = 0; int blk = 0; int cshift = 0; int cells = 0; int cat = 0; };   // vec: fp32 [B,C]; blk: row-blocked (conv_common.h); shift: floor halvings (pooling), cshift: ceil halvings (stride-2 SAME convs); cells: small images may be packed in a CellGrid (common.h)
 struct ConvPart { std::string name; int cout; float scale = 1.f; };   // scale: applied to kernel and bias when the conv is packed
-struct ConvSpec { std::vector<ConvPart> parts; int KS = 3, Cin = 0, Cout = 0; ConvWeights w; int rows_head = 0; };   // rows_head: conv_pack_weights
+struct ConvSpec { std::vector<ConvPart> parts; int KS = 3, Cin = 0, Cout = 0; ConvWeights w; int rows_head = 0; };   // rows_head: conv_plan
 // two consecutive convs of a dense block that run as ONE kernel when the shape allows (dense_fused.hip): ops[first], ops[first + 1]
 struct ChainSpec { int conv_a = -1, conv_b = -1; int tail = 0; ChainWeights w; };
 // a 64-cout 3x3 conv followed by the 3x3 conv to the image's <= 3 channels: one kernel + a finishing pass when the shape allows (conv_rows.hip)
@@ -1143,6 +1143,20 @@ int sr_forward(sr_model* m, const void* x, int io_dtype, int B, int H, int W, in
 }
 
 // ------------------------------------------------------------------------------------------------- single ops
+// The epilogue of a single conv op; a skip whose view has no pointer is unused.  allow_splitk: the single ops all choose their kernel alike (sr_conv2d
+// and sr_conv2d_dev agree bit for bit); model forwards do not set it.
+static ConvEpilogue single_op_epilogue(int act, float alpha, int clip01, int d2s_r, TensorView skip1, float beta1, TensorView skip2, float beta2) {
+    ConvEpilogue ep;
+    ep.act = act; ep.alpha = alpha; ep.clip01 = clip01; ep.d2s_r = d2s_r < 1 ? 1 : d2s_r;
+    ep.allow_splitk = 1;
+    if (skip1.p) { ep.skip1 = skip1; ep.beta1 = beta1; }
+    if (skip2.p) { ep.skip2 = skip2; ep.beta2 = beta2; }
+    return ep;
+}
+
+// channels per pixel of the padded input copy a single op hands its conv
+static int padded_cin(const ConvWeights& cw) { return cw.thin ? cw.CinP : round_up(cw.CinP, 32); }
+
 int sr_conv2d(sr_ctx* ctx, const void* x, int dtype, int B, int H, int W, int Cin, const float* w_hwio, const float* bias, int KH, int KW,
               int Cout, int act, float alpha, const void* skip1, float beta1, const void* skip2, float beta2, int clip01, int d2s_r,
               void* y, void* stream) {
@@ -1157,19 +1171,15 @@ int sr_conv2d(sr_ctx* ctx, const void* x, int dtype, int B, int H, int W, int Ci
     int rc = conv_pack_weights(ctx, w_hwio, bias, KH, Cin, Cout, dtype, &cw);
     if (rc) return rc;
     const int esz = dtype_size(dtype);
-    const int Cp = cw.thin ? cw.CinP : round_up(cw.CinP, 32);
+    const int Cp = padded_cin(cw);
     void* xp = ctx->dalloc((size_t)B * H * W * Cp * esz + 4096);
     if (!xp) { conv_free_weights(ctx, &cw); return SR_ERR_OOM; }
     rc = convert_pad_launch(ctx, x, dtype, (int64_t)B * H * W, Cin, xp, dtype, Cp, 1.f, 0.f, st);
     if (!rc) {
-        ConvEpilogue ep;
-        ep.act = act; ep.alpha = alpha; ep.clip01 = clip01; ep.d2s_r = d2s_r < 1 ? 1 : d2s_r;
-        ep.allow_splitk = 1;                                      // a single op, like sr_conv2d_dev (same kernel choice: the two agree bit for bit); model forwards do not set it
         // a skip that IS the input (a dense-block tail y = alpha * conv(x) + beta * x) is read from the padded copy the conv reads, so that the kernel
         // sees the alias the way a model forward presents it (conv_rows then takes that skip from its LDS tile)
         auto skip_view = [&](const void* s) { return (s == x && Cout == Cin) ? TensorView{xp, Cp, 0} : TensorView{s, Cout, 0}; };
-        if (skip1) { ep.skip1 = skip_view(skip1); ep.beta1 = beta1; }
-        if (skip2) { ep.skip2 = skip_view(skip2); ep.beta2 = beta2; }
+        const ConvEpilogue ep = single_op_epilogue(act, alpha, clip01, d2s_r, skip_view(skip1), beta1, skip_view(skip2), beta2);
         const int r = ep.d2s_r;
         rc = conv_launch(ctx, cw, TensorView{xp, Cp, 0}, B, H, W, y, Cout / (r * r), 0, ep, st);
     }
@@ -1191,7 +1201,7 @@ int sr_conv2d_dev(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, cons
     ConvWeights cw;
     int rc = conv_pack_weights_dev(ctx, d_w, d_bias, K, Cin, Cout, rot, &cw, st);
     if (rc) return rc;
-    const int Cp = cw.thin ? cw.CinP : round_up(cw.CinP, 32);
+    const int Cp = padded_cin(cw);
     const void* xp = x;
     if (Cp != Cin || ((uintptr_t)x % 16) != 0) {          // channel padding needed: a padded copy in the arena (else the conv reads x in place)
         void* xa = ctx->arena(ctx->dev_x, (size_t)B * H * W * Cp * 4 + 4096, st);
@@ -1200,11 +1210,7 @@ int sr_conv2d_dev(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, cons
         if (rc) return rc;
         xp = xa;
     }
-    ConvEpilogue ep;
-    ep.act = act; ep.alpha = alpha; ep.clip01 = clip01; ep.d2s_r = d2s_r < 1 ? 1 : d2s_r;
-    ep.allow_splitk = 1;
-    if (skip1) { ep.skip1 = {skip1, Cout, 0}; ep.beta1 = beta1; }
-    if (skip2) { ep.skip2 = {skip2, Cout, 0}; ep.beta2 = beta2; }
+    const ConvEpilogue ep = single_op_epilogue(act, alpha, clip01, d2s_r, TensorView{skip1, Cout, 0}, beta1, TensorView{skip2, Cout, 0}, beta2);
     const int r = ep.d2s_r;
     return conv_launch(ctx, cw, TensorView{xp, Cp, 0}, B, H, W, y, Cout / (r * r), 0, ep, st);
 }
@@ -1226,10 +1232,7 @@ int sr_conv2d_dev_views(sr_ctx* ctx, const sr_view* x, int B, int H, int W, int 
     int rc = conv_pack_weights_dev(ctx, d_w, d_bias, K, Cin, Cout, rot, &cw, st);
     if (rc) return rc;
     if (cw.thin || cw.CinP != Cin) return ctx->fail(SR_ERR_INVALID, "conv views: the input channel count must be a whole number of the kernel's channel chunks (16 fp32 channels)");
-    ConvEpilogue ep;
-    ep.act = act; ep.alpha = alpha;
-    ep.allow_splitk = 1;
-    if (skip1 && skip1->p) { ep.skip1 = {skip1->p, skip1->cs, skip1->coff}; ep.beta1 = beta1; }
+    const ConvEpilogue ep = single_op_epilogue(act, alpha, 0, 1, skip1 ? TensorView{skip1->p, skip1->cs, skip1->coff} : TensorView{}, beta1, TensorView{}, 0.f);
     return conv_launch(ctx, cw, TensorView{x->p, x->cs, x->coff}, B, H, W, TensorView{y->p, y->cs, y->coff}, ep, st);
 }
 

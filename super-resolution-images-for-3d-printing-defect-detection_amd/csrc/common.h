@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -112,11 +113,28 @@ struct DeviceGuard {
 
 static inline int dtype_size(int dt) { return dt == SR_DTYPE_F32 ? 4 : (dt == SR_DTYPE_BF16 ? 2 : 1); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+// fp32 -> bf16 bits on the host, as the device's conversion rounds: to nearest even, NaN stays NaN
+static inline uint16_t f32_to_bf16_host(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+// Every packer's device copies: `packed` and the bias zero-padded from n to npad floats (null bias: zeros), both allocated here and both freed
+// again when anything fails; weights_free releases such a pair and nulls the two pointers.
+int weights_upload(sr_ctx* ctx, const void* packed, size_t bytes, const float* bias, int n, int npad, void** d_w, float** d_bias);
+template <typename P> static inline void weights_free(sr_ctx* ctx, P*& w, float*& bias) {
+    if (w) ctx->dfree(w);
+    if (bias) ctx->dfree(bias);
+    w = nullptr; bias = nullptr;
+}
 
 // ---------------------------------------------------------------------------------------------
 // conv: packed weights + launch
 // ---------------------------------------------------------------------------------------------
-struct ConvWeights {          // device-resident, MFMA-fragment-ordered (see conv.hip header)
+struct ConvWeights {          // device-resident, MFMA-fragment-ordered (conv_pack.h: conv_plan fills the metadata)
     void* w = nullptr;        // packed kernel
     float* bias = nullptr;    // [CoutP] fp32, zero padded
     int dtype = SR_DTYPE_BF16;
@@ -192,17 +210,18 @@ struct ConvEpilogue {
                               // so only the training entry points set it: a model's forward must give the same bits whatever the batch it is called with (Keras predict's chunking)
 };
 
-// host: pack HWIO fp32 weights (+bias) for the device.  Returns SR_OK or error (ctx->err set).
-// the same packing on the device (fp32 only): `d_hwio` is a device HWIO tensor, [K,K,Cin,Cout], or with rot = 1 the kernel whose
+// Packing of HWIO fp32 weights (+bias) into the layout conv_pack.h defines.  Returns SR_OK or error (ctx->err set).
+// on the device (fp32 only): `d_hwio` is a device HWIO tensor, [K,K,Cin,Cout], or with rot = 1 the kernel whose
 // 180-degree-rotated, channel-swapped form is wanted ([K,K,Cout,Cin]: the input-gradient conv of that layer); weights and bias land in
 // the context's arenas (valid until the next sr_conv2d_dev on the stream)
 int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st);
 int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st);
+// on the host (f32 and bf16), into tracked allocations that conv_free_weights releases.
 // rows_head = 1 (bf16 3x3 only): a conv whose Cin fits one 16-byte slice (an RGB head) is packed for the row-sliding kernel on one
 // zero-padded 32-channel chunk instead of the thin kernel -- the caller then provides a 32-channel input view
 int conv_pack_weights(sr_ctx* ctx, const float* hwio, const float* bias, int KS, int Cin, int Cout,
                       int dtype, ConvWeights* out, int rows_head = 0);
-void conv_free_weights(sr_ctx* ctx, ConvWeights* w);
+static inline void conv_free_weights(sr_ctx* ctx, ConvWeights* w) { weights_free(ctx, w->w, w->bias); }
 // x view must expose >= w.CinP channels starting at coff (extra ones multiplied by zero weights).
 int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, int W,
                 void* y, int64_t y_cs, int y_coff, const ConvEpilogue& ep, hipStream_t st);
@@ -211,12 +230,12 @@ int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, i
 // fused 1x1 projection: pack the HWIO kernel [1,1,64,16 * nblk] (+ bias) of the 1x1 conv that follows a 64-channel conv_rows conv
 int proj_pack_weights(sr_ctx* ctx, const float* w_hwio, const float* bias, int cout, ProjWeights* out);
 int pw2_pack_weights(sr_ctx* ctx, const float* w_hwio, const float* bias, int cin, int cout, int act, Pw2Weights* out);
-void pw2_free_weights(sr_ctx* ctx, Pw2Weights* w);
-void proj_free_weights(sr_ctx* ctx, ProjWeights* w);
+static inline void pw2_free_weights(sr_ctx* ctx, Pw2Weights* w) { weights_free(ctx, w->a, w->bias); *w = Pw2Weights{}; }
+static inline void proj_free_weights(sr_ctx* ctx, ProjWeights* w) { weights_free(ctx, w->a, w->bias); }
 // fused RGB tail: pack the second conv's HWIO kernel [3,3,64,c2] (+ bias), size of the partial-sum buffer, and the pass that adds the
 // partial sums of the tiles covering an output pixel, applies bias / activation / alpha / clip and stores NHWC (bf16, or fp32 with out_f32)
 int rgbtail_pack_weights(sr_ctx* ctx, const float* w2_hwio, const float* bias2, int c2, RgbTailWeights* out);
-void rgbtail_free_weights(sr_ctx* ctx, RgbTailWeights* w);
+static inline void rgbtail_free_weights(sr_ctx* ctx, RgbTailWeights* w) { weights_free(ctx, w->a, w->bias); }
 int64_t rgbtail_partial_bytes(int B, int H, int W);
 int rgbtail_finish_launch(sr_ctx* ctx, const RgbTailWeights& w, const float* part, int B, int H, int W, int act, float alpha, int clip01, void* y,
                           int64_t y_cs, int y_coff, int out_f32, hipStream_t st);
@@ -230,7 +249,7 @@ struct ChainWeights {
     size_t bytes = 0;
 };
 int chain_pack_weights(sr_ctx* ctx, const float* wa_hwio, const float* ba, const float* wb_hwio, const float* bb, int ext, int nb0, int nb1, ChainWeights* out);
-void chain_free_weights(sr_ctx* ctx, ChainWeights* w);
+static inline void chain_free_weights(sr_ctx* ctx, ChainWeights* w) { weights_free(ctx, w->w, w->bias); }
 bool chain_supported(const ChainWeights& w, const TensorView& in, int W);
 // conv1 of a dense block (64 -> 32, writes chunk 2 of the row-blocked buffer it reads) as a streaming line-buffer kernel (dense_fused.hip)
 bool conv1_stream_supported(const ConvWeights& w, const TensorView& in, int W);

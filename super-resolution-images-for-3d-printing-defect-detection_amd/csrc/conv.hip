@@ -15,9 +15,9 @@
 // LDS.  The input halo tile (TH+KS-1) x (16+KS-1) pixels of one Cin chunk is staged pixel-major
 // with CS = chunk_bytes + 16 bytes per pixel (odd number of 16-byte slots -> the 16 lanes a
 // ds_read_b128 services together land on 16 distinct slots).  A tap (ky,kx) is then a constant
-// byte offset from a lane's base address.  Weights are pre-packed on the host in exactly the
-// order the lanes read them (1 KiB per (tap, k-group, cout-block), lane-linear), so the weight
-// stage is a straight copy and its ds_read_b128 is conflict free.
+// byte offset from a lane's base address.  Weights are pre-packed in exactly the order the
+// lanes read them (1 KiB per (tap, k-group, cout-block), lane-linear: conv_pack.h), so the
+// weight stage is a straight copy and its ds_read_b128 is conflict free.
 //
 // k-group = the 16 bytes lane-half 0 and the 16 bytes lane-half 1 feed to one MFMA step:
 //   wide (Cin*sizeof >= 64 B): both halves sit on the same tap, consecutive channel slices;
@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "conv_pack.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -524,7 +525,7 @@ int dispatch(sr_ctx* ctx, const ConvRoute& rt, const ConvParams& p, int nct, hip
     }
     if (p.pw2w) return ctx->fail(SR_ERR_INVALID, "conv: the fused 1x1 follows the fp32 9x9 RGB head only");
     if (rt.fam == CF_THIN) {
-        // conv_pack_weights gives every thin conv one 32-cout block per workgroup (NT = 1); only the fused head above owns more
+        // conv_plan gives every thin conv one 32-cout block per workgroup (NT = 1); only the fused head above owns more
         if (rt.NT != 1) return ctx->fail(SR_ERR_INVALID, "conv: a thin conv takes one 32-cout block per workgroup");
         switch (rt.KS) {
             case 3: return launch_thin<T, 3, 1>(ctx, p, nct, st);
@@ -538,14 +539,6 @@ int dispatch(sr_ctx* ctx, const ConvRoute& rt, const ConvParams& p, int nct, hip
         if (rt.KS == 5 && rt.KGPT == 2 && rt.NT == 1) return launch_wide<T, 5, 2, 1>(ctx, p, nct, rt.sub, st);
     }
     return ctx->fail(SR_ERR_INVALID, "conv: unsupported kernel size " + std::to_string(rt.KS));
-}
-
-inline uint16_t f32_to_bf16_host(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);                                          // round to nearest even
-    return (uint16_t)(u >> 16);
 }
 
 }  // namespace
@@ -734,149 +727,74 @@ static std::string conv_route_name(const ConvRoute& rt) {
     return s;
 }
 
+int weights_upload(sr_ctx* ctx, const void* packed, size_t bytes, const float* bias, int n, int npad, void** d_w, float** d_bias) {
+    void* w = ctx->dalloc(bytes);
+    float* b = w ? static_cast<float*>(ctx->dalloc(sizeof(float) * npad)) : nullptr;
+    auto copy = [&]() -> int {
+        std::vector<float> hb(npad, 0.f);
+        if (bias) std::copy(bias, bias + n, hb.begin());
+        SR_HIP(ctx, hipMemcpy(w, packed, bytes, hipMemcpyHostToDevice));
+        SR_HIP(ctx, hipMemcpy(b, hb.data(), sizeof(float) * npad, hipMemcpyHostToDevice));
+        return SR_OK;
+    };
+    const int rc = (w && b) ? copy() : SR_ERR_OOM;
+    if (rc) { weights_free(ctx, w, b); return rc; }
+    *d_w = w; *d_bias = b;
+    return SR_OK;
+}
+
+// host packing into a zeroed image, in packed order: fetch the source value, round once, store.  One decode per fragment and one per lane, the
+// lane's elements walked from there: a full decode per element costs sr_model_finalize its divisions.
+template <typename T, typename Round>
+static void pack_host(const float* __restrict__ hwio, const PackPlan q, int64_t n, T* __restrict__ dst, Round round) {
+    if (q.layout == PL_FEW) {
+        for (int64_t idx = 0; idx < n; ++idx) dst[idx] = round(pack_source(hwio, conv_pack_decode(idx, q), q));
+        return;
+    }
+    constexpr int E = 16 / sizeof(T);                        // = 1 << q.esh, at compile time: the whole-lane copy below unrolls
+    const int stride = pack_source_stride(q);
+    for (int64_t f = 0; f < n >> (q.esh + 6); ++f) {
+        const PackCoord o = pack_fragment_origin(f, q);
+        for (int l = 0; l < 64; ++l, dst += E) {
+            // a lane's E elements are E consecutive cins from its element 0 (pack_fragment_lane): one bounds test, then a strided copy of the cins
+            // the kernel has; `dst` is zero beyond them
+            const PackCoord c = pack_fragment_lane(o, l, q);
+            if (!(c.tap < q.ntap && c.ci < q.Cin && c.co < q.Cout)) continue;
+            const float* s = hwio + pack_source_index(c, q);
+            const int nj = std::min(E, q.Cin - c.ci);
+            if (nj == E) for (int j = 0; j < E; ++j) dst[j] = round(s[(int64_t)j * stride]);
+            else for (int j = 0; j < nj; ++j) dst[j] = round(s[(int64_t)j * stride]);
+        }
+    }
+}
+
 int conv_pack_weights(sr_ctx* ctx, const float* hwio, const float* bias, int KS, int Cin, int Cout, int dtype,
                       ConvWeights* out, int rows_head) {
-    if (dtype != SR_DTYPE_BF16 && dtype != SR_DTYPE_F32) return ctx->fail(SR_ERR_INVALID, "conv: dtype must be f32 or bf16");
-    if (KS != 1 && KS != 3 && KS != 5 && KS != 9) return ctx->fail(SR_ERR_INVALID, "conv: kernel size must be 1,3,5 or 9");
-    const int esz = dtype_size(dtype), E = 16 / esz;
     ConvWeights w;
-    w.dtype = dtype; w.KS = KS; w.Cin = Cin; w.Cout = Cout;
-    w.CoutP = round_up(Cout, 32);
-    const int nb = w.CoutP / 32;
-    w.NT = (nb % 2 == 0) ? 2 : (nb % 3 == 0 ? 3 : 1);
-    if (KS == 5 && !(Cin <= E)) w.NT = 1;   // 25 taps of weights: keep the LDS stage small
-    const bool as_rows = rows_head && dtype == SR_DTYPE_BF16 && KS == 3;
-    // thin (RGB) inputs pair two taps in a k-group; a 1x1 has no second tap and takes the wide / 1x1 kernels on zero-padded channels instead
-    w.thin = Cin <= E && !as_rows && KS != 1;
-    if (w.thin) w.NT = 1;                    // thin: one 32-cout block per workgroup (112 + 48 registers, 3 waves/SIMD);
-                                             // re-reading the 3-channel input per cout block is cheap, 1 wave/SIMD at NT=3 was not (9x9: 1.8x)
-    const int nct = nb / w.NT, ntap = KS * KS;
-    // fp32, <= 4 couts, not thin: the VALU kernel (conv_fewcout_f32_kernel), weights [tap][CinP][4]
-    w.few = (dtype == SR_DTYPE_F32 && Cout <= 4 && !w.thin && (KS == 3 || KS == 5)) ? 1 : 0;
-    w.rows = (dtype == SR_DTYPE_BF16 && KS == 3 && !w.thin) ? 1 : 0;
-    // bf16 1x1 with the whole weight matrix in 16 register fragments: the streaming kernel of conv_pw.hip (same fragment layout)
-    {   // (register budget of the instantiations in conv_pw.hip: 4 waves/SIMD without spills)
-        const int nb16 = round_up(Cout, 16) / 16, nch = round_up(Cin, 32) / 32;
-        w.pw = (dtype == SR_DTYPE_BF16 && KS == 1 && !w.thin && nch <= 4 &&
-                (nb16 <= 2 || (nb16 == 3 && nch <= 3) || (nb16 == 4 && nch == 1))) ? 1 : 0;
-    }
-    if (!w.thin && KS == 9) return ctx->fail(SR_ERR_INVALID, "conv: 9x9 supported for <= one 16-byte channel slice only");
-    std::vector<char> host;
-    auto put = [&](size_t idx, float v) {
-        if (dtype == SR_DTYPE_F32) reinterpret_cast<float*>(host.data())[idx] = v;
-        else reinterpret_cast<uint16_t*>(host.data())[idx] = f32_to_bf16_host(v);
-    };
-    auto W = [&](int tap, int ci, int co) -> float {
-        if (tap >= ntap || ci >= Cin || co >= Cout) return 0.f;
-        return hwio[((size_t)tap * Cin + ci) * Cout + co];
-    };
-    if (w.few) {
-        w.CoutP = 4; w.NT = 1; w.KGPT = 0;
-        w.CinP = round_up(Cin, 4);
-        w.nchunks = w.CinP / 4;
-        host.assign((size_t)ntap * w.CinP * 4 * sizeof(float), 0);
-        for (int tap = 0; tap < ntap; ++tap)
-            for (int ci = 0; ci < w.CinP; ++ci)
-                for (int co = 0; co < 4; ++co) put(((size_t)tap * w.CinP + ci) * 4 + co, W(tap, ci, co));
-    } else if (w.rows || w.pw) {
-        w.CoutP = round_up(Cout, 16);
-        const int nb16 = w.CoutP / 16;
-        w.NT = w.pw ? nb16 : ((nb16 % 4 == 0) ? 4 : (nb16 % 2 == 0 ? 2 : 1));
-        const int nct16 = nb16 / w.NT;
-        w.KGPT = 1;
-        w.CinP = round_up(Cin, 32);
-        w.nchunks = w.CinP / 32;
-        host.assign((size_t)nct16 * w.nchunks * ntap * w.NT * 1024, 0);
-        size_t idx = 0;
-        for (int ct = 0; ct < nct16; ++ct)
-            for (int ch = 0; ch < w.nchunks; ++ch)
-                for (int tap = 0; tap < ntap; ++tap)
-                    for (int n = 0; n < w.NT; ++n)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int j = 0; j < 8; ++j, ++idx)
-                                put(idx, W(tap, ch * 32 + (lane >> 4) * 8 + j, (ct * w.NT + n) * 16 + (lane & 15)));
-    } else if (w.thin) {
-        w.CinP = E; w.KGPT = 0;
-        const int KGT = (ntap + 1) / 2;
-        w.nchunks = KGT;
-        host.assign((size_t)nct * KGT * w.NT * 1024, 0);
-        size_t idx = 0;
-        for (int ct = 0; ct < nct; ++ct)
-            for (int g = 0; g < KGT; ++g)
-                for (int n = 0; n < w.NT; ++n)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < E; ++j, ++idx)
-                            put(idx, W(2 * g + (lane >> 5), j, (ct * w.NT + n) * 32 + (lane & 31)));
-    } else {
-        w.KGPT = (KS == 1 && (round_up(Cin, 4 * E) * esz) % 128 == 0) ? 4 : 2;
-        const int chunkE = w.KGPT * 2 * E;
-        w.CinP = round_up(Cin, chunkE);
-        w.nchunks = w.CinP / chunkE;
-        host.assign((size_t)nct * w.nchunks * ntap * w.KGPT * w.NT * 1024, 0);
-        size_t idx = 0;
-        for (int ct = 0; ct < nct; ++ct)
-            for (int ch = 0; ch < w.nchunks; ++ch)
-                for (int tap = 0; tap < ntap; ++tap)
-                    for (int kg = 0; kg < w.KGPT; ++kg)
-                        for (int n = 0; n < w.NT; ++n)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int j = 0; j < E; ++j, ++idx)
-                                    put(idx, W(tap, ch * chunkE + kg * 2 * E + (lane >> 5) * E + j, (ct * w.NT + n) * 32 + (lane & 31)));
-    }
-    w.bytes = host.size();
-    w.w = ctx->dalloc(w.bytes);
-    if (!w.w) return SR_ERR_OOM;
-    w.bias = static_cast<float*>(ctx->dalloc(sizeof(float) * w.CoutP));
-    if (!w.bias) { ctx->dfree(w.w); return SR_ERR_OOM; }
-    std::vector<float> hb(w.CoutP, 0.f);
-    if (bias) for (int i = 0; i < Cout; ++i) hb[i] = bias[i];
-    SR_HIP(ctx, hipMemcpy(w.w, host.data(), w.bytes, hipMemcpyHostToDevice));
-    SR_HIP(ctx, hipMemcpy(w.bias, hb.data(), sizeof(float) * w.CoutP, hipMemcpyHostToDevice));
+    PackPlan q;
+    int64_t n;
+    if (int rc = conv_plan(ctx, dtype, KS, Cin, Cout, rows_head, 0, &w, &q, &n)) return rc;
+    std::vector<char> host(w.bytes);
+    if (dtype == SR_DTYPE_F32) pack_host(hwio, q, n, reinterpret_cast<float*>(host.data()), [](float v) { return v; });
+    else pack_host(hwio, q, n, reinterpret_cast<uint16_t*>(host.data()), [](float v) { return f32_to_bf16_host(v); });
+    if (int rc = weights_upload(ctx, host.data(), w.bytes, bias, Cout, w.CoutP, &w.w, &w.bias)) return rc;
     *out = w;
     return SR_OK;
 }
 
-// ---- device-side packing (fp32): one thread per packed element decodes its (tap, cin, cout) exactly as the host loops above
-struct PackPlan { int layout, ntap, Cin, Cout, CinP, NT, nchunks, KGPT, rot, CoutP; };
-
-static __device__ __forceinline__ float pack_element_f32(const float* __restrict__ src, int64_t idx, const PackPlan& q) {
-    int tap, ci, co;
-    if (q.layout == 0) {                          // few: [tap][CinP][4]
-        co = (int)(idx & 3);
-        const int64_t t = idx >> 2;
-        ci = (int)(t % q.CinP); tap = (int)(t / q.CinP);
-    } else if (q.layout == 1) {                   // thin: [ct][g][n][lane][j], E = 4
-        const int j = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
-        int64_t t = idx >> 8;
-        const int nn = (int)(t % q.NT); t /= q.NT;
-        const int g = (int)(t % q.nchunks), ct = (int)(t / q.nchunks);          // nchunks = KGT
-        tap = 2 * g + (lane >> 5); ci = j; co = (ct * q.NT + nn) * 32 + (lane & 31);
-    } else {                                      // wide: [ct][ch][tap][kg][n][lane][j], E = 4
-        const int j = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
-        int64_t t = idx >> 8;
-        const int nn = (int)(t % q.NT); t /= q.NT;
-        const int kg = (int)(t % q.KGPT); t /= q.KGPT;
-        tap = (int)(t % q.ntap); t /= q.ntap;
-        const int ch = (int)(t % q.nchunks), ct = (int)(t / q.nchunks);
-        ci = ch * (q.KGPT * 8) + kg * 8 + (lane >> 5) * 4 + j; co = (ct * q.NT + nn) * 32 + (lane & 31);
-    }
-    float v = 0.f;
-    if (tap < q.ntap && ci < q.Cin && co < q.Cout)
-        v = q.rot ? src[((int64_t)(q.ntap - 1 - tap) * q.Cout + co) * q.Cin + ci] : src[((int64_t)tap * q.Cin + ci) * q.Cout + co];
-    return v;
-}
-
+// ---- device-side packing (fp32): one thread per packed element
 __global__ void pack_weights_f32_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t n, PackPlan q, const float* __restrict__ bias, float* __restrict__ bias_out) {
     // the zero-padded bias rides along (block 0): one launch per conv use less than a separate pad kernel
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < q.CoutP; i += blockDim.x) bias_out[i] = (bias && i < q.Cout) ? bias[i] : 0.f;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) dst[idx] = pack_element_f32(src, idx, q);
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) dst[idx] = pack_source(src, conv_pack_decode(idx, q), q);
 }
 
 // Many convs' weights by ONE launch (sr_conv_prepack: a training step's ~800 per-use packs were 3.9 ms of 4.9-us launches): job j owns blocks [blk0, next job's blk0),
 // PACK_JOB_ELEMS packed elements per block; a block finds its job by bisection of the table.
 constexpr int PACK_JOB_ELEMS = 2048;
-struct PackJob { const float* src; const float* bias; float* dst; float* bias_out; int64_t n; PackPlan q; int blk0; int pad_; };
+struct PackJob { const float* src; const float* bias; float* dst; float* bias_out; int64_t n; PackPlan q; int blk0; };
+static_assert(sizeof(PackJob) == 4 * sizeof(void*) + sizeof(int64_t) + sizeof(PackPlan) + sizeof(int), "conv_prepack_dev compares job tables bytewise: no padding");
 
 __global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJob* __restrict__ jobs, int njobs) {
     int lo = 0, hi = njobs - 1;
@@ -898,58 +816,14 @@ __global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJo
     const int64_t base = (int64_t)lb * PACK_JOB_ELEMS;
 #pragma unroll 4
     for (int i = threadIdx.x; i < PACK_JOB_ELEMS; i += 256)
-        if (base + i < n) dst[base + i] = pack_element_f32(src, base + i, q);
-}
-
-// the metadata of conv_pack_weights for dtype f32 (no allocation): kernel family, padded sizes, packed element count
-static int conv_plan_f32(sr_ctx* ctx, int KS, int Cin, int Cout, int rot, ConvWeights* out, PackPlan* plan, int64_t* count) {
-    if (KS != 1 && KS != 3 && KS != 5 && KS != 9) return ctx->fail(SR_ERR_INVALID, "conv: kernel size must be 1,3,5 or 9");
-    const int E = 4, ntap = KS * KS;
-    ConvWeights w;
-    w.dtype = SR_DTYPE_F32; w.KS = KS; w.Cin = Cin; w.Cout = Cout;
-    w.CoutP = round_up(Cout, 32);
-    const int nb = w.CoutP / 32;
-    w.NT = (nb % 2 == 0) ? 2 : (nb % 3 == 0 ? 3 : 1);
-    if (KS == 5 && !(Cin <= E)) w.NT = 1;
-    w.thin = Cin <= E && KS != 1;                                    // as conv_pack_weights
-    if (w.thin) w.NT = 1;
-    const int nct = nb / w.NT;
-    w.few = (Cout <= 4 && !w.thin && (KS == 3 || KS == 5)) ? 1 : 0;
-    w.rows = 0; w.pw = 0;
-    if (!w.thin && KS == 9) return ctx->fail(SR_ERR_INVALID, "conv: 9x9 supported for <= one 16-byte channel slice only");
-    int layout;
-    int64_t n;
-    if (w.few) {
-        layout = 0;
-        w.CoutP = 4; w.NT = 1; w.KGPT = 0;
-        w.CinP = round_up(Cin, 4);
-        w.nchunks = w.CinP / 4;
-        n = (int64_t)ntap * w.CinP * 4;
-    } else if (w.thin) {
-        layout = 1;
-        w.CinP = E; w.KGPT = 0;
-        w.nchunks = (ntap + 1) / 2;
-        n = (int64_t)nct * w.nchunks * w.NT * 256;
-    } else {
-        layout = 2;
-        w.KGPT = (KS == 1 && (round_up(Cin, 4 * E) * 4) % 128 == 0) ? 4 : 2;
-        const int chunkE = w.KGPT * 2 * E;
-        w.CinP = round_up(Cin, chunkE);
-        w.nchunks = w.CinP / chunkE;
-        n = (int64_t)nct * w.nchunks * ntap * w.KGPT * w.NT * 256;
-    }
-    w.bytes = (size_t)n * 4;
-    *out = w;
-    *plan = PackPlan{layout, ntap, Cin, Cout, w.CinP, w.NT, w.nchunks, w.KGPT, rot, w.CoutP};
-    *count = n;
-    return SR_OK;
+        if (base + i < n) dst[base + i] = pack_source(src, conv_pack_decode(base + i, q), q);
 }
 
 int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st) {
     ConvWeights w;
     PackPlan plan;
     int64_t n;
-    const int rc = conv_plan_f32(ctx, KS, Cin, Cout, rot, &w, &plan, &n);
+    const int rc = conv_plan(ctx, SR_DTYPE_F32, KS, Cin, Cout, 0, rot, &w, &plan, &n);
     if (rc) return rc;
     if (!ctx->pack_cache.empty()) {                                   // sr_conv_prepack: this use was packed with the step's other weights
         const auto it = ctx->pack_cache.find(sr_ctx::PackKey{d_hwio, d_bias, KS, Cin, Cout, rot});
@@ -982,9 +856,9 @@ int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t 
         if (!d.w || d.Cin <= 0 || d.Cout <= 0) return ctx->fail(SR_ERR_INVALID, "conv prepack: null kernel or bad shape");
         ConvWeights w;
         PackJob& jb = jobs[(size_t)i];
-        const int rc = conv_plan_f32(ctx, d.K, d.Cin, d.Cout, d.rot ? 1 : 0, &w, &jb.q, &jb.n);
+        const int rc = conv_plan(ctx, SR_DTYPE_F32, d.K, d.Cin, d.Cout, 0, d.rot ? 1 : 0, &w, &jb.q, &jb.n);
         if (rc) return rc;
-        jb.src = d.w; jb.bias = d.bias; jb.blk0 = (int)blocks; jb.pad_ = 0;
+        jb.src = d.w; jb.bias = d.bias; jb.blk0 = (int)blocks;
         blocks += (jb.n + PACK_JOB_ELEMS - 1) / PACK_JOB_ELEMS;
         woff[(size_t)i] = wbytes; boff[(size_t)i] = bbytes;
         wbytes += (w.bytes + 255) & ~(size_t)255;
@@ -1012,12 +886,6 @@ int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t 
     SR_HIP(ctx, hipGetLastError());
     for (int i = 0; i < n; ++i) ctx->pack_cache[keys[(size_t)i]] = {jobs[(size_t)i].dst, jobs[(size_t)i].bias_out};
     return SR_OK;
-}
-
-void conv_free_weights(sr_ctx* ctx, ConvWeights* w) {
-    if (w->w) ctx->dfree(w->w);
-    if (w->bias) ctx->dfree(w->bias);
-    w->w = nullptr; w->bias = nullptr;
 }
 
 int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, int W, void* y, int64_t y_cs, int y_coff,
@@ -1169,20 +1037,9 @@ int pw2_pack_weights(sr_ctx* ctx, const float* w, const float* bias, int cin, in
             }
     Pw2Weights pw;
     pw.cin = cin; pw.cout = cout; pw.act = act;
-    pw.a = static_cast<float*>(ctx->dalloc(host.size() * sizeof(float)));
-    if (!pw.a) return SR_ERR_OOM;
-    pw.bias = static_cast<float*>(ctx->dalloc(32 * sizeof(float)));
-    if (!pw.bias) { ctx->dfree(pw.a); return SR_ERR_OOM; }
-    float hb[32] = {0.f};
-    if (bias) for (int i = 0; i < cout; ++i) hb[i] = bias[i];
-    SR_HIP(ctx, hipMemcpy(pw.a, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-    SR_HIP(ctx, hipMemcpy(pw.bias, hb, sizeof hb, hipMemcpyHostToDevice));
+    void* a = nullptr;
+    if (int rc = weights_upload(ctx, host.data(), host.size() * sizeof(float), bias, cout, 32, &a, &pw.bias)) return rc;
+    pw.a = static_cast<float*>(a);
     *out = pw;
     return SR_OK;
-}
-
-void pw2_free_weights(sr_ctx* ctx, Pw2Weights* w) {
-    if (w->a) ctx->dfree(w->a);
-    if (w->bias) ctx->dfree(w->bias);
-    *w = Pw2Weights{};
 }

@@ -558,14 +558,6 @@ namespace {
 
 constexpr int F2_TH = 12, F2_TW = 16, F2_REGION = (F2_TH + 2) * (F2_TW + 2);    // tile of the 64-cout variant (R = 3) and its halo'd region
 
-uint16_t bf16_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 // one thread per output pixel: its own tile's partial sum, then the neighbours whose halo'd region covers it (a pixel in a tile's first /
 // last row or column is also a halo position of the tile above / below / beside, and of the diagonal one in a corner), always in this order
 __global__ void __launch_bounds__(256) rgbtail_finish_kernel(const float* __restrict__ part, int64_t npix, int H, int W, int tilesY, int tilesX,
@@ -614,18 +606,11 @@ int rgbtail_pack_weights(sr_ctx* ctx, const float* w2, const float* bias2, int c
                     if (t >= 9 * c2) continue;
                     const int tap = t / c2, co = t - tap * c2;
                     const int c = 16 * (2 * hf + (j >> 2)) + 4 * (l >> 4) + (j & 3);
-                    host[((tb * 2 + hf) * 64 + l) * 8 + j] = bf16_bits(w2[((size_t)tap * 64 + c) * c2 + co]);
+                    host[((tb * 2 + hf) * 64 + l) * 8 + j] = f32_to_bf16_host(w2[((size_t)tap * 64 + c) * c2 + co]);
                 }
     RgbTailWeights w;
     w.c2 = c2;
-    w.a = ctx->dalloc(host.size() * 2);
-    if (!w.a) return SR_ERR_OOM;
-    w.bias = static_cast<float*>(ctx->dalloc(3 * sizeof(float)));
-    if (!w.bias) { ctx->dfree(w.a); return SR_ERR_OOM; }
-    float hb[3] = {0.f, 0.f, 0.f};
-    if (bias2) for (int i = 0; i < c2; ++i) hb[i] = bias2[i];
-    SR_HIP(ctx, hipMemcpy(w.a, host.data(), host.size() * 2, hipMemcpyHostToDevice));
-    SR_HIP(ctx, hipMemcpy(w.bias, hb, sizeof hb, hipMemcpyHostToDevice));
+    if (int rc = weights_upload(ctx, host.data(), host.size() * 2, bias2, c2, 3, &w.a, &w.bias)) return rc;
     *out = w;
     return SR_OK;
 }
@@ -640,32 +625,13 @@ int proj_pack_weights(sr_ctx* ctx, const float* w, const float* bias, int cout, 
             for (int l = 0; l < 64; ++l)
                 for (int j = 0; j < 8; ++j) {
                     const int c = 16 * (2 * hf + (j >> 2)) + 4 * (l >> 4) + (j & 3);
-                    host[((size_t)(nb * 2 + hf) * 64 + l) * 8 + j] = bf16_bits(w[(size_t)c * cout + 16 * nb + (l & 15)]);
+                    host[((size_t)(nb * 2 + hf) * 64 + l) * 8 + j] = f32_to_bf16_host(w[(size_t)c * cout + 16 * nb + (l & 15)]);
                 }
     ProjWeights pw;
     pw.nblk = nblk;
-    pw.a = ctx->dalloc(host.size() * 2);
-    if (!pw.a) return SR_ERR_OOM;
-    pw.bias = static_cast<float*>(ctx->dalloc(sizeof(float) * cout));
-    if (!pw.bias) { ctx->dfree(pw.a); return SR_ERR_OOM; }
-    std::vector<float> hb(cout, 0.f);
-    if (bias) for (int i = 0; i < cout; ++i) hb[i] = bias[i];
-    SR_HIP(ctx, hipMemcpy(pw.a, host.data(), host.size() * 2, hipMemcpyHostToDevice));
-    SR_HIP(ctx, hipMemcpy(pw.bias, hb.data(), sizeof(float) * cout, hipMemcpyHostToDevice));
+    if (int rc = weights_upload(ctx, host.data(), host.size() * 2, bias, cout, cout, &pw.a, &pw.bias)) return rc;
     *out = pw;
     return SR_OK;
-}
-
-void proj_free_weights(sr_ctx* ctx, ProjWeights* w) {
-    if (w->a) ctx->dfree(w->a);
-    if (w->bias) ctx->dfree(w->bias);
-    w->a = nullptr; w->bias = nullptr;
-}
-
-void rgbtail_free_weights(sr_ctx* ctx, RgbTailWeights* w) {
-    if (w->a) ctx->dfree(w->a);
-    if (w->bias) ctx->dfree(w->bias);
-    w->a = nullptr; w->bias = nullptr;
 }
 
 int64_t rgbtail_partial_bytes(int B, int H, int W) {

@@ -851,14 +851,6 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     }
 }
 
-uint16_t bf16_host(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 template <int EXT, int NB0, int NB1, int MODE>
 int launch_chain(sr_ctx* ctx, const ChainParams& p, bool has_o, int nwg, bool seam, hipStream_t st) {
     constexpr int lds = ChainLds<NB0, NB1, MODE>::BYTES;
@@ -909,7 +901,7 @@ int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const floa
     auto frag = [&](const float* w, int cin, int cout, int c, int ky, int kx, int blk) {
         for (int l = 0; l < 64; ++l)
             for (int j = 0; j < 8; ++j)
-                host[idx++] = bf16_host(w[((size_t)(ky * 3 + kx) * cin + 32 * c + 8 * (l >> 4) + j) * cout + 16 * blk + (l & 15)]);
+                host[idx++] = f32_to_bf16_host(w[((size_t)(ky * 3 + kx) * cin + 32 * c + 8 * (l >> 4) + j) * cout + 16 * blk + (l & 15)]);
     };
     for (int c = 0; c < ext; ++c)
         for (int kx = 0; kx < 3; ++kx) {
@@ -921,23 +913,12 @@ int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const floa
     ChainWeights cw;
     cw.ext = ext; cw.nb0 = nb0; cw.nb1 = nb1;
     cw.bytes = host.size() * 2;
-    cw.w = ctx->dalloc(cw.bytes);
-    if (!cw.w) return SR_ERR_OOM;
-    cw.bias = static_cast<float*>(ctx->dalloc(sizeof(float) * (cout_a + cout_b)));
-    if (!cw.bias) { ctx->dfree(cw.w); return SR_ERR_OOM; }
     std::vector<float> hb(cout_a + cout_b, 0.f);
     if (ba) for (int i = 0; i < cout_a; ++i) hb[i] = ba[i];
     if (bb) for (int i = 0; i < cout_b; ++i) hb[cout_a + i] = bb[i];
-    SR_HIP(ctx, hipMemcpy(cw.w, host.data(), cw.bytes, hipMemcpyHostToDevice));
-    SR_HIP(ctx, hipMemcpy(cw.bias, hb.data(), sizeof(float) * hb.size(), hipMemcpyHostToDevice));
+    if (int rc = weights_upload(ctx, host.data(), cw.bytes, hb.data(), (int)hb.size(), (int)hb.size(), &cw.w, &cw.bias)) return rc;
     *out = cw;
     return SR_OK;
-}
-
-void chain_free_weights(sr_ctx* ctx, ChainWeights* w) {
-    if (w->w) ctx->dfree(w->w);
-    if (w->bias) ctx->dfree(w->bias);
-    w->w = nullptr; w->bias = nullptr;
 }
 
 // conv1 of a dense block on the streaming kernel: `in` is the block's row-blocked concat buffer (reads channels [0, 64), writes [64, 96)),
@@ -1015,7 +996,7 @@ int chain_launch(sr_ctx* ctx, const ChainWeights& w, TensorView in, int B, int H
     p.magic = (unsigned)(((1ull << 32) + (unsigned)H) / (unsigned)(H + 1));                 // ceil(2^32 / (H+1)): exact quotient for g (H+1)^2 < 2^32 (checked above)
     p.alpha = alpha; p.xscale = tail ? beta_x / alpha : 0.f; p.oscale = tail && skip_o.p ? beta_o / alpha : 0.f;
     for (float sc : {p.xscale, p.oscale}) {   // the skips join the accumulators as scale * identity MFMA fragments in bf16: only exactly representable ratios (5 and 25 here)
-        uint32_t u = (uint32_t)bf16_host(sc) << 16;
+        uint32_t u = (uint32_t)f32_to_bf16_host(sc) << 16;
         float back;
         memcpy(&back, &u, 4);
         if (back != sc) return ctx->fail(SR_ERR_INVALID, "fused dense-block tail: beta / alpha is not exactly representable in bf16");

@@ -68,7 +68,7 @@ def _wide_grid(B, H, W, nct):
 
 
 def _nct(Cout, K, Cin):
-    """cout tiles per pixel tile of an fp32 wide conv (conv_pack_weights' NT choice)."""
+    """cout tiles per pixel tile of an fp32 wide conv (conv_plan's NT choice)."""
     nb = -(-Cout // 32)
     nt = 2 if nb % 2 == 0 else (3 if nb % 3 == 0 else 1)
     if K == 5:
