@@ -378,6 +378,56 @@ int  sr_eda_pair_stats(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, 
 int  sr_eda_accumulate(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, double* fft_lr_sum_f64,
                        double* fft_hr_sum_f64, double* grad_hr_sum_f64, double* glcm_sum_f64, int64_t* sat_counts_i64, void* stream);
 
+/* ---- dataset synthesis: the per-pixel stages of degrade_image (reference data/common_methods.py:52-107), csrc/degrade.hip ----
+ * B images of one shape, x_u8 and y_u8 DEVICE uint8 [B,H,W,3] in BGR order; 16 <= H, W <= 4096, B <= 32767 (anything else: SR_ERR_INVALID).
+ * params_i32 DEVICE int32 [B,SR_DEG_PARAMS], one row per image, in SR_DEG_* order; a stage whose flag is 0 in a row copies that image
+ * through bit for bit.  The stage entries only launch.  A row outside the contract (below) is never acted on: its image is copied through
+ * and the first such row is recorded on the device; sr_degrade_status waits for the stream, returns SR_ERR_INVALID with the stage, row
+ * and value in sr_last_error when a row was recorded, and clears the record.  Integer arithmetic throughout, no reduction: the same
+ * bits on every run and for any B.  (degrade_image's resize between the blurs and the noise is sr_resize on uint8.)
+ * sr_degrade_gauss: cv2.GaussianBlur(x, (k, k), sigmaX=sigma), k = row[SR_DEG_GAUSS_KSIZE] in {3, 5, 7}, with the integer 8.8 taps
+ *   t[0..k) = row[SR_DEG_GAUSS_TAP0 ..] (each 0..256, sum 256): y = (sum_j t_j sum_i t_i x[y + j - r, x + i - r] + 32768) >> 16 per channel,
+ *   r = k / 2, rounded once after both passes, BORDER_REFLECT_101.  The host derives the taps (sr355.runtime.gauss_taps): g_i =
+ *   exp(-(i - r)^2 / (2 sigma^2)) in fp64, t_i = floor(256 g_i / sum g + 0.5), the centre tap then takes 256 - sum t.  This restates
+ *   OpenCV's 8-bit fixed-point GaussianBlur from its documented structure (8.8 taps, exact integer sums, one rounding); OpenCV spreads the
+ *   tap-rounding residue differently, so a tap may differ by 1/256.  It is not pinned against cv2, which is installed nowhere this project
+ *   runs -- the caveat the EDA's blurs above already carry.
+ * sr_degrade_motion: cv2.filter2D(x, -1, K), K the size x size kernel whose centre row is 1 / size, size = row[SR_DEG_MOTION_SIZE] in
+ *   {5, 7, 9}: a horizontal box, y = (2 S + size) / (2 size) rounded down, S the sum of the size neighbours, BORDER_REFLECT_101.  filter2D
+ *   accumulates in float and rounds half to even; S / size for odd size is never a tie (its fraction is a multiple of 1 / size, at
+ *   least 1/18 from 1/2), and fp32's error on a sum of nine products below 255 is of the order 1e-5, so both round every S alike and
+ *   the integer form is the same function.
+ * sr_degrade_noise: y = (uint8) trunc(min(max(float(x) + n, 0), 255)) where row[SR_DEG_NOISE_ON] != 0, n fp32.  field_f32 DEVICE fp32
+ *   [B,H,W,3] (may be NULL) supplies n: the reference-faithful path, np.random.normal(0, std, shape).astype(np.float32) drawn on the host.
+ *   NULL: n = std * z, std the fp32 whose bits are row[SR_DEG_NOISE_STD] (finite, >= 0), product and sum rounded separately (no
+ *   contraction), z standard normal from Philox4x32-10: key = the 64-bit seed (low word first), counter = (e / 4, 0, image index, 0) for
+ *   element e of the image's flattened (y, x, c), word e % 4 of the block; Box-Muller in fp32 per pair of words (x0, x1), (x2, x3): u1 =
+ *   ((x0 >> 8) + 1) 2^-24, u2 = (x1 >> 8) 2^-24, z = sqrt(-2 ln u1) (cos, sin)(2 pi u2) for the pair's two elements.  z_f32 DEVICE fp32
+ *   [B,H,W,3] (may be NULL; only with field_f32 NULL) receives z for every image, whatever its flag.
+ * sr_degrade_jpeg: cv2.imdecode(cv2.imencode('.jpeg', x, [IMWRITE_JPEG_QUALITY, q])[1], 1), q = row[SR_DEG_JPEG_QUALITY] in 1..100, as
+ *   libjpeg computes it with its defaults, without the lossless entropy coding: BGR -> YCbCr by the 16-bit fixed-point tables; the
+ *   image's last column repeated up to whole blocks, its last row up to an even count; h2v2 chroma down-sampling (a + b + c + d + bias)
+ *   >> 2, bias 1, 2, 1, 2 .. along a row, the last chroma row then repeated up to whole blocks; level shift and the integer "islow"
+ *   forward DCT (13-bit constants, 2 extra bits after the row pass); quantisation by the Annex K tables scaled by quality (scale = 5000 / q
+ *   below 50, 200 - 2 q from 50 up; (base scale + 50) / 100 clamped to 1..255), rounding half away from zero; dequantisation; the "islow"
+ *   inverse DCT, columns first, clamped to 0..255 after the level shift (the SIMD decoders' saturation; libjpeg's C table wraps beyond
+ *   -384..639, which no block of an 8-bit image reaches short of pathological quantisation); h2v2 "fancy" chroma up-sampling (3/4
+ *   nearer + 1/4 further sample per axis, the first and last rows / columns of the chroma image taking themselves, biases 8 / 7 for
+ *   even / odd columns); YCbCr -> BGR.  Pinned bit for bit against libjpeg-turbo through Pillow (tests/golden/degrade_jpeg.npz).
+ *   Optional raw outputs (NULL: not written), with mx = ceil(W / 16), my = ceil(H / 16): coef_y_i16 [B,16 my,16 mx], coef_cb_i16,
+ *   coef_cr_i16 [B,8 my,8 mx] the quantised coefficients, block (i, j)'s coefficient (v, u) at (8 i + v, 8 j + u); plane_y_u8
+ *   [B,16 my,16 mx], plane_cb_u8, plane_cr_u8 [B,8 my,8 mx] the decoded planes (8-byte aligned).  Blocks beyond ceil(H / 8) x ceil(W / 8)
+ *   (chroma: ceil(H / 16) x ceil(W / 16)) come from repeated samples and reach no output pixel.  Untouched for images whose flag is 0. */
+enum { SR_DEG_GAUSS_KSIZE = 0, SR_DEG_GAUSS_TAP0 = 1, SR_DEG_MOTION_SIZE = 8, SR_DEG_NOISE_ON = 9, SR_DEG_NOISE_STD = 10, SR_DEG_JPEG_QUALITY = 11,
+       SR_DEG_INTERP = 12 /* the host's resize grouping; no kernel reads it */, SR_DEG_PARAMS = 16 };
+int  sr_degrade_gauss(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, const int32_t* params_i32, uint8_t* y_u8, void* stream);
+int  sr_degrade_motion(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, const int32_t* params_i32, uint8_t* y_u8, void* stream);
+int  sr_degrade_noise(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, const int32_t* params_i32, const float* field_f32, uint64_t seed,
+                      uint8_t* y_u8, float* z_f32, void* stream);
+int  sr_degrade_jpeg(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, const int32_t* params_i32, uint8_t* y_u8, int16_t* coef_y_i16,
+                     int16_t* coef_cb_i16, int16_t* coef_cr_i16, uint8_t* plane_y_u8, uint8_t* plane_cb_u8, uint8_t* plane_cr_u8, void* stream);
+int  sr_degrade_status(sr_ctx* ctx, void* stream);
+
 /* ---- FineTunedVGG16.fit's per-batch work besides the frozen base (reference VGG16_model.py:111-157), csrc/head_train.hip ----
  * sr_affine_warp: the ImageDataGenerator transform of VGG16_model.py:129-134 as FineTunedVGG16._augment computes it (scipy
  *   affine_transform order=1, mode="nearest", per channel, then the flip), with the batch's gather fused in.  x DEVICE fp32 [N,H,W,C];

@@ -58,6 +58,8 @@ struct sr_ctx {
     Arena met_work, met_fft;            // metrics.hip: flags / partials / histograms, the DFT chunk's operands (stream-ordered reuse)
     Arena eda_work, eda_dct;            // eda.hip: accumulators / label maps / co-occurrence counts, the DCT / DFT chunk's operands; its DCT operators sit in
                                         // dft_ops under the keys -(2^32 + N)
+    Arena deg_work;                     // degrade.hip: the JPEG round trip's planar Y / Cb / Cr between its two kernels
+    int* deg_status = nullptr;          // degrade.hip: {stage, row, value} of the first bad parameter-table row a kernel met (sr_degrade_status)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
     struct PackKey {

@@ -107,6 +107,11 @@ SIGNATURES = {
     "sr_classic_scores": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_eda_pair_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_eda_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_degrade_gauss": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_degrade_motion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_degrade_noise": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "sr_degrade_jpeg": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_degrade_status": (_i, [_vp, _vp]),
     "sr_affine_warp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_dense_head_workspace_bytes": (_i64, [_i, _i]),
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
@@ -125,6 +130,9 @@ EDA_STAT_NAMES = (("psnr", "ssim", "glcm_contrast", "glcm_homogeneity", "glcm_co
                   + ("sobel_mean_lr", "sobel_mean_hr")
                   + tuple(f"ch{c}_{k}_{s}" for k in ("mean", "std") for c in range(3) for s in ("lr", "hr")))
 EDA_ROW_COLUMNS = EDA_STAT_NAMES[:32]
+
+# the columns of a degrade parameter-table row (SR_DEG_* in include/sr355.h)
+DEG_GAUSS_KSIZE, DEG_GAUSS_TAP0, DEG_MOTION_SIZE, DEG_NOISE_ON, DEG_NOISE_STD, DEG_JPEG_QUALITY, DEG_INTERP, DEG_PARAMS = 0, 1, 8, 9, 10, 11, 12, 16
 
 _lib = None
 

@@ -52,6 +52,18 @@ def _check_tensor(ctx, t, name, dtypes=(torch.float32,)):
     return t
 
 
+def gauss_taps(ksize, sigma):
+    """The integer 8.8 taps sr_degrade_gauss takes for GaussianBlur((ksize, ksize), sigma): g_i = exp(-(i - r)^2 / (2 sigma^2)) in fp64,
+    t_i = floor(256 g_i / sum g + 0.5), the centre tap then takes 256 - sum t (include/sr355.h)."""
+    if ksize not in (3, 5, 7) or not sigma > 0:
+        raise ValueError(f"gauss_taps: ksize must be 3, 5 or 7 and sigma positive, got {ksize!r}, {sigma!r}")
+    r = ksize // 2
+    g = np.exp(-((np.arange(ksize, dtype=np.float64) - r) ** 2) / (2.0 * float(sigma) ** 2))
+    t = np.floor(256.0 * g / g.sum() + 0.5).astype(np.int64)
+    t[r] += 256 - int(t.sum())
+    return t.astype(np.int32)
+
+
 class Context:
     """sr_ctx wrapper; `Context.get(i)` returns the process-wide context of GPU i."""
     _instances = {}
@@ -411,6 +423,99 @@ class Context:
         self.check(self.lib.sr_eda_accumulate(self.h, lr.data_ptr(), hr.data_ptr(), B, H, W, acc["lr_fft_sum"].data_ptr(), acc["hr_fft_sum"].data_ptr(),
                                               acc["grad_hr_sum"].data_ptr(), acc["glcm_sum"].data_ptr(), acc["sat_counts"].data_ptr(), self.stream()))
         return acc
+
+    # ------------------------------------------------------------------ dataset synthesis: degrade_image's per-pixel stages (common_methods.py:52-107)
+    @staticmethod
+    def degrade_params(records):
+        """Host int32 table [B, 16] (SR_DEG_* columns) from one dict per image: gauss_ksize (0 / None: off) with gauss_sigma or gauss_taps,
+        motion_size (0: off), noise_std (None: off), jpeg_quality (0: off), interp_code.  Missing keys mean off."""
+        t = np.zeros((len(records), L.DEG_PARAMS), np.int32)
+        for i, r in enumerate(records):
+            k = int(r.get("gauss_ksize") or 0)
+            if k:
+                taps = r["gauss_taps"] if r.get("gauss_taps") is not None else gauss_taps(k, r["gauss_sigma"])
+                t[i, L.DEG_GAUSS_KSIZE] = k
+                t[i, L.DEG_GAUSS_TAP0:L.DEG_GAUSS_TAP0 + len(taps)] = taps
+            t[i, L.DEG_MOTION_SIZE] = int(r.get("motion_size") or 0)
+            if r.get("noise_std") is not None:
+                t[i, L.DEG_NOISE_ON] = 1
+                t[i, L.DEG_NOISE_STD] = np.array([r["noise_std"]], np.float32).view(np.int32)[0]
+            t[i, L.DEG_JPEG_QUALITY] = int(r.get("jpeg_quality") or 0)
+            t[i, L.DEG_INTERP] = int(r.get("interp_code") or 0)
+        return t
+
+    def _degrade_args(self, x, params, who):
+        if isinstance(x, torch.Tensor) and x.dtype != torch.uint8:
+            raise NotImplementedError(f"{who}: {x.dtype} images are not offered (the dataset's frames are 8-bit BGR)")
+        _check_tensor(self, x, f"{who} input", (torch.uint8,))
+        if x.dim() != 4 or x.shape[3] != 3:
+            raise ValueError(f"{who}: expected a uint8 BGR batch [B,H,W,3], got shape {tuple(x.shape)}")
+        if not isinstance(params, torch.Tensor):
+            params = self.to_device(np.ascontiguousarray(params, dtype=np.int32))
+        _check_tensor(self, params, f"{who} params", (torch.int32,))
+        if tuple(params.shape) != (x.shape[0], L.DEG_PARAMS):
+            raise ValueError(f"{who}: the parameter table must be int32 [{x.shape[0]}, {L.DEG_PARAMS}], got {tuple(params.shape)}")
+        return params, x.shape[0], x.shape[1], x.shape[2]
+
+    def degrade_status(self):
+        """Waits for the stream and raises ValueError when a degrade stage met a parameter row outside its contract (sr_degrade_status)."""
+        self.check(self.lib.sr_degrade_status(self.h, self.stream()))
+
+    def degrade_gauss(self, x, params, check=True):
+        """cv2.GaussianBlur per image of x [B,H,W,3] uint8 with the kernel size and 8.8 taps of its row of `params` (sr_degrade_gauss).
+        check=False leaves the table's validation to a later degrade_status() (no wait for the device here)."""
+        params, B, H, W = self._degrade_args(x, params, "degrade_gauss")
+        y = torch.empty_like(x)
+        self.check(self.lib.sr_degrade_gauss(self.h, x.data_ptr(), B, H, W, params.data_ptr(), y.data_ptr(), self.stream()))
+        if check:
+            self.degrade_status()
+        return y
+
+    def degrade_motion(self, x, params, check=True):
+        """The reference's horizontal motion blur (filter2D with a centre row of 1 / size) per image (sr_degrade_motion)."""
+        params, B, H, W = self._degrade_args(x, params, "degrade_motion")
+        y = torch.empty_like(x)
+        self.check(self.lib.sr_degrade_motion(self.h, x.data_ptr(), B, H, W, params.data_ptr(), y.data_ptr(), self.stream()))
+        if check:
+            self.degrade_status()
+        return y
+
+    def degrade_noise(self, x, params, field=None, seed=0, raw=False, check=True):
+        """clip(float32(x) + n, 0, 255) truncated (sr_degrade_noise).  field: float32 [B,H,W,3] device tensor of n (the reference's host
+        draw); None: n = std * z from the kernel's Philox4x32-10 stream keyed by the 64-bit `seed`, and raw=True -> (y, z float32)."""
+        params, B, H, W = self._degrade_args(x, params, "degrade_noise")
+        if field is not None:
+            _check_tensor(self, field, "degrade_noise field")
+            if field.shape != x.shape:
+                raise ValueError(f"degrade_noise: the field's shape {tuple(field.shape)} is not the batch's {tuple(x.shape)}")
+            if raw:
+                raise ValueError("degrade_noise: raw=True returns the kernel's own z; there is none with a supplied field")
+        y = torch.empty_like(x)
+        z = self.empty(x.shape, torch.float32) if raw else None
+        self.check(self.lib.sr_degrade_noise(self.h, x.data_ptr(), B, H, W, params.data_ptr(), None if field is None else field.data_ptr(),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, y.data_ptr(), None if z is None else z.data_ptr(), self.stream()))
+        if check:
+            self.degrade_status()
+        return (y, z) if raw else y
+
+    def degrade_jpeg(self, x, params, raw=False, check=True):
+        """The baseline-JPEG round trip of cv2.imencode / imdecode at each row's quality (sr_degrade_jpeg).  raw=True -> (y, dict: 'coef_y'
+        int16 [B,16 my,16 mx], 'coef_cb', 'coef_cr' int16 [B,8 my,8 mx] quantised coefficients, 'y', 'cb', 'cr' uint8 decoded planes of those
+        shapes; mx, my = ceil(W / 16), ceil(H / 16)); zeros for images whose quality is 0."""
+        params, B, H, W = self._degrade_args(x, params, "degrade_jpeg")
+        y = torch.empty_like(x)
+        inter = {}
+        if raw:
+            mx, my = (W + 15) // 16, (H + 15) // 16
+            for k, f in (("y", 16), ("cb", 8), ("cr", 8)):
+                inter["coef_" + k] = torch.zeros((B, f * my, f * mx), dtype=torch.int16, device=self.torch_device)
+                inter[k] = torch.zeros((B, f * my, f * mx), dtype=torch.uint8, device=self.torch_device)
+        ptr = (lambda k: inter[k].data_ptr() if k in inter else None)
+        self.check(self.lib.sr_degrade_jpeg(self.h, x.data_ptr(), B, H, W, params.data_ptr(), y.data_ptr(), ptr("coef_y"), ptr("coef_cb"), ptr("coef_cr"),
+                                            ptr("y"), ptr("cb"), ptr("cr"), self.stream()))
+        if check:
+            self.degrade_status()
+        return (y, inter) if raw else y
 
     @staticmethod
     def _view(t, coff, c):
