@@ -428,6 +428,41 @@ int  sr_degrade_jpeg(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, cons
                      int16_t* coef_cb_i16, int16_t* coef_cr_i16, uint8_t* plane_y_u8, uint8_t* plane_cb_u8, uint8_t* plane_cr_u8, void* stream);
 int  sr_degrade_status(sr_ctx* ctx, void* stream);
 
+/* ---- dataset synthesis: smart_square_crop (reference data/common_methods.py:4-49) for a stack of frames, csrc/crop.hip ----
+ * B frames of one shape, bgr_u8 DEVICE uint8 [B,H,W,3] in BGR order; 2 <= H, W <= 4096, B <= 32767 (anything else: SR_ERR_INVALID).  The
+ * reference thresholds the gray frame with Otsu, takes findContours(RETR_EXTERNAL)'s contour of the largest contourArea, and cuts the
+ * square of side S = min(W, H) centred on that contour's boundingRect.  No contour is traced here; each stage is stated as what it computes:
+ *   gray      COLOR_BGR2GRAY exactly as the EDA section above states it;
+ *   otsu_t    OpenCV 4's getThreshVal_Otsu_8u on the frame's 256-bin histogram h, in fp64, every operation rounded on its own (no fused
+ *             multiply-add): scale = 1 / (W H); mu = scale sum_i i h[i], the sum in ascending i; then, from mu1 = q1 = 0, for i = 0 .. 255:
+ *             p = h[i] scale; mu1 *= q1; q1 += p; q2 = 1 - q1; i is skipped when min(q1, q2) < FLT_EPSILON or max(q1, q2) > 1 - FLT_EPSILON;
+ *             else mu1 = (mu1 + i p) / q1, mu2 = (mu - q1 mu1) / q2, sigma = q1 q2 (mu1 - mu2)^2, and i is kept when sigma exceeds every
+ *             earlier sigma (strictly; 0 to begin with).  A constant frame gives 0;
+ *   mask      gray > otsu_t (255 / 0);
+ *   filled    findContours pads the frame with one ring of background (OpenCV >= 3.2; border pixels count as image).  `outside` is the
+ *             4-connected component of the background (mask == 0) that holds that ring: every background pixel 4-connected to the frame's
+ *             border.  F = not outside: the foreground, its holes and whatever lies inside them;
+ *   labels    the external contours correspond one to one to the 8-connected components of F.  A pixel's label is the smallest raster index
+ *             y W + x of its component (the pixel at which the border follower's raster scan starts that contour), -1 outside F;
+ *   area      contourArea of a component's traced outer border = sum over the 2 x 2 pixel cells of the frame: 1 for a cell with all four
+ *             pixels in the component, 1/2 for exactly three, 0 otherwise (kept as twice the area, an integer);
+ *   winner    the component of the largest area; among equal areas the one with the LARGEST label.  (max(contours, key=contourArea) takes
+ *             the first maximum of a list that OpenCV returns last-found first.  That order is the one point of this contract that is not
+ *             pinned against OpenCV itself, which is installed nowhere this project runs; ties occur only among zero-area contours, single
+ *             pixels and one-pixel lines.)  A component nested in another's hole is part of that other's F component and never competes;
+ *   box       boundingRect = the winner's pixel bounding box (x, y, ww, hh); cx = x + ww / 2, cy = y + hh / 2 (integer division);
+ *             left = max(0, cx - S / 2), top = max(0, cy - S / 2), then pulled back to W - S / H - S where the square would leave the frame.
+ *             Without any foreground pixel: found = 0, x = y = ww = hh = 0 and the centre crop left = (W - S) / 2, top = (H - S) / 2.
+ * sr_object_boxes: boxes_i32 DEVICE int32 [B,SR_BOX_COLS] in SR_BOX_* order.  Optional raw outputs (NULL: not written): gray_u8, mask_u8
+ *   [B,H,W], labels_i32 [B,H,W].  Launches only; every sum is an integer atomic: a frame's row is the same bits on every run and for any B.
+ * sr_square_crop: y_u8 DEVICE uint8 [B,S,S,3] = bgr_u8[b, top : top + S, left : left + S] with left, top of the frame's row of boxes_i32
+ *   (as sr_object_boxes wrote it, or the caller's own); a left or top outside 0 .. W - S / 0 .. H - S is clamped into that range, so no
+ *   table reads outside the frame.  y_u8 must not be bgr_u8.  A square frame is copied whole. */
+enum { SR_BOX_FOUND = 0, SR_BOX_X, SR_BOX_Y, SR_BOX_W, SR_BOX_H, SR_BOX_LEFT, SR_BOX_TOP, SR_BOX_OTSU, SR_BOX_COLS };
+int  sr_object_boxes(sr_ctx* ctx, const uint8_t* bgr_u8, int B, int H, int W, int32_t* boxes_i32, uint8_t* gray_u8, uint8_t* mask_u8,
+                     int32_t* labels_i32, void* stream);
+int  sr_square_crop(sr_ctx* ctx, const uint8_t* bgr_u8, int B, int H, int W, const int32_t* boxes_i32, uint8_t* y_u8, void* stream);
+
 /* ---- FineTunedVGG16.fit's per-batch work besides the frozen base (reference VGG16_model.py:111-157), csrc/head_train.hip ----
  * sr_affine_warp: the ImageDataGenerator transform of VGG16_model.py:129-134 as FineTunedVGG16._augment computes it (scipy
  *   affine_transform order=1, mode="nearest", per channel, then the flip), with the batch's gather fused in.  x DEVICE fp32 [N,H,W,C];

@@ -59,6 +59,7 @@ struct sr_ctx {
     Arena eda_work, eda_dct;            // eda.hip: accumulators / label maps / co-occurrence counts, the DCT / DFT chunk's operands; its DCT operators sit in
                                         // dft_ops under the keys -(2^32 + N)
     Arena deg_work;                     // degrade.hip: the JPEG round trip's planar Y / Cb / Cr between its two kernels
+    Arena crop_work;                    // crop.hip: gray / mask / filled planes, the label map, per-root areas, per-frame histograms and winners
     int* deg_status = nullptr;          // degrade.hip: {stage, row, value} of the first bad parameter-table row a kernel met (sr_degrade_status)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
@@ -112,6 +113,9 @@ struct DeviceGuard {
         if (e_ != hipSuccess)                                                                    \
             return (ctx)->fail(SR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
+
+// OpenCV's 8-bit COLOR_BGR2GRAY (include/sr355.h, the EDA section): the one statement of it, for eda.hip and crop.hip
+__device__ inline int gray_bgr(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }
 
 static inline int dtype_size(int dt) { return dt == SR_DTYPE_F32 ? 4 : (dt == SR_DTYPE_BF16 ? 2 : 1); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }

@@ -64,8 +64,6 @@ __device__ inline int r101(int i, int n) {
 
 __device__ inline int clampi(int i, int lo, int hi) { return i < lo ? lo : (i > hi ? hi : i); }
 
-__device__ inline int gray_bgr(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }
-
 // 8-bit COLOR_BGR2HSV's V and S: V = max, S = (diff * sdiv[V] + 2^11) >> 12, sdiv[v] = round(255 * 2^12 / v) (never a tie), sdiv[0] = 0
 __device__ inline void hsv_sv(int b, int g, int r, int* s, int* v) {
     const int mx = max(b, max(g, r)), mn = min(b, min(g, r));

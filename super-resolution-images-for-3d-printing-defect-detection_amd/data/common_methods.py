@@ -9,8 +9,12 @@ np.random state (or a RandomState handed in) and returns them as a record, witho
 degrade_image therefore takes the decisions the reference takes after the same seed, noise field included.  degrade_batch does a whole
 stack in one pass with decisions from a seeded np.random.Generator and the noise from the kernel's counter-based Philox generator.
 
-Out of scope: smart_square_crop (Otsu threshold and contour tracing: host work on one image at a time) raises NotImplementedError.
-Importing this module and draw_degradation need no GPU."""
+The crop that precedes it in the notebook's loop, smart_square_crop, runs on the device for a stack of frames: square_crop_batch (csrc/crop.hip:
+Otsu threshold, hole filling and connected components in place of contour tracing, sr_object_boxes / sr_square_crop), and synthesize_pairs is
+the loop's body -- crop, then degrade -- with nothing returning to the host in between.
+
+Out of scope: smart_square_crop itself (Otsu threshold and contour tracing: host work on one image at a time) raises NotImplementedError;
+square_crop_batch is its batched form.  Importing this module and draw_degradation need no GPU."""
 import numpy as np
 
 # cv2.INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4, in the order the reference hands them to np.random.choice
@@ -26,7 +30,8 @@ def _context():
 
 def smart_square_crop(img):
     raise NotImplementedError("smart_square_crop: Otsu thresholding and contour tracing are host work on one image at a time and are outside this "
-                              "port's scope (crop the frames with the reference's own function before handing them to degrade_image)")
+                              "port's scope (crop the frames with the reference's own function before handing them to degrade_image, or hand a stack of "
+                              "frames [B, H, W, 3] to square_crop_batch, which computes the same crop on the device)")
 
 
 def lr_size(shape, scale_factor):
@@ -97,6 +102,23 @@ def _check_frames(a, ndim, who):
     return a, is_t
 
 
+def _check_stack(a, who):
+    """_check_frames for the crop's input: any frame of at least 2 x 2 pixels, and at least one of them.  Touches no device."""
+    import torch
+    is_t = isinstance(a, torch.Tensor)
+    if not is_t:
+        a = np.asarray(a)
+    if a.dtype != (torch.uint8 if is_t else np.uint8):
+        raise NotImplementedError(f"{who}: {a.dtype} images are not offered (the dataset's frames are 8-bit BGR)")
+    if a.ndim != 4 or a.shape[-1] != 3:
+        raise ValueError(f"{who}: expected uint8 BGR [B, H, W, 3], got shape {tuple(a.shape)}")
+    if a.shape[0] < 1:
+        raise ValueError(f"{who}: empty batch")
+    if min(int(a.shape[1]), int(a.shape[2])) < 2:
+        raise ValueError(f"{who}: frames of {int(a.shape[1])} x {int(a.shape[2])} are below the crop's minimum of 2 pixels a side")
+    return a, is_t
+
+
 def _run_stages(ctx, x, recs, field=None, seed=0):
     """x [B,H,W,3] uint8 on the device through the stages the records switch on -> LR batch on the device."""
     params = ctx.to_device(ctx.degrade_params(recs))
@@ -150,3 +172,29 @@ def degrade_batch(hr_batch, scale_factor=0.5, seed=0):
     ctx = _context()
     x = a.contiguous() if is_t else ctx.to_device(np.ascontiguousarray(a))
     return _run_stages(ctx, x, recs, seed=int(seed)), [r["interp_name"] for r in recs]
+
+
+def square_crop_batch(frames):
+    """The reference's smart_square_crop for a stack: frames uint8 BGR [B, H, W, 3] (NumPy array or device tensor) -> (crops uint8
+    [B, S, S, 3] on the device, S = min(H, W); boxes as a NumPy int32 array [B, 8]: found, x, y, w, h of the largest contour's bounding
+    rectangle, left, top of the crop, Otsu's threshold).  The frames themselves never come back to the host."""
+    a, is_t = _check_stack(frames, "square_crop_batch")
+    ctx = _context()
+    x = a.contiguous() if is_t else ctx.to_device(np.ascontiguousarray(a))
+    boxes = ctx.object_boxes(x)
+    return ctx.square_crop(x, boxes, check=False), boxes.cpu().numpy()
+
+
+def synthesize_pairs(frames, scale_factor=0.5, seed=0):
+    """The notebook's loop body for a stack of decoded frames: hr = smart_square_crop(frame), lr = degrade_image(hr), as square_crop_batch
+    followed by degrade_batch's stages, the crops staying on the device.  -> (hr crops uint8 [B, S, S, 3] and lr uint8 [B, h, w, 3] on the
+    device, the list of interpolation names)."""
+    a, is_t = _check_stack(frames, "synthesize_pairs")
+    S = min(int(a.shape[1]), int(a.shape[2]))
+    if min(S, *lr_size((S, S), scale_factor)) < MIN_SIDE:
+        raise ValueError(f"synthesize_pairs: crops of {S} x {S} at scale {scale_factor} are below the device stages' minimum of {MIN_SIDE} pixels a side")
+    ctx = _context()
+    x = a.contiguous() if is_t else ctx.to_device(np.ascontiguousarray(a))
+    hr = ctx.square_crop(x)
+    lr, names = degrade_batch(hr, scale_factor, seed)
+    return hr, lr, names

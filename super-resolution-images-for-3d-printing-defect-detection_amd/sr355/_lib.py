@@ -112,6 +112,8 @@ SIGNATURES = {
     "sr_degrade_noise": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "sr_degrade_jpeg": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_degrade_status": (_i, [_vp, _vp]),
+    "sr_object_boxes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sr_square_crop": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sr_affine_warp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_dense_head_workspace_bytes": (_i64, [_i, _i]),
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
@@ -133,6 +135,9 @@ EDA_ROW_COLUMNS = EDA_STAT_NAMES[:32]
 
 # the columns of a degrade parameter-table row (SR_DEG_* in include/sr355.h)
 DEG_GAUSS_KSIZE, DEG_GAUSS_TAP0, DEG_MOTION_SIZE, DEG_NOISE_ON, DEG_NOISE_STD, DEG_JPEG_QUALITY, DEG_INTERP, DEG_PARAMS = 0, 1, 8, 9, 10, 11, 12, 16
+
+# the columns of a row of sr_object_boxes (SR_BOX_* in include/sr355.h)
+BOX_NAMES = ("found", "x", "y", "w", "h", "left", "top", "otsu_t")
 
 _lib = None
 

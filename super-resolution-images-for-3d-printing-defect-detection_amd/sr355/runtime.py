@@ -517,6 +517,54 @@ class Context:
             self.degrade_status()
         return (y, inter) if raw else y
 
+    # ------------------------------------------------------------------ dataset synthesis: smart_square_crop for a stack of frames (common_methods.py:4-49)
+    def _crop_frames(self, x, who):
+        if isinstance(x, torch.Tensor) and x.dtype != torch.uint8:
+            raise NotImplementedError(f"{who}: {x.dtype} images are not offered (the dataset's frames are 8-bit BGR)")
+        _check_tensor(self, x, f"{who} input", (torch.uint8,))
+        if x.dim() != 4 or x.shape[3] != 3 or x.shape[0] < 1:
+            raise ValueError(f"{who}: expected a non-empty uint8 BGR batch [B,H,W,3], got shape {tuple(x.shape)}")
+        return x.shape[0], x.shape[1], x.shape[2]
+
+    def object_boxes(self, x, raw=False):
+        """Per frame of x [B,H,W,3] uint8 BGR (device tensor): the Otsu mask's largest external contour and the square crop centred on it
+        (sr_object_boxes) -> int32 [B, 8] on the device, columns BOX_NAMES: found, x, y, w, h (the contour's bounding rectangle), left,
+        top (the crop's origin), otsu_t.  raw=True -> (boxes, dict: 'gray' uint8 [B,H,W], 'mask' uint8 [B,H,W] (0 / 255), 'labels' int32
+        [B,H,W]: the smallest raster index of the pixel's component of the hole-filled mask, -1 outside it)."""
+        B, H, W = self._crop_frames(x, "object_boxes")
+        boxes = self.empty((B, len(L.BOX_NAMES)), torch.int32)
+        inter = {}
+        if raw:
+            inter = {"gray": self.empty((B, H, W), torch.uint8), "mask": self.empty((B, H, W), torch.uint8), "labels": self.empty((B, H, W), torch.int32)}
+        ptr = (lambda k: inter[k].data_ptr() if k in inter else None)
+        self.check(self.lib.sr_object_boxes(self.h, x.data_ptr(), B, H, W, boxes.data_ptr(), ptr("gray"), ptr("mask"), ptr("labels"), self.stream()))
+        return (boxes, inter) if raw else boxes
+
+    def square_crop(self, x, boxes=None, check=True):
+        """x[b, top : top + S, left : left + S], S = min(H, W), with left and top from frame b's row of `boxes` (sr_square_crop) -> uint8
+        [B,S,S,3] on the device.  boxes None: object_boxes(x), nothing returning to the host in between.  A table of the caller's (int32
+        [B, 8], device tensor or array) is validated here when check=True, which waits for the device; check=False leaves a left or top
+        outside the frame to the kernel, which clamps it into the frame."""
+        B, H, W = self._crop_frames(x, "square_crop")
+        S = min(H, W)
+        if boxes is None:
+            boxes = self.object_boxes(x)
+        else:
+            if not isinstance(boxes, torch.Tensor):
+                boxes = self.to_device(np.ascontiguousarray(boxes, dtype=np.int32))
+            _check_tensor(self, boxes, "square_crop boxes", (torch.int32,))
+            if tuple(boxes.shape) != (B, len(L.BOX_NAMES)):
+                raise ValueError(f"square_crop: the box table must be int32 [{B}, {len(L.BOX_NAMES)}], got {tuple(boxes.shape)}")
+            if check:
+                lt = boxes[:, 5:7].cpu().numpy()
+                bad = np.nonzero((lt[:, 0] < 0) | (lt[:, 0] > W - S) | (lt[:, 1] < 0) | (lt[:, 1] > H - S))[0]
+                if bad.size:
+                    raise ValueError(f"square_crop: row {int(bad[0])} of the box table puts the {S} x {S} square at left {int(lt[bad[0], 0])}, top "
+                                     f"{int(lt[bad[0], 1])}, outside the {H} x {W} frame")
+        y = self.empty((B, S, S, 3), torch.uint8)
+        self.check(self.lib.sr_square_crop(self.h, x.data_ptr(), B, H, W, boxes.data_ptr(), y.data_ptr(), self.stream()))
+        return y
+
     @staticmethod
     def _view(t, coff, c):
         """(tensor [B,H,W,Cbuf] fp32 contiguous, first channel, channels) -> sr_view."""
