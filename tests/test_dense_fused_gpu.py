@@ -139,6 +139,49 @@ def test_fused_tail_exact_integers(fused_ctx):
         assert np.array_equal(t0[n].float().cpu().numpy().astype(np.float64), ref), n
 
 
+def test_fused_seam_exact_integers(fused_ctx):
+    """test_fused_tail_exact_integers on the SEAM instances: (7, 11, 24, 3) rides two-up (an odd batch: the last pair's right half is padding; two ranges
+    cutting the packed images), sparse small-integer weights at three times that test's density (dense_ref.EXACT_DENSITY: the most the < 2^8 exactness
+    allows).  Fused and layer-by-layer conv2 / conv3 must be IDENTICAL and equal to the fp64 integers; a conv reading across columns 23 | 24 adds an
+    integer of the neighbour image and cannot hide in a rounding."""
+    import dense_ref as D
+    ctx = fused_ctx
+    m = Model("esrgan_g", compute_dtype="bf16", scale_factor=2, num_blocks=1, growth_channels=32, use_attention=False, ctx=ctx)
+    w = bf16_rounded(D.exact_integer_weights(m.layer_shapes(), D.EXACT_DENSITY, D.EXACT_SEED))
+    m.set_weights(w)
+    x, feats = D.exact_integer_case()
+    assert x.shape == (7, 11, 24, 3)
+    xd = ctx.to_device(x, torch.bfloat16)
+    names = ["rrdb_0_dense1_conv2", "rrdb_0_dense1_conv3", "rrdb_0_dense1_conv5", "rrdb_0_dense2_conv5", "rrdb_0_dense3_conv5"]
+    ctx.set_fused(0, 0)
+    ctx.profile_begin()
+    _, t0 = m.forward_with_taps(xd, names + ["rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"])
+    k0 = {r["kernel"] for r in ctx.profile_end()}
+    ctx.set_fused(ctx.FUSED_ALL, 2)
+    ctx.profile_begin()
+    _, t1 = m.forward_with_taps(xd, names + ["rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"])
+    k1 = {r["kernel"] for r in ctx.profile_end()}
+    assert not any(k.startswith("dense_") for k in k0), k0
+    # on 24-pixel-wide images the fused kernels (48-pixel rows only) can have run no other way than two-up
+    assert {"dense_tail_fused<bf16,conv4+conv5>", "dense_pair_fused<bf16>", "dense_conv1_stream<bf16,64->32>"} <= k1, k1
+    assert not any(k.startswith("conv_rows<bf16,k3,kg1,nt2>") for k in k1), k1
+    for n in ("rrdb_0_dense1_conv1", "rrdb_0_dense2_conv1"):
+        a, b = t0[n].cpu().numpy(), t1[n].cpu().numpy()
+        assert (np.array_equal(a, b) if "dense1" in n else np.abs(a - b).max() <= 2.0 ** -7 * max(1.0, np.abs(a).max())), (n, float(np.abs(a - b).max()))
+    for n in names[:2]:
+        a, b = t0[n].cpu().numpy(), t1[n].cpu().numpy()
+        assert np.array_equal(a, b), (n, float(np.abs(a - b).max()), np.argwhere(a != b)[:5])
+    for n in names[2:]:                                                       # that test's rule for conv5: x + 0.2 * conv5 is no integer
+        a, b = t0[n].cpu().numpy(), t1[n].cpu().numpy()
+        assert np.abs(a - b).max() <= 2.0 ** -7 * max(1.0, np.abs(a).max()), (n, float(np.abs(a - b).max()))
+    # the reference's integers: everything conv2 and conv3 read is below 2^8 (exact in bf16 storage); conv3's own sums may exceed it and are rounded once
+    assert max(float(np.abs(f).max()) for f in feats[:3]) < 256 and all(np.array_equal(f, np.round(f)) for f in feats)
+    for n, ref in (("rrdb_0_dense1_conv1", feats[1]), ("rrdb_0_dense1_conv2", feats[2]), ("rrdb_0_dense1_conv3", D.rbf(feats[3]))):
+        for t in (t1, t0):
+            got = t[n].float().cpu().numpy().astype(np.float64)
+            assert np.array_equal(got, ref), (n, np.argwhere(got != ref)[:5])
+
+
 # ---- 24-pixel-wide patches, two per 48-pixel row (round 4: api.hip pack2, dense_fused.hip SEAM; patch_size_lr = 24 is the reference's own training patch,
 # ESRGAN_model.py:858 / constants.py:8) ----
 
