@@ -21,6 +21,12 @@
 //   * roles: 8 compute waves (one stream row each; MFMAs, LDS reads, epilogues) + 4 loader waves (the whole DMA stream, one or two
 //     granules / chunks ahead, counted vmcnt; they also hold part -- for the growth pairs all -- of the weights in their registers for
 //     the whole kernel and put them into the slots with ds_write_b128); one s_barrier per granule (54 MFMAs per compute wave);
+//   * a compute wave's operand reads are one static software pipeline (weight fragment of stage k + 3 and the next row's pixel fragments requested
+//     ahead of the MFMAs of stage k).  In the tail the pipeline runs on ACROSS the granule barriers between an epilogue and the next: a granule's last
+//     stages request the next granule's first three weight fragments -- resident pieces, written and published a granule early; a granule is packed in
+//     stage order for that -- and, inside a chunk and between the ring's kx taps, its row 0; the barrier waits with a counted lgkmcnt.  The growth pairs
+//     restart the pipeline behind every barrier (their two weight slots are written while the pre-read would run; the skeleton prices a ring of their
+//     own for the first fragments at no gain at 36 MFMAs per granule: DESIGN.md 3.15);
 //   * output rows leave through an LDS transposition (whole cache lines instead of 64 16-byte fragments per store instruction).
 // LDS: tail 2 x 33 + 30 + 3 x 18 KiB = 150 KiB, pairs 3 x 33 + 30 + 2 x 12 = 153 KiB -> one workgroup per CU, three waves per SIMD.
 // What bounds the kernels (round 3): not the CU's memory port -- it delivers 59 B/clk from L2 and the loaders now issue a
@@ -51,7 +57,7 @@ struct ChainParams {
     int B, H;
     int rows_per_wg; unsigned magic;   // stream rows (separators included) a workgroup owns; g / (H+1) == umulhi(g, magic) for every stream row index that occurs
     float alpha, xscale, oscale;       // MODE 1: out = alpha * (acc + bias + xscale * x + oscale * so); xscale = beta_x / alpha, oscale = beta_o / alpha, both exact in bf16
-    int dbg_flags;                     // diagnostic builds only (env SR355_CHAIN_DBG_FLAGS): 1 = drop the tail's output stores, 2 = skip the external granules' MFMA bodies (timing experiments; results are wrong)
+    int dbg_flags;                     // diagnostic builds only (env SR355_CHAIN_DBG_FLAGS): 1 = drop the tail's output stores (timing experiment; results are wrong)
     unsigned long long* dbg;           // diagnostic builds only (sr_debug_set_chain_stamp_buffer): s_memtime stamps, [wg < 64][wave 0 / 5 / 8 / 11][granule < 64][4]
 };
 
@@ -120,6 +126,23 @@ template <int EXT, int NB0, int NB1, int MODE, int LW> struct LoaderPlan {
 
 // (the same for the tail's 64 couts -- two 32-channel chunks of the row-blocked destination -- measured 0.3-0.5 % on the tail, inside the noise: the
 // transposition through LDS stays there)
+// Which operands of a granule its predecessor has already requested (chain2_kernel's compute waves, "one continuous pipeline").  Weights: the first WDEPTH
+// fragments, from the next weight slot.  Pixels: row 0 of the next granule -- only where that row is already published and is not rewritten during the
+// following iteration:
+//   kx -> kx + 1 inside an external chunk: the same staging buffer; ring kx 0 -> 1 -> 2: the same ring rows;
+//   chunk c -> c + 1: growth pairs only (three staging buffers, rows published a chunk early); the tail's next chunk is published by the very barrier in between;
+//   never into a step's first granule or into ring kx = 0 (behind the bias re-initialisation / the layer-0 epilogue that has just written the ring row).
+// tests/test_operand_prefetch_schedule_cpu.py restates this and replays it against the loaders' schedule.
+template <int EXT, int MODE, bool CARRY> struct CarryPlan {
+    static constexpr bool ext_w(int i) { return CARRY && i > 0 && i < 3 * EXT; }                      // external granule i = 3 * chunk + kx of a step
+    static constexpr bool ext_x(int i) { return ext_w(i) && (i % 3 != 0 || MODE == 0); }
+    static constexpr bool ring_w(int kx) { return CARRY && kx > 0 && kx < 3; }
+    static constexpr bool ring_x(int kx) { return ring_w(kx); }
+};
+// MODE 1 (tail): carried.  MODE 0 (growth pairs): not carried -- their weight slot of granule G + 1 is written during granule G (two slots, one granule
+// ahead); the first fragments would need a three-buffer ring of their own, and the skeleton shows nothing to gain at their granule sizes.
+template <int MODE> constexpr bool kCarry = MODE == 1;
+
 constexpr bool kDirectStores = true;   // growth convs (32 couts) store their rows straight from the accumulators (lane-pair swap: 16 contiguous bytes per lane)
 constexpr int NCOMP = 8, NLOAD = 4;    // compute waves (one stream row each) + loader waves (LDS-DMA issue only), one loader per SIMD
 
@@ -389,6 +412,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // that is in [0, 8).  Built where it is used (a few selects) rather than held in eight registers.  xscale (5 or 25 in this graph) is
     // exact in bf16: the host refuses anything that is not.
     auto xfold = [&](int h, float scale) {
+        asm volatile("" : "+s"(scale));       // converted where it is used: hoisted, the bf16 forms of both scales sat in five registers through the step loop
         const bf16_t xs_b = (bf16_t)scale;
         int j0 = 16 * h + px - 8 * q;
         asm volatile("" : "+v"(j0));          // not loop invariant as far as hipcc can tell: hoisted, the fragments were spilled to scratch
@@ -407,50 +431,81 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // fragments are requested at the first stage of the current row, as before.
     // (round 4, same-box A/B/A of the tail at 7056 patches: s_setprio 2 on the compute waves 1186.7 against 1186.6 / 1183.2 TFLOP/s, WDEPTH 4 1180.8, one
     //  sched_barrier per two stages 1181.2: nothing moves it -- profiles/r04_dense_variants_ab.txt)
-    constexpr int WDEPTH = 3, NWREG = WDEPTH + 1;
+    constexpr int WDEPTH = 3, NWQ = 6;
+    // One CONTINUOUS pipeline per compute wave.  The pixel and weight fragment registers belong to the wave, not to a granule: in its last WDEPTH stages a
+    // granule requests the first WDEPTH weight fragments of the NEXT granule from the next weight slot (into the entries its own last stages have just freed),
+    // and at the first stage of its last input row the next granule's row 0 (into the half of xr that row does not use) -- where the source is already
+    // published and is not rewritten during the following iteration (CarryPlan).  The first MFMAs behind the barrier then find their operands in
+    // registers; restarted per granule, all eight compute waves issued 48 ds_read_b128 at the same moment behind every barrier with nothing to hide them
+    // (tools/micro/mfma_ceiling.hip modes 9-14 price the difference).  Nothing is carried across an epilogue or the bias re-initialisation: those sections
+    // need their own temporaries and the ring rows they write must be complete, so the pipeline restarts behind them as before.
+    // wq is indexed by stage modulo NWQ (four entries are live at any time); every granule's stage count is a multiple of NWQ, so a stage uses the same
+    // entry whichever granule it follows.
+    bf16x8 xr[2][3], wq[NWQ];
+    constexpr bool CARRY = kCarry<MODE> && !STAMP;      // (the stamped diagnostic build restarts per granule: its stamps need the registers)
     // one (chunk, kx) granule on an external chunk staged at `sb`: staged row j holds stream row 8s-2+j; layer 0 (row 8s+w) reads
     // j = w+1+ky, layer 1 (row 8s+w-1) reads j = w+ky.  Stage order: row d = 0..3: [layer 0, ky = d-1 (d >= 1)] [layer 1, ky = d (d <= 2)]
-    struct ExtStage { int d, layer, n, frag, first; };
+    // (stage k uses weight fragment k: chain_pack_weights packs a granule in stage order, so a granule's first fragments are its first stages')
+    struct ExtStage { int d, layer, n, first; };
     auto ext_stage = [](int k) constexpr -> ExtStage {
         int i = 0;
         for (int d = 0; d < 4; ++d) {
             bool first = true;
             if (d >= 1)
                 for (int n = 0; n < NB0; ++n, ++i, first = false)
-                    if (i == k) return ExtStage{d, 0, n, (d - 1) * NB0 + n, first};
+                    if (i == k) return ExtStage{d, 0, n, first};
             if (d <= 2)
                 for (int n = 0; n < NB1; ++n, ++i, first = false)
-                    if (i == k) return ExtStage{d, 1, n, 3 * NB0 + d * NB1 + n, first};
+                    if (i == k) return ExtStage{d, 1, n, first};
         }
-        return ExtStage{-1, 0, 0, 0, 0};
+        return ExtStage{-1, 0, 0, 0};
     };
-    constexpr int NEXTST = 3 * (NB0 + NB1);
-    auto ext_granule = [&](auto KXc, auto FOLDc, const char* sb, const char* ws) {
+    constexpr int NEXTST = 3 * (NB0 + NB1), NRINGST = 3 * NB1;
+    static_assert(NEXTST % NWQ == 0 && NRINGST % NWQ == 0 && WDEPTH < NWQ, "a stage's wq entry must not depend on the granule in front of it");
+    // the three column-group fragments of tap KX of the row whose LDS image starts at `row`
+    auto load_row = [&](auto KXc, const char* row, bf16x8 (&x)[3]) {
         constexpr int KX = decltype(KXc)::value;
-        constexpr int FOLD = KX == 1 ? decltype(FOLDc)::value : -1;      // the centre tap carries the skip
-        const char* rb = sb + wave * ROWB;
-        auto load_row = [&](int d, bf16x8 (&x)[3]) {
 #pragma unroll
-            for (int cg = 0; cg < 3; ++cg) {
-                const int off = (KX == 0 && cg == 0) ? off_l : (KX == 2 && cg == 2) ? off_r : offk[KX];
-                x[cg] = *reinterpret_cast<const bf16x8*>(rb + d * ROWB + cg * 1024 + off);
-                if ((KX == 0 && cg == 0 && edge_l) || (KX == 2 && cg == 2 && edge_r)) x[cg] = bf16x8{};
-                if (SEAM && cg == 1 && ((KX == 0 && seam_l) || (KX == 2 && seam_r))) x[cg] = bf16x8{};
-            }
-        };
-        auto ldw = [&](int frag) { return *reinterpret_cast<const bf16x8*>(ws + frag * 1024 + lane * 16); };
-        bf16x8 xr[2][3], wq[NWREG];
-        load_row(0, xr[0]);
-        static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(ext_stage(decltype(K)::value).frag); });
+        for (int cg = 0; cg < 3; ++cg) {
+            const int off = (KX == 0 && cg == 0) ? off_l : (KX == 2 && cg == 2) ? off_r : offk[KX];
+            x[cg] = *reinterpret_cast<const bf16x8*>(row + cg * 1024 + off);
+            if ((KX == 0 && cg == 0 && edge_l) || (KX == 2 && cg == 2 && edge_r)) x[cg] = bf16x8{};
+            if (SEAM && cg == 1 && ((KX == 0 && seam_l) || (KX == 2 && seam_r))) x[cg] = bf16x8{};
+        }
+    };
+    // this lane's 16 bytes of fragment `frag` of the slot whose lane address is wl.  wlane() keeps that address ONE register with the fragment in the
+    // instruction's offset: with a step's granules unrolled the slot numbers are constants, and hipcc otherwise materialises an address per fragment
+    // (LDS addresses above 64 KiB do not fit the offset field) and spills them.
+    typedef const __attribute__((address_space(3))) char* lds_cptr;
+    auto wlane = [&](const char* ws) {
+        lds_cptr wl = (lds_cptr)(ws + lane * 16);      // (an LDS pointer: through the asm a generic one would come back as a 64-bit flat address)
+        asm volatile("" : "+v"(wl));
+        return wl;
+    };
+    auto ldw = [&](lds_cptr wl, int frag) { return *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(wl + frag * 1024); };
+    // external granule I = 3 * chunk + kx of a step on the chunk staged at `sb`, weights in slot `ws`; `sbn` / `wsn`: staging buffer and weight slot of granule I + 1
+    auto ext_granule = [&](auto Ic, auto FOLDc, const char* sb, const char* sbn, const char* ws, const char* wsn) {
+        constexpr int I = decltype(Ic)::value, KX = I % 3;
+        constexpr int FOLD = KX == 1 ? decltype(FOLDc)::value : -1;      // the centre tap carries the skip
+        using CP = CarryPlan<EXT, MODE, CARRY>;
+        constexpr bool IN_W = CP::ext_w(I), IN_X = CP::ext_x(I), OUT_W = CP::ext_w(I + 1) && I + 1 < EXTG, OUT_X = CP::ext_x(I + 1) && I + 1 < EXTG;
+        const char* rb = sb + wave * ROWB;
+        const lds_cptr wl = wlane(ws);
+        lds_cptr wln = nullptr;
+        if constexpr (!IN_X) load_row(std::integral_constant<int, KX>{}, rb, xr[0]);
+        if constexpr (!IN_W) static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(wl, decltype(K)::value); });
         static_for<NEXTST>([&](auto K) {
             constexpr int k = decltype(K)::value;
             constexpr ExtStage st = ext_stage(k);
-            if constexpr (st.first && st.d < 3) load_row(st.d + 1, xr[(st.d + 1) & 1]);       // next row's fragments fly under this row's MFMAs
-            if constexpr (k + WDEPTH < NEXTST) wq[(k + WDEPTH) % NWREG] = ldw(ext_stage(k + WDEPTH).frag);
+            if constexpr (st.first && st.d < 3) load_row(std::integral_constant<int, KX>{}, rb + (st.d + 1) * ROWB, xr[(st.d + 1) & 1]);       // next row's fragments fly under this row's MFMAs
+            if constexpr (st.first && st.d == 3 && OUT_X) load_row(std::integral_constant<int, (KX + 1) % 3>{}, sbn + wave * ROWB, xr[0]);   // ... and the next granule's row 0 under the last row's
+            if constexpr (k + WDEPTH == NEXTST && OUT_W) wln = wlane(wsn);
+            if constexpr (k + WDEPTH < NEXTST) wq[(k + WDEPTH) % NWQ] = ldw(wl, k + WDEPTH);
+            else if constexpr (OUT_W) wq[(k + WDEPTH) % NWQ] = ldw(wln, k + WDEPTH - NEXTST);
 #pragma unroll
             for (int cg = 0; cg < 3; ++cg) {
-                if constexpr (st.layer == 0) a0[st.n][cg] = mma16(wq[k % NWREG], xr[st.d & 1][cg], a0[st.n][cg]);
-                else a1[st.n][cg] = mma16(wq[k % NWREG], xr[st.d & 1][cg], a1[st.n][cg]);
+                if constexpr (st.layer == 0) a0[st.n][cg] = mma16(wq[k % NWQ], xr[st.d & 1][cg], a0[st.n][cg]);
+                else a1[st.n][cg] = mma16(wq[k % NWQ], xr[st.d & 1][cg], a1[st.n][cg]);
             }
             // The block's own input x (channels [0, 64) = chunks 0, 1) is layer 1's skip: xscale * x(centre pixel) joins the accumulators of
             // cout blocks 2 FOLD, 2 FOLD + 1 as one more "tap" whose weight fragments are xscale times the identity (xfold[], built in
@@ -468,81 +523,86 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
         });
     };
     // one kx granule of layer 1 on layer 0's output: ring rows r1-1, r1, r1+1 with r1 = 8s+w-1
-    constexpr int NRINGST = 3 * NB1;
-    auto ring_granule = [&](auto KXc, int s, const char* ws) {
-        constexpr int KX = decltype(KXc)::value;
-        auto load_row = [&](int ky, bf16x8 (&x)[3]) {
-            const char* rb = win + ((8 * s + wave - 2 + ky + 2 * WINR) % WINR) * ROWB;
-#pragma unroll
-            for (int cg = 0; cg < 3; ++cg) {
-                const int off = (KX == 0 && cg == 0) ? off_l : (KX == 2 && cg == 2) ? off_r : offk[KX];
-                x[cg] = *reinterpret_cast<const bf16x8*>(rb + cg * 1024 + off);
-                if ((KX == 0 && cg == 0 && edge_l) || (KX == 2 && cg == 2 && edge_r)) x[cg] = bf16x8{};
-                if (SEAM && cg == 1 && ((KX == 0 && seam_l) || (KX == 2 && seam_r))) x[cg] = bf16x8{};
-            }
-        };
-        auto ldw = [&](int frag) { return *reinterpret_cast<const bf16x8*>(ws + frag * 1024 + lane * 16); };
-        bf16x8 xr[2][3], wq[NWREG];
-        load_row(0, xr[0]);
-        static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(decltype(K)::value); });
+    // A ring granule has three rows: row ky sits in xr[(ky + XP) & 1] with XP = 1 for kx = 1, so that the row 0 its predecessor requested lies in the half
+    // the predecessor's last row did not use.
+    auto ring_granule = [&](auto KXc, int s, const char* ws, const char* wsn) {
+        constexpr int KX = decltype(KXc)::value, XP = KX == 1 ? 1 : 0;
+        using CP = CarryPlan<EXT, MODE, CARRY>;
+        constexpr bool IN_W = CP::ring_w(KX), IN_X = CP::ring_x(KX), OUT_W = KX < 2 && CP::ring_w(KX + 1), OUT_X = KX < 2 && CP::ring_x(KX + 1);
+        auto rowp = [&](int ky) { return win + ((8 * s + wave - 2 + ky + 2 * WINR) % WINR) * ROWB; };
+        const lds_cptr wl = wlane(ws);
+        lds_cptr wln = nullptr;
+        if constexpr (!IN_X) load_row(KXc, rowp(0), xr[XP]);
+        if constexpr (!IN_W) static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(wl, decltype(K)::value); });
         static_for<NRINGST>([&](auto K) {
             constexpr int k = decltype(K)::value;            // stage k: ky = k / NB1, cout block n = k % NB1, fragment k
             constexpr int ky = k / NB1, n = k % NB1;
-            if constexpr (n == 0 && ky < 2) load_row(ky + 1, xr[(ky + 1) & 1]);
-            if constexpr (k + WDEPTH < NRINGST) wq[(k + WDEPTH) % NWREG] = ldw(k + WDEPTH);
+            if constexpr (n == 0 && ky < 2) load_row(KXc, rowp(ky + 1), xr[(ky + 1 + XP) & 1]);
+            if constexpr (n == 0 && ky == 2 && OUT_X) load_row(std::integral_constant<int, (KX + 1) % 3>{}, rowp(0), xr[XP ^ 1]);
+            if constexpr (k + WDEPTH == NRINGST && OUT_W) wln = wlane(wsn);
+            if constexpr (k + WDEPTH < NRINGST) wq[(k + WDEPTH) % NWQ] = ldw(wl, k + WDEPTH);
+            else if constexpr (OUT_W) wq[(k + WDEPTH) % NWQ] = ldw(wln, k + WDEPTH - NRINGST);
 #pragma unroll
-            for (int cg = 0; cg < 3; ++cg) a1[n][cg] = mma16(wq[k % NWREG], xr[ky & 1][cg], a1[n][cg]);
+            for (int cg = 0; cg < 3; ++cg) a1[n][cg] = mma16(wq[k % NWQ], xr[(ky + XP) & 1][cg], a1[n][cg]);
             __builtin_amdgcn_sched_barrier(0);
         });
     };
     // Granule boundary of a compute wave: its LDS reads / writes of the finished granule are done, then the barrier that publishes the
-    // loaders' pieces.  No vmcnt here: a compute wave issues no DMA, and its epilogue stores drain on their own.
-    auto sync = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // loaders' pieces.  No vmcnt here: a compute wave issues no DMA, and its epilogue stores drain on their own.  NPRE: the pre-reads of the
+    // next granule's operands that stay in flight across the barrier -- a wave's LDS operations return in order, so all but the NPRE youngest
+    // being done means every read of the finished granule is.  Behind an epilogue NPRE = 0: the ring writes must be complete.
+    auto sync = [&](auto NPREc) {
+        asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(decltype(NPREc)::value) : "memory");
         __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
     };
 
     int nch = 0;
-    auto chunk = [&](auto FOLDc, int& Gr) {
+    auto chunk = [&](auto Cc, auto FOLDc) {
+        constexpr int C = decltype(Cc)::value;
         const char* sb = stg + (nch % NSB) * STGB;
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx, ++Gr) {
+        const char* sbn = stg + ((nch + 1) % NSB) * STGB;
+        static_for<3>([&](auto KXc) {
+            constexpr int KX = decltype(KXc)::value, I = 3 * C + KX;
+            using CP = CarryPlan<EXT, MODE, CARRY>;
             CHAIN_STAMP(0);
-            sync();
+            sync(std::integral_constant<int, (CP::ext_w(I) ? WDEPTH : 0) + (CP::ext_x(I) ? 3 : 0)>{});
             CHAIN_STAMP(1);
             CHAIN_STAMP(2);
-            const char* ws = wr + (Gr % NWS) * WSLOT;
-            if (STAMP && (p.dbg_flags & 2)) { /* timing experiment: loaders alone */ }
-            else if (kx == 0) ext_granule(std::integral_constant<int, 0>{}, FOLDc, sb, ws);
-            else if (kx == 1) ext_granule(std::integral_constant<int, 1>{}, FOLDc, sb, ws);
-            else ext_granule(std::integral_constant<int, 2>{}, FOLDc, sb, ws);
+            ext_granule(std::integral_constant<int, I>{}, FOLDc, sb, KX == 2 ? sbn : sb, wr + (G % NWS) * WSLOT, wr + ((G + 1) % NWS) * WSLOT);
             CHAIN_STAMP(3);
-        }
+            ++G;
+        });
         ++nch;
     };
     for (int s = 0; s < nsteps; ++s) {
-        // accumulators start at the bias (the epilogues then have no bias add)
+        // accumulators start at the bias (the epilogues then have no bias add); one address register made here, not one per cout block held through the step loop
+        lds_cptr lb = (lds_cptr)(reinterpret_cast<const char*>(lbias) + 16 * q);
+        asm volatile("" : "+v"(lb));
 #pragma unroll
         for (int n = 0; n < NB0; ++n) {
-            const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + n * 16 + 4 * q);
+            const f32x4 b = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lb + n * 64);
 #pragma unroll
             for (int cg = 0; cg < 3; ++cg) a0[n][cg] = b;
         }
 #pragma unroll
         for (int n = 0; n < NB1; ++n) {
-            const f32x4 b = *reinterpret_cast<const f32x4*>(lbias + (NB0 + n) * 16 + 4 * q);
+            const f32x4 b = *reinterpret_cast<const __attribute__((address_space(3))) f32x4*>(lb + (NB0 + n) * 64);
 #pragma unroll
             for (int cg = 0; cg < 3; ++cg) a1[n][cg] = b;
         }
-        if constexpr (MODE == 1) {
-            static_assert(MODE == 0 || EXT >= 2, "the tail's skip spans chunks 0 and 1");
-            chunk(std::integral_constant<int, 0>{}, G);
-            chunk(std::integral_constant<int, 1>{}, G);
+        static_assert(MODE == 0 || EXT >= 2, "the tail's skip spans chunks 0 and 1");
+        if constexpr (CARRY) {
+            // every external granule of the step is its own code: what it finds in registers and what it requests for its successor depend on its position
+            static_for<EXT>([&](auto Cc) { chunk(Cc, std::integral_constant<int, (MODE == 1 && decltype(Cc)::value < 2) ? decltype(Cc)::value : -1>{}); });
+        } else if constexpr (MODE == 1) {
+            chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            chunk(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
 #pragma nounroll
-            for (int c = 2; c < EXT; ++c) chunk(std::integral_constant<int, -1>{}, G);
+            for (int c = 2; c < EXT; ++c) chunk(std::integral_constant<int, 2>{}, std::integral_constant<int, -1>{});
         } else {
 #pragma nounroll
-            for (int c = 0; c < EXT; ++c) chunk(std::integral_constant<int, -1>{}, G);
+            for (int c = 0; c < EXT; ++c) chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{});
         }
         // ---- layer 0 epilogue: ReLU -> bf16 -> ring row (8s+w) mod 10 (zeros on separator / out-of-stream rows)
         {
@@ -611,16 +671,18 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx, ++G) {
             CHAIN_STAMP(0);
-            sync();
+            if (kx == 0 || !CARRY) sync(std::integral_constant<int, 0>{});
+            else sync(std::integral_constant<int, WDEPTH + 3>{});
             CHAIN_STAMP(1);
             // behind the barrier, every wave: the slots sit in the staging buffer of the last external chunk, which other waves read until
             // they have passed the barrier of the first ring granule
             so_fetch(kx);
             CHAIN_STAMP(2);
             const char* ws = wr + (G % NWS) * WSLOT;
-            if (kx == 0) ring_granule(std::integral_constant<int, 0>{}, s, ws);
-            else if (kx == 1) ring_granule(std::integral_constant<int, 1>{}, s, ws);
-            else ring_granule(std::integral_constant<int, 2>{}, s, ws);
+            const char* wsn = wr + ((G + 1) % NWS) * WSLOT;
+            if (kx == 0) ring_granule(std::integral_constant<int, 0>{}, s, ws, wsn);
+            else if (kx == 1) ring_granule(std::integral_constant<int, 1>{}, s, ws, wsn);
+            else ring_granule(std::integral_constant<int, 2>{}, s, ws, wsn);
             if (MODE == 1 && HAS_O && sob) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // this wave's own two pieces (and its long-finished output stores)
                 int l = lane;
@@ -646,6 +708,8 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                 const float alpha = p.alpha;
                 int t_a, t_line;
                 transpose_offsets(t_a, t_line);
+                int l16 = lane * 16;                               // (made here: hoisted out of the step loop, the 64-bit store address p.out + 16 lane was spilled)
+                asm volatile("" : "+v"(l16));
                 if constexpr (MODE == 0 && NB1 == 2 && kDirectStores) {
 #pragma unroll
                     for (int cg = 0; cg < 3; ++cg) {
@@ -675,7 +739,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                         }
                         asm volatile("" ::: "memory");                 // the read-back below is of other lanes' writes: keep the order
                         const u32x4 line = *reinterpret_cast<const u32x4*>(slot + t_line);
-                        __builtin_nontemporal_store(line, reinterpret_cast<u32x4*>(grow + h * ROWB + cg * 1024 + lane * 16));
+                        __builtin_nontemporal_store(line, reinterpret_cast<u32x4*>(grow + h * ROWB + cg * 1024 + l16));
                     }
             }
         }
@@ -890,9 +954,11 @@ int launch_chain(sr_ctx* ctx, const ChainParams& p, bool has_o, int nwg, bool se
 // host side
 // ------------------------------------------------------------------------------------------------------------------------------
 // Weights of the pair (conv_a: Cin_a = 32*ext -> 16*nb0 couts, conv_b: Cin_b = 32*(ext+1) -> 16*nb1 couts), HWIO fp32, packed in
-// the order the kernel consumes them: for each external chunk c and kx: [a: ky x cout block][b: ky x cout block] (1 KiB MFMA
+// the order the kernel's stages consume them, so that stage k of a granule uses its fragment k: for each external chunk c and kx, row by row of
+// the four staged rows a wave walks: [b: ky 0][a: ky 0][b: ky 1][a: ky 1][b: ky 2][a: ky 2], every cout block of a conv in turn (1 KiB MFMA
 // A-fragments, lane l element j = W[ky][kx][32c + 8(l>>4) + j][16 blk + (l&15)]), then for conv_b's last chunk (= conv_a's
-// output) and kx: [b: ky x cout block].
+// output) and kx: [b: ky x cout block].  A granule's first eight fragments are the pieces the tail's loaders keep in registers and write a
+// granule early: the compute waves request the first three before the barrier that opens the granule.
 int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const float* wb, const float* bb, int ext, int nb0, int nb1, ChainWeights* out) {
     const int cin_a = 32 * ext, cin_b = 32 * (ext + 1), cout_a = 16 * nb0, cout_b = 16 * nb1;
     const size_t nfrag = (size_t)3 * ext * 3 * (nb0 + nb1) + (size_t)3 * 3 * nb1;
@@ -904,10 +970,11 @@ int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const floa
                 host[idx++] = f32_to_bf16_host(w[((size_t)(ky * 3 + kx) * cin + 32 * c + 8 * (l >> 4) + j) * cout + 16 * blk + (l & 15)]);
     };
     for (int c = 0; c < ext; ++c)
-        for (int kx = 0; kx < 3; ++kx) {
-            for (int ky = 0; ky < 3; ++ky) for (int n = 0; n < nb0; ++n) frag(wa, cin_a, cout_a, c, ky, kx, n);
-            for (int ky = 0; ky < 3; ++ky) for (int n = 0; n < nb1; ++n) frag(wb, cin_b, cout_b, c, ky, kx, n);
-        }
+        for (int kx = 0; kx < 3; ++kx)
+            for (int d = 0; d < 4; ++d) {                 // staged row d of a wave's four: conv_a's ky = d - 1, conv_b's ky = d (ext_stage in chain2_kernel)
+                if (d >= 1) for (int n = 0; n < nb0; ++n) frag(wa, cin_a, cout_a, c, d - 1, kx, n);
+                if (d <= 2) for (int n = 0; n < nb1; ++n) frag(wb, cin_b, cout_b, c, d, kx, n);
+            }
     for (int kx = 0; kx < 3; ++kx)
         for (int ky = 0; ky < 3; ++ky) for (int n = 0; n < nb1; ++n) frag(wb, cin_b, cout_b, ext, ky, kx, n);
     ChainWeights cw;

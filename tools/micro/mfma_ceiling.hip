@@ -9,12 +9,19 @@
 //   mode 6 / 7 (round 4): the same flops on v_mfma_f32_32x32x16_bf16 -- a 32-cout x 32-pixel tile per instruction, HALF the operand bytes (registers and LDS) per flop:
 //           four compute waves (one per SIMD), nine 32 x 32 accumulator tiles each (conv4 + conv5 of two image rows); 6 = bare, 7 = 30 LDS reads per 54 MFMAs + the
 //           loaders' 29 KiB of LDS-DMA + one barrier per granule (what mode 2 is to the kernels as they are, this is to a kernel rebuilt on 32 x 32 tiles)
+//   modes 9-14: what the post-barrier pipeline restart of the fused kernels' granule lambdas costs, on one generic stage list (NST stages of one weight fragment x three column
+//           groups, the next row's pixel fragments requested at a row's first stage, weight fragments three stages ahead, loader volume scaled with the granule):
+//           14 = mode 2 restated on that list (54 MFMAs per granule, the pipeline CONTINUOUS across the barrier: the last three stages request the next granule's
+//           first three weight fragments, the last row's first stage the next granule's row 0), 9 = the same with the pipeline RESTARTED per granule as the kernels
+//           do it (no reads in the last three stages, three weight + three pixel reads right behind the barrier); 10 / 11 = continuous / restarted at 36 MFMAs
+//           per granule, 12 / 13 = at 18 (the growth pairs' external and ring granules)
 // One workgroup per CU (150 KiB of LDS), 8 compute waves (two per SIMD).  Each configuration runs back to back for ~2 s before it is timed;
 // the in-kernel clock is s_memtime / s_memrealtime (100 MHz) over the timed launch.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -32,8 +39,24 @@ struct P {
     int iters;                // granules (54 MFMAs per compute wave each)
 };
 
-template <int MODE>
-__global__ void __launch_bounds__((MODE == 2 || MODE == 4 || MODE == 5 || MODE == 8) ? 768 : (MODE == 6 ? 256 : 512)) k(P p) {
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// generic stage list (modes 9-14): rows of a granule of NST stages and the stage each row starts at
+template <int NST> struct Rows {
+    static constexpr int n = NST == 6 ? 3 : 4;
+    static constexpr int start(int r) { return NST == 18 ? (r == 0 ? 0 : r == 1 ? 4 : r == 2 ? 10 : 16) : NST == 12 ? (r == 0 ? 0 : r == 1 ? 2 : r == 2 ? 6 : 10) : 2 * r; }
+    static constexpr int row(int s) { int r = 0; for (int i = 1; i < n; ++i) if (s >= start(i)) r = i; return r; }
+    static constexpr int npiece = NST == 18 ? 7 : NST == 12 ? 5 : 3;      // loader pieces per loader wave and granule
+    static constexpr int nhbm = NST == 18 ? 3 : NST == 12 ? 2 : 1;        // ... of them from the private HBM stream
+};
+
+template <int MODE, int NST = 18, bool RESTART = false>
+__global__ void __launch_bounds__((MODE == 2 || MODE == 4 || MODE == 5 || MODE >= 8) ? 768 : (MODE == 6 ? 256 : 512)) k(P p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -113,6 +136,67 @@ __global__ void __launch_bounds__((MODE == 2 || MODE == 4 || MODE == 5 || MODE =
 #pragma unroll
         for (int j = 0; j < 36; ++j) sum += acc[j][0] + acc[j][3];
         if (sum == 12345.678f) p.sink[0] = sum;
+    } else if (MODE >= 9 && wave < 8) {
+        using R = Rows<NST>;
+        constexpr int NXB = R::n % 2 ? 3 : 2, NW = 6;           // NST and the row count are multiples: the register a stage reads is the same in every granule
+        f32x4 acc[18];
+#pragma unroll
+        for (int j = 0; j < 18; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const char* base = smem + wave * 4096 + lane * 16;
+        bf16x8 w[NW], x[NXB][3];
+        auto ldw = [&](int s, int it) { return *reinterpret_cast<const bf16x8*>(base + (((s + it) & 31) << 10)); };
+        auto ldx = [&](int s, int j, int it) { return *reinterpret_cast<const bf16x8*>(base + 24576 + (((s + j + it) & 7) << 10)); };
+        if (!RESTART) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) { w[j] = ldw(j, 0); x[0][j] = ldx(0, j, 0); }
+        }
+        for (int it = 0; it < p.iters; ++it) {
+            if (RESTART) {
+                // as ext_granule / ring_granule today: row 0 and the first three weight fragments right behind the barrier, by every wave at once
+#pragma unroll
+                for (int j = 0; j < 3; ++j) x[0][j] = ldx(0, j, it);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) w[j] = ldw(j, it);
+            }
+            static_for<NST>([&](auto S) {
+                constexpr int s = decltype(S)::value, r = R::row(s);
+                if constexpr (R::start(r) == s && (r + 1 < R::n || !RESTART)) {
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) x[((r + 1) % R::n) % NXB][j] = ldx(s + 1, j, it);
+                }
+                if constexpr (s + 3 < NST || !RESTART) w[(s + 3) % NW] = ldw(s + 3, it);
+#pragma unroll
+                for (int cg = 0; cg < 3; ++cg) acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[s % NW], x[r % NXB][cg], acc[s], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < 18; ++j) sum += acc[j][0] + acc[j][3];
+        if (sum == 12345.678f) p.sink[0] = sum;
+    } else if (MODE >= 9) {
+        // loaders of the generic modes: mode 2's stream scaled with the granule
+        using R = Rows<NST>;
+        const int lw = wave - 8;
+        const char* gh = p.hbm + (size_t)blockIdx.x * p.per_wg + (size_t)lw * (p.per_wg / 4) + lane * 16;
+        const char* gl = p.rnd + lane * 16;
+        unsigned slot = lw;
+        const size_t hmask = p.per_wg / 4 - 1;
+        size_t ho = 0;
+        for (int it = 0; it < p.iters; ++it) {
+#pragma unroll
+            for (int j = 0; j < R::npiece; ++j) {
+                char* dst = smem + 65536 + ((slot & 63u) << 10);
+                slot += 4;
+                if (j < R::nhbm) { __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gh + (ho & hmask)), (__attribute__((address_space(3))) void*)dst, 16, 0, 2); ho += 1024; }
+                else __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gl + (((it * 7 + j) & 63) << 10)), (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(R::npiece) : "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else if (MODE != 3 && MODE != 6 && MODE != 7 && wave < 8) {
         f32x4 acc[18];
 #pragma unroll
@@ -241,14 +325,24 @@ int main() {
                            "mode 2 with two barriers per granule and waves 4-7 half a granule behind their SIMD partners (stagger)",
                            "bare v_mfma_f32_32x32x16_bf16, 4 waves (one per SIMD) x nine 32x32 tiles, operands in registers",
                            "32x32x16 MFMAs, 4 compute waves: 30 ds_read_b128 per 54 MFMAs (half of mode 2's per flop) + 29 KiB of LDS-DMA + one barrier per granule",
-                           "mode 2 with 22 LDS reads per granule and 72 v_mov_b32_dpp making the kx-shifted pixel fragments in registers"};
+                           "mode 2 with 22 LDS reads per granule and 72 v_mov_b32_dpp making the kx-shifted pixel fragments in registers",
+                           "generic stage list, 54 MFMAs per granule, pipeline RESTARTED behind every barrier (no reads in the last 3 stages, 6 reads behind the barrier)",
+                           "generic stage list, 36 MFMAs per granule, pipeline continuous across the barrier",
+                           "generic stage list, 36 MFMAs per granule, pipeline RESTARTED behind every barrier",
+                           "generic stage list, 18 MFMAs per granule, pipeline continuous across the barrier",
+                           "generic stage list, 18 MFMAs per granule, pipeline RESTARTED behind every barrier",
+                           "generic stage list, 54 MFMAs per granule, pipeline continuous across the barrier (mode 2 restated)"};
+    const int nst_of[] = {18, 18, 18, 18, 18, 18, 18, 18, 18, 18, 12, 12, 6, 6, 18};
     const int only = getenv("MFMA_MODE") ? atoi(getenv("MFMA_MODE")) : -1;
-    for (int mode = 0; mode < 9; ++mode) {
+    const int first = getenv("MFMA_MODE_FIRST") ? atoi(getenv("MFMA_MODE_FIRST")) : 0;
+    for (int mode = first; mode < 15; ++mode) {
         if (only >= 0 && mode != only) continue;
-        auto kern = mode == 0 ? k<0> : mode == 1 ? k<1> : mode == 2 ? k<2> : mode == 3 ? k<3> : mode == 4 ? k<4> : mode == 5 ? k<5> : mode == 6 ? k<6> : mode == 7 ? k<7> : k<8>;
+        auto kern = mode == 0 ? k<0> : mode == 1 ? k<1> : mode == 2 ? k<2> : mode == 3 ? k<3> : mode == 4 ? k<4> : mode == 5 ? k<5> : mode == 6 ? k<6> : mode == 7 ? k<7> : mode == 8 ? k<8>
+                  : mode == 9 ? k<9, 18, true> : mode == 10 ? k<10, 12, false> : mode == 11 ? k<11, 12, true> : mode == 12 ? k<12, 6, false> : mode == 13 ? k<13, 6, true> : k<14, 18, false>;
         CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        P p{rnd, hbm, per_wg, stamps, sink, 20000};
-        const int threads = (mode == 2 || mode == 4 || mode == 5 || mode == 8) ? 768 : (mode == 6 ? 256 : 512);      // modes 3, 7: 4 compute + 4 loader waves
+        const int nst = nst_of[mode];
+        P p{rnd, hbm, per_wg, stamps, sink, 20000 * 18 / nst};      // the same MFMA count in every mode
+        const int threads = (mode == 2 || mode == 4 || mode == 5 || mode >= 8) ? 768 : (mode == 6 ? 256 : 512);      // modes 3, 7: 4 compute + 4 loader waves
         float ms = 0.f, total = 0.f;
         int n = 0;
         while (total < 2500.f && n < 400) {             // ~2.5 s of back-to-back launches, the last one is the measurement
@@ -267,8 +361,8 @@ int main() {
             if (dr > 0) { clk.push_back(dt / dr * 100.0); cyc.push_back(dt); }
         }
         std::sort(clk.begin(), clk.end()); std::sort(cyc.begin(), cyc.end());
-        const double flop = (double)ncu * 8 * 54.0 * p.iters * 16 * 16 * 32 * 2;      // mode 3: 4 waves x 108 MFMAs = the same
-        const double mfma_per_simd = 2.0 * 54.0 * p.iters;      // in units of 16-cycle MFMAs (modes 6, 7: one wave per SIMD, 54 32-cycle MFMAs)
+        const double flop = (double)ncu * 8 * 3.0 * nst * p.iters * 16 * 16 * 32 * 2;      // mode 3: 4 waves x 108 MFMAs = the same
+        const double mfma_per_simd = 2.0 * 3.0 * nst * p.iters;      // in units of 16-cycle MFMAs (modes 6, 7: one wave per SIMD, 54 32-cycle MFMAs)
         printf("mode %d (%s): %.3f ms, %.1f TFLOP/s, in-kernel clock %.0f MHz (median), %.2f cycles per MFMA per SIMD, pipe utilisation %.3f, %d launches\n", mode, names[mode], ms,
                flop / ms / 1e9, clk[clk.size() / 2], cyc[cyc.size() / 2] / mfma_per_simd, 16.0 * mfma_per_simd / cyc[cyc.size() / 2], n);
         fflush(stdout);
