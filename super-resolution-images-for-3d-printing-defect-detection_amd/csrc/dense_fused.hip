@@ -44,8 +44,11 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "dense_plan.h"
 
 namespace {
+
+using namespace dense_plan;      // the schedule: geometry, LDS budgets, the loaders' piece lists and counted waits, the carry plan, the stage lists
 
 struct ChainParams {
     const char* in; int in_nch;        // source concat buffer (row-blocked bf16), 32-channel chunks per pixel
@@ -63,28 +66,8 @@ struct ChainParams {
 
 __device__ __forceinline__ f32x4 mma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
-constexpr int ROWB = 3072;             // one LDS / HBM row of a chunk: 48 pixels x 64 B
-constexpr int NSTG = 11;               // staged rows per chunk: stream rows [8s-2, 8s+9)
-constexpr int STGB = NSTG * ROWB;
-constexpr int WINR = 10;               // ring rows of layer 0's output: [8s-2, 8s+8)
-constexpr int ZERO_PAGE_BYTES = sr_ctx::ZERO_PAGE_BYTES;
-
-template <int NB0, int NB1, int MODE> struct ChainLds {
-    static constexpr int WSLOT = (NB0 + NB1) * 3 * 1024;
-    // Tail: two staging buffers (next chunk's rows fly during this chunk), three weight slots (the loaders' DMA runs two granules
-    // ahead).  Growth pairs: their weights are register-resident in the loader waves (ds_write, one granule ahead: two slots), which
-    // frees the room for a THIRD staging buffer -- rows are requested two chunks ahead, so a row piece has a whole chunk (~7 k
-    // cycles) more than HBM's latency to land before anybody waits for it.
-    static constexpr int NSB = MODE == 0 ? 3 : 2;
-    static constexpr int NWS = MODE == 0 ? 2 : 3;
-    static constexpr int BYTES = NSB * STGB + WINR * ROWB + NWS * WSLOT + (NB0 + NB1) * 16 * 4;
-};
-
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// EXT: external 32-channel chunks both convs read; NB0 / NB1: 16-cout blocks of layer 0 / layer 1.
-// MODE 0: both layers are growth convs (ReLU) whose outputs go to chunks EXT and EXT+1 of the source buffer.
-// MODE 1: layer 0 is a growth conv kept on chip only, layer 1 is the block tail (NB1 = 4).
 #define CHAIN_STAMP(k) do { if (STAMP && blockIdx.x < 64 && G < 64 && (wave == 0 || wave == 5 || wave == 8 || wave == 11) && lane == 0)                \
         p.dbg[(((size_t)blockIdx.x * 4 + (wave == 0 ? 0 : wave == 5 ? 1 : wave == 8 ? 2 : 3)) * 64 + G) * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
 
@@ -101,55 +84,33 @@ template <int N> __device__ __forceinline__ void wait_imm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// What loader wave LW issues where, as compile-time functions of the granule position in a step (chain2_kernel's loader section).
-template <int EXT, int NB0, int NB1, int MODE, int LW> struct LoaderPlan {
-    static constexpr int NBT = NB0 + NB1, EXTG = 3 * EXT, NGR = 3 * (EXT + 1);
-    static constexpr int RT_E = MODE == 1 ? 2 : 3;      // resident pieces per loader of an external granule's ceil(3 NBT / 4) = 5 (tail) / 3 (growth pair)
-    static constexpr int RT_R = 2;                      // ... of a ring granule's ceil(3 NB1 / 4) = 3 / 2
-    // rows of a chunk requested in the chunk's granule kx: {LW, LW + 4} | {8 + LW} (LW < 3) | {}
-    static constexpr int nrows(int kx) { return kx == 0 ? 2 : kx == 1 ? (LW < 3 ? 1 : 0) : 0; }
-    // row pieces requested at granule position i of a step (any integer: the pattern repeats every step)
-    static constexpr int nst_at(int i) {
-        i = (i % NGR + NGR) % NGR;
-        return i < EXTG ? 3 * nrows(i % 3) : 0;
-    }
-    // weight pieces fetched by DMA (the non-resident ones) for the granule at position iw
-    static constexpr int nwdma(int iw) {
-        const bool ext = iw < EXTG;
-        const int nw = ext ? NBT * 3 : NB1 * 3, rt = ext ? RT_E : RT_R;
-        int n = 0;
-        for (int t = 0; t < (nw + 3) / 4; ++t)
-            if (LW + 4 * t < nw && t >= rt) ++n;
-        return n;
-    }
-};
+// LDS-DMA source swizzle: lane i of a 1 KiB piece fills LDS slot i -> pixel i/4, slice position i%4, which must hold global slice (i%4) ^ 2*bit2(pixel)
+// (a macro: as a function, inlined later than the lane arithmetic around it, it changes conv1_stream_kernel's instruction stream)
+#define DMA_SRC_SWIZZLE(lane) (64 * ((lane) >> 2) + 16 * (((lane) & 3) ^ (2 * (((lane) >> 4) & 1))))
 
-// (the same for the tail's 64 couts -- two 32-channel chunks of the row-blocked destination -- measured 0.3-0.5 % on the tail, inside the noise: the
-// transposition through LDS stays there)
-// Which operands of a granule its predecessor has already requested (chain2_kernel's compute waves, "one continuous pipeline").  Weights: the first WDEPTH
-// fragments, from the next weight slot.  Pixels: row 0 of the next granule -- only where that row is already published and is not rewritten during the
-// following iteration:
-//   kx -> kx + 1 inside an external chunk: the same staging buffer; ring kx 0 -> 1 -> 2: the same ring rows;
-//   chunk c -> c + 1: growth pairs only (three staging buffers, rows published a chunk early); the tail's next chunk is published by the very barrier in between;
-//   never into a step's first granule or into ring kx = 0 (behind the bias re-initialisation / the layer-0 epilogue that has just written the ring row).
-// tests/test_operand_prefetch_schedule_cpu.py restates this and replays it against the loaders' schedule.
-template <int EXT, int MODE, bool CARRY> struct CarryPlan {
-    static constexpr bool ext_w(int i) { return CARRY && i > 0 && i < 3 * EXT; }                      // external granule i = 3 * chunk + kx of a step
-    static constexpr bool ext_x(int i) { return ext_w(i) && (i % 3 != 0 || MODE == 0); }
-    static constexpr bool ring_w(int kx) { return CARRY && kx > 0 && kx < 3; }
-    static constexpr bool ring_x(int kx) { return ring_w(kx); }
-};
-// MODE 1 (tail): carried.  MODE 0 (growth pairs): not carried -- their weight slot of granule G + 1 is written during granule G (two slots, one granule
-// ahead); the first fragments would need a three-buffer ring of their own, and the skeleton shows nothing to gain at their granule sizes.
-template <int MODE> constexpr bool kCarry = MODE == 1;
+// one staged row = three 1 KiB pieces from ONE address (immediate offsets 0 / 1024 / 2048 on both the global and the LDS side); POLICY: the cache
+// policy bits of the load (0: default, 2: nt)
+template <int POLICY> __device__ __forceinline__ void stage_row_pieces(const char* src, char* dst) {
+    const auto gs = (const __attribute__((address_space(1))) void*)src;
+    const auto ld = (__attribute__((address_space(3))) void*)dst;
+    __builtin_amdgcn_global_load_lds(gs, ld, 16, 0, POLICY);
+    __builtin_amdgcn_global_load_lds(gs, ld, 16, 1024, POLICY);
+    __builtin_amdgcn_global_load_lds(gs, ld, 16, 2048, POLICY);
+}
 
-constexpr bool kDirectStores = true;   // growth convs (32 couts) store their rows straight from the accumulators (lane-pair swap: 16 contiguous bytes per lane)
-constexpr int NCOMP = 8, NLOAD = 4;    // compute waves (one stream row each) + loader waves (LDS-DMA issue only), one loader per SIMD
+// 32 couts (a growth conv) of 16 pixels straight from the accumulators: `lo` / `hi` are this lane's four channels of cout blocks 0 / 1; lanes q, q ^ 1
+// trade halves and every lane stores 16 contiguous bytes at `dst` = the column group's KiB + 64 px + 2 ((q & 1) 16 + 4 (q & ~1)), a column group one
+// contiguous KiB -- no read-back through LDS.  (The same for the tail's 64 couts -- two 32-channel chunks of the row-blocked destination -- measured
+// 0.3-0.5 % on the tail, inside the noise: the transposition through LDS stays there.)
+__device__ __forceinline__ void store_32couts(char* dst, bf16x4 lo, bf16x4 hi) {
+    const u32x2 au = __builtin_bit_cast(u32x2, lo), cu = __builtin_bit_cast(u32x2, hi);
+    const auto s0 = __builtin_amdgcn_permlane16_swap(au[0], cu[0], false, false);
+    const auto s1 = __builtin_amdgcn_permlane16_swap(au[1], cu[1], false, false);
+    const u32x4 ov = {(unsigned)s0[0], (unsigned)s1[0], (unsigned)s0[1], (unsigned)s1[1]};
+    __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(dst));
+}
 
-// EXT: external 32-channel chunks both convs read; NB0 / NB1: 16-cout blocks of layer 0 / layer 1.
-// MODE 0: both layers are growth convs (ReLU) whose outputs go to chunks EXT and EXT+1 of the source buffer.
-// MODE 1: layer 0 is a growth conv kept on chip only, layer 1 is the block tail (NB1 = 4).
-//
+// EXT, NB0, NB1, MODE: the shape of the pair, see dense_plan.h.
 // Roles.  Four loader waves own the whole DMA stream and run two granules ahead (three weight slots, counted vmcnt): barrier -> issue ->
 // wait for what the next barrier publishes -> barrier; the eight compute waves go barrier -> MFMAs -> barrier and touch vector memory only
 // in the epilogues (and for the RRDB skip's two pieces per ring granule).  Round 2 read its stamps (200-300 cycles per DMA issue, the same
@@ -184,7 +145,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // whole number of images: 882 patches on 256 CUs used to mean four images for 221 workgroups and none for 35 (what a rank sees at N = 8).
     // The range may start and end inside an image, so the local stream begins one row early (layer 0 recomputes row R0 - 1 for layer 1's
     // first own row) and ends one row late (layer 0's row R1 for layer 1's last); those two rows are computed, never stored -- the
-    // neighbouring workgroups own and store them, with the same values.
+    // neighbouring workgroups own and store them, with the same values.  (The host splits the stream: split_row_stream.)
     const int T = p.B * Hp1;                           // global stream rows
     const int R0 = blockIdx.x * p.rows_per_wg, R1 = min(T, R0 + p.rows_per_wg);
     if (R0 >= R1) return;                              // whole workgroup (uniform)
@@ -228,51 +189,31 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
         //     s_waitcnt count are immediates; out-of-stream rows and the weights "after the last step" are issued all the same
         //     (zero page / valid memory, nobody reads them), so the counts never depend on the position in the stream.
         const int lwr = wave - NCOMP;
-        // LDS-DMA source swizzle: lane i of a 1 KiB piece fills LDS slot i -> pixel i/4, slice position i%4, which must hold global slice
-        // (i%4) ^ 2*bit2(pixel)
-        const int lsrc = 64 * (lane >> 2) + 16 * ((lane & 3) ^ (2 * ((lane >> 4) & 1)));
+        const int lsrc = DMA_SRC_SWIZZLE(lane);
         auto loader = [&](auto LWc) {
             constexpr int LW = decltype(LWc)::value;
+            using Plan = LoaderPlan<EXT, NB0, NB1, MODE, LW>;
             // base address of staged row j of step s2 (stream row 8 s2 - 2 + j), chunk 0, this lane's slice
             auto row_base = [&](int s2, int j) -> const char* {
                 int img, y;
                 const bool real = row_of(8 * s2 - 2 + j, img, y);
                 return real ? p.in + ((int64_t)img * H + y) * p.in_nch * ROWB : p.zero;
             };
-            // rows of a chunk this loader requests in the chunk's granule kx: {LW, LW + 4} | {8 + LW} (LW < 3) | {}
-            using Plan = LoaderPlan<EXT, NB0, NB1, MODE, LW>;
+            // the rows of a chunk this loader requests (Plan::row: two in the chunk's granule kx = 0, at most one in kx = 1): rb[2 kx + r]
             const char* rb_cur[3];
             const char* rb_nxt[3];
             auto bases_of = [&](int s2, const char* (&rb)[3]) {
-                rb[0] = row_base(s2, LW);
-                rb[1] = row_base(s2, LW + 4);
-                rb[2] = row_base(s2, 8 + (LW < 3 ? LW : 2));
+                rb[0] = row_base(s2, Plan::row(0, 0));
+                rb[1] = row_base(s2, Plan::row(0, 1));
+                rb[2] = row_base(s2, Plan::nrows(1) ? Plan::row(1, 0) : NSTG - 1);      // (a loader without a third row keeps a valid address nobody uses)
             };
             // one staged row = three pieces; rows 0..7 of a step are read by no later step (nt), rows 8..10 are the next step's halo
-            auto stage_row = [&](auto Jc, const char* rb, int c1, char* sdst) {
-                constexpr int j = decltype(Jc)::value;
-                const char* src = rb + c1 * ROWB + lsrc;
-                char* dst = sdst + j * ROWB;
-                const auto gs = (const __attribute__((address_space(1))) void*)src;
-                const auto ld = (__attribute__((address_space(3))) void*)dst;
-                if constexpr (j < 8) {
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 0, 2);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 1024, 2);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 2048, 2);
-                } else {
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 0, 0);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 1024, 0);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 2048, 0);
-                }
-            };
             auto stage_rows = [&](auto KXc, const char* (&rb)[3], int c1, char* sdst) {
                 constexpr int kx = decltype(KXc)::value;
-                if constexpr (kx == 0) {
-                    stage_row(std::integral_constant<int, LW>{}, rb[0], c1, sdst);
-                    stage_row(std::integral_constant<int, LW + 4>{}, rb[1], c1, sdst);
-                } else if constexpr (kx == 1 && LW < 3) {
-                    stage_row(std::integral_constant<int, 8 + (LW < 3 ? LW : 0)>{}, rb[2], c1, sdst);
-                }
+                static_for<Plan::nrows(kx)>([&](auto Rc) {
+                    constexpr int r = decltype(Rc)::value, j = Plan::row(kx, r);
+                    stage_row_pieces<(j < 8 ? 2 : 0)>(rb[2 * kx + r] + c1 * ROWB + lsrc, sdst + j * ROWB);
+                });
             };
             // Resident weights.  Every 8-row step re-reads ALL weights: 54 of a tail chunk's 87 pieces.  A loader wave needs few registers
             // and owns 168, so each keeps the first RT_E (RT_R) of its pieces of every external (ring) granule in registers for the whole
@@ -285,26 +226,26 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
             for (int iw = 0; iw < EXTG; ++iw)
 #pragma unroll
                 for (int t = 0; t < RT_E; ++t)
-                    if (LW + 4 * t < NBT * 3) wre[iw][t] = *reinterpret_cast<const u32x4*>(wsrc_of(iw) + (LW + 4 * t) * 1024 + lane * 16);
+                    if (LW + 4 * t < Plan::npieces(iw)) wre[iw][t] = *reinterpret_cast<const u32x4*>(wsrc_of(iw) + (LW + 4 * t) * 1024 + lane * 16);
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int t = 0; t < RT_R; ++t)
-                    if (LW + 4 * t < NB1 * 3) wrr[r][t] = *reinterpret_cast<const u32x4*>(wsrc_of(EXTG + r) + (LW + 4 * t) * 1024 + lane * 16);
+                    if (LW + 4 * t < Plan::npieces(EXTG + r)) wrr[r][t] = *reinterpret_cast<const u32x4*>(wsrc_of(EXTG + r) + (LW + 4 * t) * 1024 + lane * 16);
             // weights of the granule at position IW of a step (running number Gw) -> slot Gw % NWS
             auto put_weights = [&](auto IW, int Gw) {
                 constexpr int iw = decltype(IW)::value;
                 constexpr bool ext = iw < EXTG;
-                constexpr int nw = ext ? NBT * 3 : NB1 * 3, rt = ext ? RT_E : RT_R;
+                constexpr int nw = Plan::npieces(iw);
                 const char* wq = p.w;
                 asm volatile("" : "+s"(wq));                                 // recompute the piece addresses here: hoisted out of the step loop they cost two registers each
                 const char* wsrc = wq + (ext ? iw * WSLOT : EXTG * WSLOT + (iw - EXTG) * (NB1 * 3 * 1024)) + lane * 16;
                 char* wdst = wr + (Gw % NWS) * WSLOT;
 #pragma unroll
-                for (int t = 0; t < (nw + 3) / 4; ++t) {
-                    const int k = LW + 4 * t;
+                for (int t = 0; t < (nw + NLOAD - 1) / NLOAD; ++t) {
+                    const int k = LW + NLOAD * t;
                     if (k < nw) {
-                        if (t < rt) {
+                        if (Plan::resident(iw, k)) {
                             if constexpr (ext) *reinterpret_cast<u32x4*>(wdst + k * 1024 + lane * 16) = wre[ext ? iw : 0][t < RT_E ? t : 0];
                             else *reinterpret_cast<u32x4*>(wdst + k * 1024 + lane * 16) = wrr[ext ? 0 : iw - EXTG][t < RT_R ? t : 0];
                         } else {
@@ -314,10 +255,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                 }
             };
             // prologue: weights of the first WL granules, the first SL external chunks of step 0; all of it is waited for before the first barrier
-            constexpr int WL = NWS - 1;                                      // weights run WL granules ahead
-            constexpr int SL = NSB - 1;                                      // rows run SL chunks ahead
-            static_assert(MODE == 1 || (RT_E * NLOAD >= NBT * 3 && RT_R * NLOAD >= NB1 * 3), "growth pairs: every weight piece is resident (no weight DMA in the counted waits)");
-            static_assert(SL <= EXT, "rows run at most one step ahead");
+            constexpr int WL = Plan::WL, SL = Plan::SL;                      // weights run WL granules ahead, rows SL chunks
             static_for<WL>([&](auto I) { put_weights(I, decltype(I)::value); });
             bases_of(0, rb_cur);
             bases_of(1, rb_nxt);
@@ -336,12 +274,9 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the resident pieces written in the previous iteration
                     __builtin_amdgcn_s_barrier();
                     CHAIN_STAMP(1);
-                    constexpr int i2 = (i + WL) % NGR;                       // granule G+WL
-                    // Order of issue: weights of granule G+WL, then this granule's rows.  vmcnt retires in order.  The barrier that ends this
-                    // iteration publishes the weights of granule G+1 (issued first in the PREVIOUS iteration) and, after a chunk's third granule,
-                    // all of the next chunk's rows (issued in its first two).  Tail: leave in flight this iteration's pieces and -- except in a
-                    // third granule -- the previous iteration's rows (younger than its weights).  Growth pairs (no weight DMA, rows two
-                    // chunks ahead): everything older than three iterations has landed.
+                    constexpr int i2 = Plan::issue_w(i);                     // granule G+WL
+                    // Order of issue: weights of granule G+WL, then this granule's rows; then the counted wait for what the barrier that ends this
+                    // iteration publishes (Plan::wait_n).
                     put_weights(std::integral_constant<int, i2>{}, G + WL);
                     if constexpr (i < EXTG) {
                         constexpr int c = i / 3, kx = i - 3 * c;
@@ -352,12 +287,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                         if (kx == 2) ++nch;
                     }
                     CHAIN_STAMP(2);
-                    if constexpr (MODE == 0) {
-                        wait_imm<Plan::nst_at(i) + Plan::nst_at(i - 1) + Plan::nst_at(i - 2)>();
-                    } else {
-                        constexpr bool third = i < EXTG && i % 3 == 2;
-                        wait_imm<Plan::nwdma(i2) + Plan::nst_at(i) + (third ? 0 : Plan::nst_at(i - 1))>();
-                    }
+                    wait_imm<Plan::wait_n(i)>();
                     CHAIN_STAMP(3);
                     ++G;
                 });
@@ -386,6 +316,17 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     const int off_l = edge_l ? offk[1] : offk[0];      // ... and read from a valid address
     const int off_r = edge_r ? offk[1] : offk[2];
     const bool seam_l = SEAM && px == 8, seam_r = SEAM && px == 7;      // column group 1: column 24's left neighbour / column 23's right neighbour belong to the other image
+    // the three column-group fragments of tap KX of the row whose LDS image starts at `row`
+    auto load_row = [&](auto KXc, const char* row, bf16x8 (&x)[3]) {
+        constexpr int KX = decltype(KXc)::value;
+#pragma unroll
+        for (int cg = 0; cg < 3; ++cg) {
+            const int off = (KX == 0 && cg == 0) ? off_l : (KX == 2 && cg == 2) ? off_r : offk[KX];
+            x[cg] = *reinterpret_cast<const bf16x8*>(row + cg * 1024 + off);
+            if ((KX == 0 && cg == 0 && edge_l) || (KX == 2 && cg == 2 && edge_r)) x[cg] = bf16x8{};
+            if (SEAM && cg == 1 && ((KX == 0 && seam_l) || (KX == 2 && seam_r))) x[cg] = bf16x8{};
+        }
+    };
 
     f32x4 a0[NB0][3], a1[NB1][3];
 
@@ -431,7 +372,6 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // fragments are requested at the first stage of the current row, as before.
     // (round 4, same-box A/B/A of the tail at 7056 patches: s_setprio 2 on the compute waves 1186.7 against 1186.6 / 1183.2 TFLOP/s, WDEPTH 4 1180.8, one
     //  sched_barrier per two stages 1181.2: nothing moves it -- profiles/r04_dense_variants_ab.txt)
-    constexpr int WDEPTH = 3, NWQ = 6;
     // One CONTINUOUS pipeline per compute wave.  The pixel and weight fragment registers belong to the wave, not to a granule: in its last WDEPTH stages a
     // granule requests the first WDEPTH weight fragments of the NEXT granule from the next weight slot (into the entries its own last stages have just freed),
     // and at the first stage of its last input row the next granule's row 0 (into the half of xr that row does not use) -- where the source is already
@@ -443,36 +383,12 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // entry whichever granule it follows.
     bf16x8 xr[2][3], wq[NWQ];
     constexpr bool CARRY = kCarry<MODE> && !STAMP;      // (the stamped diagnostic build restarts per granule: its stamps need the registers)
+    using CP = CarryPlan<EXT, MODE, CARRY>;
     // one (chunk, kx) granule on an external chunk staged at `sb`: staged row j holds stream row 8s-2+j; layer 0 (row 8s+w) reads
-    // j = w+1+ky, layer 1 (row 8s+w-1) reads j = w+ky.  Stage order: row d = 0..3: [layer 0, ky = d-1 (d >= 1)] [layer 1, ky = d (d <= 2)]
-    // (stage k uses weight fragment k: chain_pack_weights packs a granule in stage order, so a granule's first fragments are its first stages')
-    struct ExtStage { int d, layer, n, first; };
-    auto ext_stage = [](int k) constexpr -> ExtStage {
-        int i = 0;
-        for (int d = 0; d < 4; ++d) {
-            bool first = true;
-            if (d >= 1)
-                for (int n = 0; n < NB0; ++n, ++i, first = false)
-                    if (i == k) return ExtStage{d, 0, n, first};
-            if (d <= 2)
-                for (int n = 0; n < NB1; ++n, ++i, first = false)
-                    if (i == k) return ExtStage{d, 1, n, first};
-        }
-        return ExtStage{-1, 0, 0, 0};
-    };
-    constexpr int NEXTST = 3 * (NB0 + NB1), NRINGST = 3 * NB1;
-    static_assert(NEXTST % NWQ == 0 && NRINGST % NWQ == 0 && WDEPTH < NWQ, "a stage's wq entry must not depend on the granule in front of it");
-    // the three column-group fragments of tap KX of the row whose LDS image starts at `row`
-    auto load_row = [&](auto KXc, const char* row, bf16x8 (&x)[3]) {
-        constexpr int KX = decltype(KXc)::value;
-#pragma unroll
-        for (int cg = 0; cg < 3; ++cg) {
-            const int off = (KX == 0 && cg == 0) ? off_l : (KX == 2 && cg == 2) ? off_r : offk[KX];
-            x[cg] = *reinterpret_cast<const bf16x8*>(row + cg * 1024 + off);
-            if ((KX == 0 && cg == 0 && edge_l) || (KX == 2 && cg == 2 && edge_r)) x[cg] = bf16x8{};
-            if (SEAM && cg == 1 && ((KX == 0 && seam_l) || (KX == 2 && seam_r))) x[cg] = bf16x8{};
-        }
-    };
+    // j = w+1+ky, layer 1 (row 8s+w-1) reads j = w+ky.  Stage order: ext_stage (dense_plan.h) -- stage k uses weight fragment k, and
+    // chain_pack_weights packs by the same list, so a granule's first fragments are its first stages'.
+    constexpr int NEXTST = ext_stages(NB0, NB1), NRINGST = ring_stages(NB1);
+    static_assert(NEXTST % NWQ == 0 && NRINGST % NWQ == 0, "a stage's wq entry must not depend on the granule in front of it");
     // this lane's 16 bytes of fragment `frag` of the slot whose lane address is wl.  wlane() keeps that address ONE register with the fragment in the
     // instruction's offset: with a step's granules unrolled the slot numbers are constants, and hipcc otherwise materialises an address per fragment
     // (LDS addresses above 64 KiB do not fit the offset field) and spills them.
@@ -487,8 +403,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     auto ext_granule = [&](auto Ic, auto FOLDc, const char* sb, const char* sbn, const char* ws, const char* wsn) {
         constexpr int I = decltype(Ic)::value, KX = I % 3;
         constexpr int FOLD = KX == 1 ? decltype(FOLDc)::value : -1;      // the centre tap carries the skip
-        using CP = CarryPlan<EXT, MODE, CARRY>;
-        constexpr bool IN_W = CP::ext_w(I), IN_X = CP::ext_x(I), OUT_W = CP::ext_w(I + 1) && I + 1 < EXTG, OUT_X = CP::ext_x(I + 1) && I + 1 < EXTG;
+        constexpr bool IN_W = CP::pre_w(I), IN_X = CP::pre_x(I), OUT_W = I + 1 < EXTG && CP::pre_w(I + 1), OUT_X = I + 1 < EXTG && CP::pre_x(I + 1);
         const char* rb = sb + wave * ROWB;
         const lds_cptr wl = wlane(ws);
         lds_cptr wln = nullptr;
@@ -496,7 +411,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
         if constexpr (!IN_W) static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(wl, decltype(K)::value); });
         static_for<NEXTST>([&](auto K) {
             constexpr int k = decltype(K)::value;
-            constexpr ExtStage st = ext_stage(k);
+            constexpr ExtStage st = ext_stage(NB0, NB1, k);
             if constexpr (st.first && st.d < 3) load_row(std::integral_constant<int, KX>{}, rb + (st.d + 1) * ROWB, xr[(st.d + 1) & 1]);       // next row's fragments fly under this row's MFMAs
             if constexpr (st.first && st.d == 3 && OUT_X) load_row(std::integral_constant<int, (KX + 1) % 3>{}, sbn + wave * ROWB, xr[0]);   // ... and the next granule's row 0 under the last row's
             if constexpr (k + WDEPTH == NEXTST && OUT_W) wln = wlane(wsn);
@@ -527,17 +442,16 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     // the predecessor's last row did not use.
     auto ring_granule = [&](auto KXc, int s, const char* ws, const char* wsn) {
         constexpr int KX = decltype(KXc)::value, XP = KX == 1 ? 1 : 0;
-        using CP = CarryPlan<EXT, MODE, CARRY>;
-        constexpr bool IN_W = CP::ring_w(KX), IN_X = CP::ring_x(KX), OUT_W = KX < 2 && CP::ring_w(KX + 1), OUT_X = KX < 2 && CP::ring_x(KX + 1);
+        constexpr bool IN_W = CP::pre_w(EXTG + KX), IN_X = CP::pre_x(EXTG + KX), OUT_W = CP::pre_w(EXTG + KX + 1), OUT_X = CP::pre_x(EXTG + KX + 1);
         auto rowp = [&](int ky) { return win + ((8 * s + wave - 2 + ky + 2 * WINR) % WINR) * ROWB; };
         const lds_cptr wl = wlane(ws);
         lds_cptr wln = nullptr;
-        if constexpr (!IN_X) load_row(KXc, rowp(0), xr[XP]);
+        if constexpr (!IN_X) load_row(std::integral_constant<int, KX>{}, rowp(0), xr[XP]);
         if constexpr (!IN_W) static_for<WDEPTH>([&](auto K) { wq[decltype(K)::value] = ldw(wl, decltype(K)::value); });
         static_for<NRINGST>([&](auto K) {
-            constexpr int k = decltype(K)::value;            // stage k: ky = k / NB1, cout block n = k % NB1, fragment k
-            constexpr int ky = k / NB1, n = k % NB1;
-            if constexpr (n == 0 && ky < 2) load_row(KXc, rowp(ky + 1), xr[(ky + 1 + XP) & 1]);
+            constexpr int k = decltype(K)::value;            // stage k uses fragment k
+            constexpr int ky = ring_stage(NB1, k).ky, n = ring_stage(NB1, k).n;
+            if constexpr (n == 0 && ky < 2) load_row(std::integral_constant<int, KX>{}, rowp(ky + 1), xr[(ky + 1 + XP) & 1]);
             if constexpr (n == 0 && ky == 2 && OUT_X) load_row(std::integral_constant<int, (KX + 1) % 3>{}, rowp(0), xr[XP ^ 1]);
             if constexpr (k + WDEPTH == NRINGST && OUT_W) wln = wlane(wsn);
             if constexpr (k + WDEPTH < NRINGST) wq[(k + WDEPTH) % NWQ] = ldw(wl, k + WDEPTH);
@@ -564,9 +478,8 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
         const char* sbn = stg + ((nch + 1) % NSB) * STGB;
         static_for<3>([&](auto KXc) {
             constexpr int KX = decltype(KXc)::value, I = 3 * C + KX;
-            using CP = CarryPlan<EXT, MODE, CARRY>;
             CHAIN_STAMP(0);
-            sync(std::integral_constant<int, (CP::ext_w(I) ? WDEPTH : 0) + (CP::ext_x(I) ? 3 : 0)>{});
+            sync(std::integral_constant<int, CP::npre(I)>{});
             CHAIN_STAMP(1);
             CHAIN_STAMP(2);
             ext_granule(std::integral_constant<int, I>{}, FOLDc, sb, KX == 2 ? sbn : sb, wr + (G % NWS) * WSLOT, wr + ((G + 1) % NWS) * WSLOT);
@@ -624,26 +537,9 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                     const int slice = n * 2 + (q >> 1);
                     *reinterpret_cast<bf16x4*>(wrow + cg * 1024 + 64 * px + 16 * (slice ^ (2 * ((px >> 2) & 1))) + (q & 1) * 8) = o;
                 }
-                if constexpr (MODE == 0 && NB0 == 2 && kDirectStores) {
-                    // 32 couts: lanes q, q ^ 1 trade halves and every lane stores 16 contiguous bytes, a column group one contiguous KiB -- no read-back of the ring row
-                    if (grow) {
-                        const u32x2 au = __builtin_bit_cast(u32x2, ob[0]), cu = __builtin_bit_cast(u32x2, ob[NB0 - 1]);
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(au[0], cu[0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(au[1], cu[1], false, false);
-                        const u32x4 ov = {(unsigned)s0[0], (unsigned)s1[0], (unsigned)s0[1], (unsigned)s1[1]};
-                        __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(grow + cg * 1024 + 64 * px + 2 * ((q & 1) * 16 + 4 * (q & ~1))));
-                    }
-                }
-            }
-            if (MODE == 0 && grow && !(NB0 == 2 && kDirectStores)) {
-                // the ring row just written IS the row's memory image (64 B per pixel, slices swizzled by 2 * bit2(pixel)): read it back in
-                // lane order and store whole lines
-                static_assert(MODE == 1 || NB0 == 2, "growth convs have 32 output channels");
-                asm volatile("" ::: "memory");
-#pragma unroll
-                for (int cg = 0; cg < 3; ++cg) {
-                    const u32x4 v = *reinterpret_cast<const u32x4*>(wrow + cg * 1024 + (lane >> 2) * 64 + 16 * ((lane & 3) ^ (2 * ((lane >> 4) & 1))));
-                    __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(grow + cg * 1024 + lane * 16));
+                if constexpr (MODE == 0) {
+                    static_assert(NB0 == 2, "growth convs have 32 output channels");
+                    if (grow) store_32couts(grow + cg * 1024 + 64 * px + 2 * ((q & 1) * 16 + 4 * (q & ~1)), ob[0], ob[1]);
                 }
             }
         }
@@ -662,7 +558,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
             if (MODE == 1 && HAS_O && sob) {
                 int l = lane;
                 asm volatile("" : "+v"(l));
-                const int ls = 64 * (l >> 2) + 16 * ((l & 3) ^ (2 * ((l >> 4) & 1)));      // the loaders' source swizzle
+                const int ls = DMA_SRC_SWIZZLE(l);
                 dma(sob + cg * 1024 + ls, tb);
                 dma(sob + ROWB + cg * 1024 + ls, tb + 1024);
             }
@@ -671,8 +567,9 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx, ++G) {
             CHAIN_STAMP(0);
-            if (kx == 0 || !CARRY) sync(std::integral_constant<int, 0>{});
-            else sync(std::integral_constant<int, WDEPTH + 3>{});
+            static_assert(CP::npre(EXTG) == 0 && CP::npre(EXTG + 1) == CP::npre(EXTG + 2), "ring kx = 1 and 2 wait alike");
+            if (kx == 0 || CP::npre(EXTG + 1) == 0) sync(std::integral_constant<int, 0>{});
+            else sync(std::integral_constant<int, CP::npre(EXTG + 1)>{});
             CHAIN_STAMP(1);
             // behind the barrier, every wave: the slots sit in the staging buffer of the last external chunk, which other waves read until
             // they have passed the barrier of the first ring granule
@@ -698,7 +595,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
             }
             CHAIN_STAMP(3);
         }
-        // ---- layer 1 epilogue (row 8s+w-1): ReLU | * alpha -> bf16 -> transposition slot -> whole-line stores
+        // ---- layer 1 epilogue (row 8s+w-1): growth conv: ReLU -> bf16 -> direct stores; tail: * alpha -> bf16 -> transposition slot -> whole-line stores
         {
             int img, y;
             const bool real = row_of(8 * s + wave - 1, img, y) && own(8 * s + wave - 1);
@@ -710,18 +607,15 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                 transpose_offsets(t_a, t_line);
                 int l16 = lane * 16;                               // (made here: hoisted out of the step loop, the 64-bit store address p.out + 16 lane was spilled)
                 asm volatile("" : "+v"(l16));
-                if constexpr (MODE == 0 && NB1 == 2 && kDirectStores) {
+                if constexpr (MODE == 0) {
+                    static_assert(NB1 == 2, "growth convs have 32 output channels");
 #pragma unroll
                     for (int cg = 0; cg < 3; ++cg) {
                         bf16x4 ob[2];
 #pragma unroll
                         for (int n = 0; n < 2; ++n)
                             ob[n] = bf16x4{(bf16_t)fmaxf(a1[n][cg][0], 0.f), (bf16_t)fmaxf(a1[n][cg][1], 0.f), (bf16_t)fmaxf(a1[n][cg][2], 0.f), (bf16_t)fmaxf(a1[n][cg][3], 0.f)};
-                        const u32x2 au = __builtin_bit_cast(u32x2, ob[0]), cu = __builtin_bit_cast(u32x2, ob[1]);
-                        const auto s0 = __builtin_amdgcn_permlane16_swap(au[0], cu[0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane16_swap(au[1], cu[1], false, false);
-                        const u32x4 ov = {(unsigned)s0[0], (unsigned)s1[0], (unsigned)s0[1], (unsigned)s1[1]};
-                        __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(grow + cg * 1024 + 64 * px + 2 * ((q & 1) * 16 + 4 * (q & ~1))));
+                        store_32couts(grow + cg * 1024 + 64 * px + 2 * ((q & 1) * 16 + 4 * (q & ~1)), ob[0], ob[1]);
                     }
                 } else
 #pragma unroll
@@ -734,7 +628,7 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
                             const int n = 2 * h + u;
                             f32x4 v;
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) v[e] = MODE == 0 ? fmaxf(a1[n][cg][e], 0.f) : alpha * a1[n][cg][e];
+                            for (int e = 0; e < 4; ++e) v[e] = alpha * a1[n][cg][e];
                             *reinterpret_cast<bf16x4*>(slot + (t_a ^ (32 * u))) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
                         }
                         asm volatile("" ::: "memory");                 // the read-back below is of other lanes' writes: keep the order
@@ -765,11 +659,6 @@ struct Conv1Params {
     int rows_per_wg; unsigned magic;
 };
 
-constexpr int C1_NSTG = 10;            // staged rows per chunk and step: stream rows [8s - 1, 8s + 9)
-constexpr int C1_STGB = C1_NSTG * ROWB;
-constexpr int C1_NSB = 4;
-constexpr int C1_WBYTES = 2 * 9 * 2 * 1024;
-constexpr int C1_LDS = C1_NSB * C1_STGB + C1_WBYTES + 32 * 4;
 static_assert(C1_LDS <= 160 * 1024, "LDS budget");
 
 template <bool SEAM>
@@ -801,37 +690,31 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     };
     if (wave >= NCOMP) {
         // ------------------------------------------------------------------------------------------------ loader waves
-        // unit k = (step k / 2, chunk k % 2) goes to buffer k % 4.  Loader LW stages rows LW, LW + 4 and (LW < 2) 8 + LW of every unit: three
-        // 1 KiB pieces per row from one address.  Schedule per barrier k (the barrier that lets the compute waves start unit k): issue unit
-        // k + 3 (its buffer was released by the barrier before: unit k - 1 is done), then wait until unit k + 1 has landed = all but this
-        // loader's pieces of units k + 2 and k + 3.
+        // unit k = (step k / 2, chunk k % 2) goes to buffer k % C1_NSB; which rows a loader stages, how far ahead and what it waits with:
+        // Conv1LoaderPlan (dense_plan.h)
         const int lwr = wave - NCOMP;
-        const int lsrc = 64 * (lane >> 2) + 16 * ((lane & 3) ^ (2 * ((lane >> 4) & 1)));
+        const int lsrc = DMA_SRC_SWIZZLE(lane);
         auto loader = [&](auto LWc) {
-            constexpr int LW = decltype(LWc)::value;
-            constexpr int NROWS = LW < 2 ? 3 : 2, NP = 3 * NROWS;
+            using Plan = Conv1LoaderPlan<decltype(LWc)::value>;
             auto stage_unit = [&](int k) {                         // every unit is issued, also those past the end (zero page: nobody reads them)
                 const int s2 = k >> 1, c = k & 1;
                 char* const sdst = stg + (k % C1_NSB) * C1_STGB;
-                static_for<NROWS>([&](auto Jc) {
-                    constexpr int j = decltype(Jc)::value == 0 ? LW : decltype(Jc)::value == 1 ? LW + 4 : 8 + LW;
+                static_for<Plan::NROWS>([&](auto Rc) {
+                    constexpr int j = Plan::row(decltype(Rc)::value);
                     int img, y;
                     const bool real = k < nchunks && row_of(8 * s2 - 1 + j, img, y);
                     const char* src = (real ? p.in + (((int64_t)img * H + y) * p.in_nch + c) * ROWB : p.zero) + lsrc;
-                    const auto gs = (const __attribute__((address_space(1))) void*)src;
-                    const auto ld = (__attribute__((address_space(3))) void*)(sdst + j * ROWB);
                     // (the nt policy for the rows no later step re-reads, which keeps the fused pairs' halo rows in L2, measured 2 % slower here)
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 0, 0);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 1024, 0);
-                    __builtin_amdgcn_global_load_lds(gs, ld, 16, 2048, 0);
+                    stage_row_pieces<0>(src, sdst + j * ROWB);
                 });
             };
+            static_assert(Plan::AHEAD == 3, "the prologue below issues the first AHEAD units");
             stage_unit(0); stage_unit(1); stage_unit(2);
             for (int k = 0; k < nchunks; ++k) {
-                if (k == 0) wait_imm<2 * NP>();                    // unit 0 has landed (units 1, 2 may fly)
+                if (k == 0) wait_imm<Plan::WAIT>();                // unit 0 has landed (units 1, 2 may fly)
                 __builtin_amdgcn_s_barrier();                      // compute may start unit k; unit k - 1's buffer is free
-                stage_unit(k + 3);
-                wait_imm<2 * NP>();                                // unit k + 1 has landed
+                stage_unit(k + Plan::AHEAD);
+                wait_imm<Plan::WAIT>();                            // unit k + 1 has landed
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         };
@@ -854,7 +737,6 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
     const bool edge_l = px == 0, edge_r = px == 15;
     const int off_l = edge_l ? offk[1] : offk[0];
     const int off_r = edge_r ? offk[1] : offk[2];
-    typedef unsigned u32x2c __attribute__((ext_vector_type(2)));
     for (int s = 0; s < nsteps; ++s) {
         f32x4 acc[2][3];
         // (the biases were written before the first barrier below)
@@ -905,47 +787,34 @@ __global__ void __launch_bounds__((NCOMP + NLOAD) * 64, (NCOMP + NLOAD + 3) / 4)
 #pragma unroll
                 for (int n = 0; n < 2; ++n)
                     o[n] = bf16x4{(bf16_t)fmaxf(acc[n][cg][0], 0.f), (bf16_t)fmaxf(acc[n][cg][1], 0.f), (bf16_t)fmaxf(acc[n][cg][2], 0.f), (bf16_t)fmaxf(acc[n][cg][3], 0.f)};
-                const u32x2c au = __builtin_bit_cast(u32x2c, o[0]), cu = __builtin_bit_cast(u32x2c, o[1]);
-                const auto s0 = __builtin_amdgcn_permlane16_swap(au[0], cu[0], false, false);
-                const auto s1 = __builtin_amdgcn_permlane16_swap(au[1], cu[1], false, false);
-                const u32x4 ov = {(unsigned)s0[0], (unsigned)s1[0], (unsigned)s0[1], (unsigned)s1[1]};
-                __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(grow + cg * 1024 + lane_b));
+                store_32couts(grow + cg * 1024 + lane_b, o[0], o[1]);
             }
         }
     }
 }
 
-template <int EXT, int NB0, int NB1, int MODE>
-int launch_chain(sr_ctx* ctx, const ChainParams& p, bool has_o, int nwg, bool seam, hipStream_t st) {
-    constexpr int lds = ChainLds<NB0, NB1, MODE>::BYTES;
-    static_assert(lds <= 160 * 1024, "LDS budget");
-    if (seam) {                                   // two 24-pixel-wide images per row
-        if (has_o) {
-            auto k = chain2_kernel<EXT, NB0, NB1, MODE, true, false, true>;
-            if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
-            hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, p);
-        } else {
-            auto k = chain2_kernel<EXT, NB0, NB1, MODE, false, false, true>;
-            if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
-            hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, p);
-        }
-    } else if (p.dbg) {                                  // diagnostic stamped variant (never in production)
-        auto k = chain2_kernel<EXT, NB0, NB1, MODE, MODE == 1, true>;
-        if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
-        ChainParams q = p;
-        if (MODE == 1 && !has_o) { q.so = p.in; q.so_nch = p.in_nch; q.oscale = 0.f; }   // the stamped build always carries the skip loads
-        hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, q);
-    } else if (has_o) {
-        auto k = chain2_kernel<EXT, NB0, NB1, MODE, true, false>;
-        if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, p);
-    } else {
-        auto k = chain2_kernel<EXT, NB0, NB1, MODE, false, false>;
-        if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
-        hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, p);
-    }
+template <class K> int launch_chain_kernel(sr_ctx* ctx, K k, int lds, const ChainParams& p, int nwg, hipStream_t st) {
+    if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(k), lds)) return rc;
+    hipLaunchKernelGGL(k, dim3(nwg), dim3((NCOMP + NLOAD) * 64), lds, st, p);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
+}
+
+template <int EXT, int NB0, int NB1, int MODE>
+int launch_chain(sr_ctx* ctx, ChainParams p, bool has_o, int nwg, bool seam, hipStream_t st) {
+    constexpr int lds = ChainLds<NB0, NB1, MODE>::BYTES;
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    constexpr bool TAIL = MODE == 1;                     // HAS_O (the RRDB skip's loads) exists for the tail only
+    void (*k)(ChainParams);
+    if (p.dbg && !seam) {                                // diagnostic stamped variant (never in production)
+        k = chain2_kernel<EXT, NB0, NB1, MODE, TAIL, true>;
+        if (TAIL && !has_o) { p.so = p.in; p.so_nch = p.in_nch; p.oscale = 0.f; }        // the stamped build always carries the skip loads
+    } else if (TAIL && has_o) {
+        k = seam ? chain2_kernel<EXT, NB0, NB1, MODE, TAIL, false, true> : chain2_kernel<EXT, NB0, NB1, MODE, TAIL, false, false>;
+    } else {                                             // (seam: two 24-pixel-wide images per row)
+        k = seam ? chain2_kernel<EXT, NB0, NB1, MODE, false, false, true> : chain2_kernel<EXT, NB0, NB1, MODE, false, false, false>;
+    }
+    return launch_chain_kernel(ctx, k, lds, p, nwg, st);
 }
 
 }  // namespace
@@ -953,30 +822,23 @@ int launch_chain(sr_ctx* ctx, const ChainParams& p, bool has_o, int nwg, bool se
 // ------------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------------
-// Weights of the pair (conv_a: Cin_a = 32*ext -> 16*nb0 couts, conv_b: Cin_b = 32*(ext+1) -> 16*nb1 couts), HWIO fp32, packed in
-// the order the kernel's stages consume them, so that stage k of a granule uses its fragment k: for each external chunk c and kx, row by row of
-// the four staged rows a wave walks: [b: ky 0][a: ky 0][b: ky 1][a: ky 1][b: ky 2][a: ky 2], every cout block of a conv in turn (1 KiB MFMA
-// A-fragments, lane l element j = W[ky][kx][32c + 8(l>>4) + j][16 blk + (l&15)]), then for conv_b's last chunk (= conv_a's
-// output) and kx: [b: ky x cout block].  A granule's first eight fragments are the pieces the tail's loaders keep in registers and write a
-// granule early: the compute waves request the first three before the barrier that opens the granule.
+// Weights of the pair (conv_a: Cin_a = 32*ext -> 16*nb0 couts, conv_b: Cin_b = 32*(ext+1) -> 16*nb1 couts), HWIO fp32, packed in the order the
+// kernel's stages consume them: dense_plan::frag_at walks the kernel's own stage lists, so stage k of a granule uses its fragment k (1 KiB MFMA
+// A-fragments, lane l element j = W[ky][kx][32c + 8(l>>4) + j][16 blk + (l&15)]).  A granule's first eight fragments are the pieces the tail's
+// loaders keep in registers and write a granule early: the compute waves request the first three before the barrier that opens the granule.
 int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const float* wb, const float* bb, int ext, int nb0, int nb1, ChainWeights* out) {
     const int cin_a = 32 * ext, cin_b = 32 * (ext + 1), cout_a = 16 * nb0, cout_b = 16 * nb1;
-    const size_t nfrag = (size_t)3 * ext * 3 * (nb0 + nb1) + (size_t)3 * 3 * nb1;
-    std::vector<uint16_t> host(nfrag * 512);
+    const int nfrag = nfrags(ext, nb0, nb1);
+    std::vector<uint16_t> host((size_t)nfrag * 512);
     size_t idx = 0;
-    auto frag = [&](const float* w, int cin, int cout, int c, int ky, int kx, int blk) {
+    for (int f = 0; f < nfrag; ++f) {
+        const Frag fr = frag_at(ext, nb0, nb1, f);
+        const float* w = fr.conv == 0 ? wa : wb;
+        const int cin = fr.conv == 0 ? cin_a : cin_b, cout = fr.conv == 0 ? cout_a : cout_b;
         for (int l = 0; l < 64; ++l)
             for (int j = 0; j < 8; ++j)
-                host[idx++] = f32_to_bf16_host(w[((size_t)(ky * 3 + kx) * cin + 32 * c + 8 * (l >> 4) + j) * cout + 16 * blk + (l & 15)]);
-    };
-    for (int c = 0; c < ext; ++c)
-        for (int kx = 0; kx < 3; ++kx)
-            for (int d = 0; d < 4; ++d) {                 // staged row d of a wave's four: conv_a's ky = d - 1, conv_b's ky = d (ext_stage in chain2_kernel)
-                if (d >= 1) for (int n = 0; n < nb0; ++n) frag(wa, cin_a, cout_a, c, d - 1, kx, n);
-                if (d <= 2) for (int n = 0; n < nb1; ++n) frag(wb, cin_b, cout_b, c, d, kx, n);
-            }
-    for (int kx = 0; kx < 3; ++kx)
-        for (int ky = 0; ky < 3; ++ky) for (int n = 0; n < nb1; ++n) frag(wb, cin_b, cout_b, ext, ky, kx, n);
+                host[idx++] = f32_to_bf16_host(w[((size_t)(fr.ky * 3 + fr.kx) * cin + 32 * fr.chunk + 8 * (l >> 4) + j) * cout + 16 * fr.blk + (l & 15)]);
+    }
     ChainWeights cw;
     cw.ext = ext; cw.nb0 = nb0; cw.nb1 = nb1;
     cw.bytes = host.size() * 2;
@@ -985,6 +847,20 @@ int chain_pack_weights(sr_ctx* ctx, const float* wa, const float* ba, const floa
     if (bb) for (int i = 0; i < cout_b; ++i) hb[cout_a + i] = bb[i];
     if (int rc = weights_upload(ctx, host.data(), cw.bytes, hb.data(), (int)hb.size(), (int)hb.size(), &cw.w, &cw.bias)) return rc;
     *out = cw;
+    return SR_OK;
+}
+
+// The global row stream (B images of H rows, a separator row after each) split over workgroups: all CUs busy whatever the batch, but no fewer than
+// `min_rows` stream rows each.
+static int split_row_stream(sr_ctx* ctx, int B, int H, int min_rows, const char* what, int* rows_per_wg, int* nwg, unsigned* magic) {
+    int ncu = ctx->cu_count();
+    if (ctx->chain_max_wgs > 0 && ctx->chain_max_wgs < ncu) ncu = ctx->chain_max_wgs;      // test hook: several images per workgroup at small batches
+    const int64_t T = (int64_t)B * (H + 1);
+    if ((T + 16) * (int64_t)(H + 1) * (H + 1) >= (1ll << 32)) return ctx->fail(SR_ERR_INVALID, std::string(what) + ": stream too long");
+    const int nwg_target = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, (T + min_rows - 1) / min_rows));
+    *rows_per_wg = (int)((T + nwg_target - 1) / nwg_target);
+    *nwg = (int)((T + *rows_per_wg - 1) / *rows_per_wg);
+    *magic = (unsigned)(((1ull << 32) + (unsigned)H) / (unsigned)(H + 1));              // ceil(2^32 / (H+1)): exact quotient for g (H+1)^2 < 2^32 (checked above)
     return SR_OK;
 }
 
@@ -999,18 +875,12 @@ int conv1_stream_launch(sr_ctx* ctx, const ConvWeights& w, TensorView in, int B,
     if (!conv1_stream_supported(w, in, W)) return ctx->fail(SR_ERR_INVALID, "streaming conv1: needs a 64 -> 32 bf16 3x3 conv on a 48-pixel-wide row-blocked buffer");
     if (B <= 0 || H <= 0) return ctx->fail(SR_ERR_INVALID, "streaming conv1: empty tensor");
     if (!ctx->zero_page) return ctx->fail(SR_ERR_STATE, "context has no zero page");      // sr_init allocates and clears it
-    int ncu = ctx->cu_count();
-    if (ctx->chain_max_wgs > 0 && ctx->chain_max_wgs < ncu) ncu = ctx->chain_max_wgs;
     Conv1Params p;
     p.in = static_cast<const char*>(in.p); p.in_nch = (int)(in.cs / 32);
     p.w = static_cast<const char*>(w.w); p.bias = w.bias; p.zero = static_cast<const char*>(ctx->zero_page);
     p.B = B; p.H = H;
-    const int64_t T = (int64_t)B * (H + 1);
-    if ((T + 16) * (int64_t)(H + 1) * (H + 1) >= (1ll << 32)) return ctx->fail(SR_ERR_INVALID, "streaming conv1: stream too long");
-    const int nwg_target = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, (T + 15) / 16));
-    p.rows_per_wg = (int)((T + nwg_target - 1) / nwg_target);
-    const int nwg = (int)((T + p.rows_per_wg - 1) / p.rows_per_wg);
-    p.magic = (unsigned)(((1ull << 32) + (unsigned)H) / (unsigned)(H + 1));
+    int nwg;
+    if (int rc = split_row_stream(ctx, B, H, 16, "streaming conv1", &p.rows_per_wg, &nwg, &p.magic)) return rc;
     int rec = -1;
     if (ctx->prof) {
         const double px = (double)B * H * W;
@@ -1038,29 +908,17 @@ int chain_launch(sr_ctx* ctx, const ChainWeights& w, TensorView in, int B, int H
     if (tail && (!out.p || !out.blk || out.coff != 0 || out.cs % 32 != 0 || alpha == 0.f)) return ctx->fail(SR_ERR_INVALID, "fused dense-block tail: bad destination view");
     if (skip_o.p && (!skip_o.blk || skip_o.coff != 0 || skip_o.cs % 32 != 0)) return ctx->fail(SR_ERR_INVALID, "fused dense-block tail: bad skip view");
     // separator / out-of-stream rows are staged from the zero page with the same chunk offset as real rows: (EXT - 1) * 3 KiB + one 3 KiB row
-    static_assert(ZERO_PAGE_BYTES >= 6 * ROWB, "zero page covers every chunk offset");
+    static_assert(sr_ctx::ZERO_PAGE_BYTES >= 6 * ROWB, "zero page covers every chunk offset");
     if (!ctx->zero_page) return ctx->fail(SR_ERR_STATE, "context has no zero page");      // sr_init allocates and clears it
-    int ncu = ctx->num_cus;
-    if (ncu <= 0) {
-        hipDeviceProp_t prop;
-        SR_HIP(ctx, hipGetDeviceProperties(&prop, ctx->device));
-        ncu = ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    if (ctx->chain_max_wgs > 0 && ctx->chain_max_wgs < ncu) ncu = ctx->chain_max_wgs;      // test hook: several images per workgroup at small batches
     ChainParams p;
     p.in = static_cast<const char*>(in.p); p.in_nch = (int)(in.cs / 32);
     p.out = static_cast<char*>(const_cast<void*>(out.p)); p.out_nch = (int)(out.cs / 32);
     p.so = static_cast<const char*>(skip_o.p); p.so_nch = (int)(skip_o.cs / 32);
     p.w = static_cast<const char*>(w.w); p.bias = w.bias; p.zero = static_cast<const char*>(ctx->zero_page);
     p.B = B; p.H = H;
-    // rows of the global stream per workgroup: all CUs busy whatever the batch, but no fewer than 24 rows each (two of a range's rows are
-    // recomputed for its neighbours)
-    const int64_t T = (int64_t)B * (H + 1);
-    if ((T + 16) * (int64_t)(H + 1) * (H + 1) >= (1ll << 32)) return ctx->fail(SR_ERR_INVALID, "fused dense-block pair: stream too long");
-    const int nwg_target = (int)std::max<int64_t>(1, std::min<int64_t>(ncu, (T + 23) / 24));
-    p.rows_per_wg = (int)((T + nwg_target - 1) / nwg_target);
-    const int nwg = (int)((T + p.rows_per_wg - 1) / p.rows_per_wg);
-    p.magic = (unsigned)(((1ull << 32) + (unsigned)H) / (unsigned)(H + 1));                 // ceil(2^32 / (H+1)): exact quotient for g (H+1)^2 < 2^32 (checked above)
+    // no fewer than 24 rows per workgroup: two of a range's rows are recomputed for its neighbours
+    int nwg;
+    if (int rc = split_row_stream(ctx, B, H, 24, "fused dense-block pair", &p.rows_per_wg, &nwg, &p.magic)) return rc;
     p.alpha = alpha; p.xscale = tail ? beta_x / alpha : 0.f; p.oscale = tail && skip_o.p ? beta_o / alpha : 0.f;
     for (float sc : {p.xscale, p.oscale}) {   // the skips join the accumulators as scale * identity MFMA fragments in bf16: only exactly representable ratios (5 and 25 here)
         uint32_t u = (uint32_t)f32_to_bf16_host(sc) << 16;

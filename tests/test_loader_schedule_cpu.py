@@ -1,43 +1,29 @@
 """csrc/dense_fused.hip, loader waves: a model check of the issue / counted-wait schedule (the counted `s_waitcnt vmcnt(N)` of the
-fused kernels' loaders was covered by the GPU parity tests alone).  The schedule is restated here from `LoaderPlan` and the loader loop --
-which pieces a loader requests in the iteration of granule G, in which order, and the N it then waits with -- and replayed against the two
-facts the hardware gives: a wave's vector-memory operations retire IN ORDER, and `vmcnt(N)` returns when all but the N youngest have.  At
-every barrier the test checks what the compute waves are about to read: the DMA'd weight pieces of granule G+1, and, when G+1 opens a
+fused kernels' loaders was covered by the GPU parity tests alone).  The schedule is the kernels' own, csrc/dense_plan.h dumped by
+tests/dense_plan.py -- which pieces a loader requests in the iteration of granule G, in the loader loop's order, and the N it then waits
+with -- and replayed against the two facts the hardware gives: a wave's vector-memory operations retire IN ORDER, and `vmcnt(N)` returns
+when all but the N youngest have.  At every barrier the test checks what the compute waves are about to read: the DMA'd weight pieces of granule G+1, and, when G+1 opens a
 chunk, every row piece of that chunk.  It also checks that nothing is written into a staging buffer or weight slot that a compute wave may
 still be reading.  All four loaders, the tail (EXT 5) and both growth pairs (EXT 2, 3), many steps."""
 import pytest
 
-NLOAD = 4
+import dense_plan
+
+NLOAD = dense_plan.plan()["NLOAD"]
 
 
 class Plan:
+    """Loader `lw` of a shape: a view of the dumped tables.  wait_extra: pieces left in flight beyond the plan's count (the negative test)."""
+    wait_extra = 0
+
     def __init__(self, ext, nb0, nb1, mode, lw):
-        self.ext, self.nb0, self.nb1, self.mode, self.lw = ext, nb0, nb1, mode, lw
-        self.nbt, self.extg, self.ngr = nb0 + nb1, 3 * ext, 3 * (ext + 1)
-        self.rt_e, self.rt_r = (2 if mode == 1 else 3), 2
-        self.nsb, self.nws = (3, 2) if mode == 0 else (2, 3)
-        self.wl, self.sl = self.nws - 1, self.nsb - 1
-
-    def nrows(self, kx):
-        return 2 if kx == 0 else (1 if (kx == 1 and self.lw < 3) else 0)
-
-    def rows(self, kx):
-        return [self.lw, self.lw + 4] if kx == 0 else ([8 + self.lw] if (kx == 1 and self.lw < 3) else [])
-
-    def nst_at(self, i):
-        i %= self.ngr
-        return 3 * self.nrows(i % 3) if i < self.extg else 0
-
-    def nwdma(self, iw):
-        ext = iw < self.extg
-        nw, rt = (self.nbt * 3, self.rt_e) if ext else (self.nb1 * 3, self.rt_r)
-        return sum(1 for t in range((nw + 3) // 4) if self.lw + 4 * t < nw and t >= rt)
+        t = dense_plan.shape((ext, nb0, nb1, mode))
+        self.lw, self.t, self.npieces = lw, t["loaders"][lw], t["npieces"]
+        self.extg, self.ngr, self.wl, self.sl, self.nsb, self.nws = t["extg"], t["ngr"], t["wl"], t["sl"], t["lds"]["nsb"], t["lds"]["nws"]
+        self.rows, self.nwdma = self.t["rows"].__getitem__, self.t["nwdma"].__getitem__
 
     def wait_n(self, i):
-        if self.mode == 0:
-            return self.nst_at(i) + self.nst_at(i - 1) + self.nst_at(i - 2)
-        third = i < self.extg and i % 3 == 2
-        return self.nwdma((i + self.wl) % self.ngr) + self.nst_at(i) + (0 if third else self.nst_at(i - 1))
+        return self.t["wait_n"][i] + self.wait_extra
 
 
 def simulate(ext, nb0, nb1, mode, lw, nsteps):
@@ -66,7 +52,7 @@ def simulate(ext, nb0, nb1, mode, lw, nsteps):
                 assert idx < done, (ext, mode, lw, "granule", G, "not landed", op)
             # --- the iteration: weights of granule G + WL into slot (G + WL) % NWS -- last read in granule G - 1 when NWS = WL + 1 + ... check below
             assert (G + p.wl) % p.nws != G % p.nws or p.wl == 0                 # never the slot being read
-            issued += [("w", G + p.wl)] * p.nwdma((i + p.wl) % p.ngr)
+            issued += [("w", G + p.wl)] * p.nwdma(p.t["issue_w"][i])
             if i < p.extg:
                 c, kx = divmod(i, 3)
                 target = nch + p.sl                                              # chunk number staged now -> buffer target % NSB
@@ -101,48 +87,57 @@ def test_weight_pieces_are_covered_once_by_the_four_loaders():
     for ext, nb0, nb1, mode in ((5, 2, 4, 1), (2, 2, 2, 0), (3, 2, 2, 0)):
         plans = [Plan(ext, nb0, nb1, mode, lw) for lw in range(NLOAD)]
         for iw in range(plans[0].ngr):
-            nw = plans[0].nbt * 3 if iw < plans[0].extg else nb1 * 3
-            pieces = sorted(lw + 4 * t for lw in range(NLOAD) for t in range((nw + 3) // 4) if lw + 4 * t < nw)
+            nw = plans[0].npieces[iw]
+            assert nw == (3 * (nb0 + nb1) if iw < 3 * ext else 3 * nb1)
+            assert all(len(p.t["resident"][iw]) == nw for p in plans)
+            pieces = sorted(k for lw in range(NLOAD) for k in range(lw, nw, NLOAD))          # loader lw owns pieces lw, lw + NLOAD, ...
             assert pieces == list(range(nw)), (ext, iw)
+            for p in plans:                                                      # ... and counts its non-resident ones as DMA
+                assert p.nwdma(iw) == sum(1 for k in range(p.lw, nw, NLOAD) if not p.t["resident"][iw][k])
             if mode == 0:
                 assert all(p.nwdma(iw) == 0 for p in plans)                      # growth pairs: every weight piece is register resident
+            else:                                                                # tail: a granule's first eight pieces are, the others come by DMA
+                assert sum(p.nwdma(iw) for p in plans) == nw - 8 == (10 if iw < 3 * ext else 4)
 
 
 def test_model_catches_a_wrong_wait():
     """Self-test: leaving one more piece in flight than the schedule allows must trip the landed-check."""
-    real = Plan.wait_n
     try:
-        Plan.wait_n = lambda self, i: real(self, i) + 1
+        Plan.wait_extra = 1
         with pytest.raises(AssertionError):
             for lw in range(NLOAD):
                 simulate(5, 2, 4, 1, lw, nsteps=4)
     finally:
-        Plan.wait_n = real
+        Plan.wait_extra = 0
 
 
 # ---- conv1_stream_kernel (csrc/dense_fused.hip): units k = (step k // 2, chunk k % 2) through four staging buffers ----------------------------
 
 def _conv1_loader_replay(lw, nunits):
-    """The loader loop of conv1_stream_kernel restated: prologue units 0..2; per barrier k: [k == 0: wait all but 2 NP]; barrier; issue unit
-    k + 3 into buffer (k + 3) % 4; wait all but 2 NP.  Returns, per barrier k, the units of this loader's pieces that have landed when the
-    barrier opens, and the unit whose buffer the iteration then overwrites."""
-    np_ = 3 * (3 if lw < 2 else 2)
+    """The loader loop of conv1_stream_kernel on Conv1LoaderPlan's numbers (NP pieces per unit, AHEAD units issued ahead, the WAIT count, C1_NSB
+    buffers): prologue units 0..AHEAD-1; per barrier k: [k == 0: wait all but WAIT]; barrier; issue unit k + AHEAD into buffer (k + AHEAD) %
+    NSB; wait all but WAIT.  Returns, per barrier k, the units of this loader's pieces that have landed when the barrier opens, and the unit
+    whose buffer the iteration then overwrites."""
+    c1 = dense_plan.plan()["conv1"]
+    t = c1["loaders"][lw]
+    np_, ahead, wait, nsb = t["np"], t["ahead"], t["wait"], c1["nsb"]
+    assert np_ == 3 * len(t["rows"])
     issued, done = [], 0
 
     def wait_all_but(n):
         nonlocal done
         done = max(done, len(issued) - n)
 
-    for k in (0, 1, 2):
+    for k in range(ahead):
         issued += [k] * np_
     landed_at, overwritten_at = [], []
     for k in range(nunits):
         if k == 0:
-            wait_all_but(2 * np_)
+            wait_all_but(wait)
         landed_at.append(list(issued[:done]))
-        overwritten_at.append(k + 3 - 4)                    # the unit that lived in buffer (k + 3) % 4 before unit k + 3
-        issued += [k + 3] * np_
-        wait_all_but(2 * np_)
+        overwritten_at.append(k + ahead - nsb)              # the unit that lived in buffer (k + ahead) % nsb before unit k + ahead
+        issued += [k + ahead] * np_
+        wait_all_but(wait)
     return landed_at, overwritten_at
 
 

@@ -8,63 +8,57 @@ only if, for every LDS location they touch,
       piece (ds_write_b128) is drained by the loader's lgkmcnt(0) in front of the next barrier; an LDS-DMA piece lands when the loader's
       counted vmcnt says so (in-order retirement, as in test_loader_schedule_cpu.py); a ring row is written in the layer-0 epilogue;
   (b) no write to it is issued before barrier G + 2, the barrier that ends the consuming granule G + 1.
-The loaders' schedule (LoaderPlan, the loader loop) and the plan are restated here and replayed together: all four loaders, the tail (EXT 5,
-NB 2 / 4) and both growth pairs (EXT 2 and 3, NB 2 / 2), several steps.  The growth pairs carry nothing (their two weight slots are written
+The loaders' schedule (LoaderPlan) and the plan are the kernels' own -- csrc/dense_plan.h, dumped by tests/dense_plan.py -- and are replayed
+together in the loader loop's order of issue: all four loaders, the tail (EXT 5, NB 2 / 4) and both growth pairs (EXT 2 and 3, NB 2 / 2),
+several steps.  The growth pairs carry nothing (their two weight slots are written
 one granule ahead, i.e. while the pre-read would run: the model shows it); the test still walks them, so that switching their plan on
-without a weight ring that allows it fails here.  The LDS byte sums of both kernels are restated and checked against the 160 KiB of a CU."""
+without a weight ring that allows it fails here.  The header's LDS byte sums are pinned and checked against the 160 KiB of a CU."""
 import pytest
 
-NLOAD, NCOMP, WDEPTH = 4, 8, 3
-ROWB, NSTG, WINR = 3072, 11, 10
+import dense_plan
+
+_P = dense_plan.plan()
+NLOAD, NCOMP, WDEPTH, WINR = _P["NLOAD"], _P["NCOMP"], _P["WDEPTH"], _P["WINR"]
 LDS_LIMIT = 160 * 1024
 
 
 class Cfg:
-    def __init__(self, ext, nb0, nb1, mode, carry=None, carry_x_across_chunks=None):
+    """One shape's dumped tables, with the hooks of the negative tests: carry=True reads the plan as if it were switched on,
+    carry_x_across_chunks=True lets pixel pre-reads follow every weight pre-read, `dma` turns resident pieces (iw, k) into DMA pieces."""
+
+    def __init__(self, ext, nb0, nb1, mode, carry=None, carry_x_across_chunks=False):
+        t = self.t = dense_plan.shape((ext, nb0, nb1, mode))
         self.ext, self.nb0, self.nb1, self.mode = ext, nb0, nb1, mode
-        self.nbt, self.extg, self.ngr = nb0 + nb1, 3 * ext, 3 * (ext + 1)
-        self.rt_e, self.rt_r = (2 if mode == 1 else 3), 2
-        self.nsb, self.nws = (3, 2) if mode == 0 else (2, 3)
-        self.wl, self.sl = self.nws - 1, self.nsb - 1
-        self.wslot = self.nbt * 3 * 1024
-        # CarryPlan / kCarry: the tail carries, the growth pairs do not; pixels across a chunk boundary only with three staging buffers
-        self.carry = (mode == 1) if carry is None else carry
-        self.x_across_chunks = (mode == 0) if carry_x_across_chunks is None else carry_x_across_chunks
+        self.extg, self.ngr, self.wl, self.sl = t["extg"], t["ngr"], t["wl"], t["sl"]
+        self.nsb, self.nws = t["lds"]["nsb"], t["lds"]["nws"]
+        self.carry = t["carry_forced" if carry else "carry"]
+        self.x_across_chunks = carry_x_across_chunks
+        self.dma = lambda iw, k: False
 
     def lds_bytes(self):
-        return self.nsb * NSTG * ROWB + WINR * ROWB + self.nws * self.wslot + self.nbt * 16 * 4
+        return self.t["lds"]["bytes"]
 
-    # ---- LoaderPlan
     def rows(self, lw, kx):
-        return [lw, lw + 4] if kx == 0 else ([8 + lw] if (kx == 1 and lw < 3) else [])
-
-    def nst_at(self, lw, i):
-        i %= self.ngr
-        return 3 * len(self.rows(lw, i % 3)) if i < self.extg else 0
+        return self.t["loaders"][lw]["rows"][kx]
 
     def npieces(self, iw):
-        return self.nbt * 3 if iw < self.extg else self.nb1 * 3
+        return self.t["npieces"][iw]
 
     def resident(self, iw, k):
-        return k // NLOAD < (self.rt_e if iw < self.extg else self.rt_r)
-
-    def nwdma(self, lw, iw):
-        return sum(1 for k in range(lw, self.npieces(iw), NLOAD) if not self.resident(iw, k))
+        return bool(self.t["loaders"][k % NLOAD]["resident"][iw][k]) and not self.dma(iw, k)
 
     def wait_n(self, lw, i):
-        if self.mode == 0:
-            return self.nst_at(lw, i) + self.nst_at(lw, i - 1) + self.nst_at(lw, i - 2)
-        third = i < self.extg and i % 3 == 2
-        return self.nwdma(lw, (i + self.wl) % self.ngr) + self.nst_at(lw, i) + (0 if third else self.nst_at(lw, i - 1))
+        """The plan's count; a piece a hook took out of the registers is one more DMA piece of the granule whose weights iteration i issues."""
+        t = self.t["loaders"][lw]
+        iw = t["issue_w"][i]
+        return t["wait_n"][i] + sum(1 for k in range(lw, self.npieces(iw), NLOAD) if self.dma(iw, k))
 
-    # ---- CarryPlan: what granule i of a step (external: i < extg; ring: kx = i - extg) finds requested by its predecessor
+    # ---- what granule i of a step (external: i < extg; ring: kx = i - extg) finds requested by its predecessor
     def pre_w(self, i):
-        return self.carry and ((0 < i < self.extg) or i > self.extg)
+        return bool(self.carry["pre_w"][i])
 
     def pre_x(self, i):
-        if not self.pre_w(i):
-            return False
-        return i > self.extg or i % 3 != 0 or self.x_across_chunks
+        return self.pre_w(i) if self.x_across_chunks else bool(self.carry["pre_x"][i])
 
 
 class Write:
@@ -119,7 +113,7 @@ def replay(cfg, nsteps):
             for i in range(cfg.ngr):
                 if lw == 0:
                     granules.append((i, nch, s))
-                weights((i + cfg.wl) % cfg.ngr, G + cfg.wl, G)
+                weights(cfg.t["loaders"][lw]["issue_w"][i], G + cfg.wl, G)
                 if i < cfg.extg:
                     rows(i % 3, nch + cfg.sl, G)
                 n = cfg.wait_n(lw, i)
@@ -197,6 +191,7 @@ def test_tail_plan_in_detail():
     # the pre-read fragments are pieces the loaders keep in registers and write a granule early (t < RT_E / RT_R), for every granule position
     for iw in range(cfg.ngr):
         assert all(cfg.resident(iw, k) for k in range(WDEPTH))
+        assert [k for k in range(cfg.npieces(iw)) if cfg.resident(iw, k)] == list(range(8))     # (a granule's first eight fragments, as the packer says)
 
 
 def test_model_catches_pixels_across_a_tail_chunk_boundary():
@@ -216,9 +211,8 @@ def test_model_catches_weight_prereads_from_a_two_slot_ring(shape):
 def test_model_catches_a_dma_piece_among_the_head_fragments():
     """A head fragment that came by LDS-DMA is waited for one iteration too late for the pre-read (the old fragment order: stage 2 used piece 8)."""
     cfg = Cfg(*TAIL)
-    real = cfg.resident
-    cfg.resident = lambda iw, k: real(iw, k) and k != 2
-    cfg.nwdma = lambda lw, iw: sum(1 for k in range(lw, cfg.npieces(iw), NLOAD) if not cfg.resident(iw, k))
+    assert all(cfg.resident(iw, 2) for iw in range(cfg.ngr))
+    cfg.dma = lambda iw, k: k == 2
     with pytest.raises(AssertionError):
         check(cfg)
 
