@@ -485,6 +485,32 @@ int  sr_dense_head_step(sr_ctx* ctx, const float* feats, int n, int in_dim, int 
                         const uint8_t* keep0, const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads,
                         double* stats, void* work, int64_t work_bytes, void* stream);
 
+/* ---- the discriminator's update inside ESRGAN._train_step besides its convs (reference ESRGAN_model.py:347-377, :475-533), csrc/disc_train.hip ----
+ * sr_spectral_norm_bucket: tfa SpectralNormalization.normalize_weights, one power iteration, of n_layers kernels IN PLACE where they lie in a
+ *   flat parameter bucket (sr355/train.py ParamBucket), by one launch.  bucket DEVICE fp32 [bucket_len]; u DEVICE fp32 [u_len], every layer's
+ *   power-iteration vector; descs HOST [n_layers]: the kernel is bucket[koff : koff + K * Cout] read as w [K, Cout] (K = the product of all axes
+ *   but the last), its vector u[uoff : uoff + Cout].  Per layer, in fp64 on the widened fp32 values: v = l2n(u w^T), u' = l2n(v w),
+ *   sigma = v w u'^T with l2n(a) = a / sqrt(max(sum a^2, 1e-12)); then kernel <- kernel / float(sigma) (an fp32 division) and u <- u'.  Nothing
+ *   else of the bucket is touched.  Any K >= 1 and Cout >= 1.  SR_ERR_INVALID, and no launch, for a null pointer, n_layers <= 0, a descriptor
+ *   that reaches past bucket_len / u_len, or two descriptors whose kernels or whose u ranges overlap (each layer is a workgroup of its own).  Every sum runs in a fixed order (no atomics): the same state gives the same bits.
+ * sr_disc_head_step: the discriminator's head on the last conv's activation map, forward + loss + backward.  h DEVICE fp32 [B,H,W,in_dim];
+ *   params DEVICE fp32: disc_dense1's kernel [in_dim,hidden] and bias [hidden], disc_output's kernel [hidden,out_dim] and bias [out_dim] as they
+ *   follow each other in the bucket; (in_dim, hidden, out_dim) must be (256, 256, 1).  g = mean_{H,W} h, z1 = g k1 + b1, a1 = LeakyReLU_0.2(z1),
+ *   z2 = a1 k2 + b2, p = sigmoid(z2); loss = mean_B of keras.backend.binary_crossentropy(target, p) on probabilities (clip to [1e-7, 1 - 1e-7],
+ *   + 1e-7 inside both logs; the gradient passes only where p lies inside the clip range), target 0 or 1.  Writes *loss (DEVICE fp32, one slot of the
+ *   caller's loss buffer), p [B], dh [B,H,W,in_dim] = d loss / d h (d loss / d g spread over the map, / (H W)) and, when grads is non-NULL, the
+ *   four parameter gradients into grads (DEVICE fp32, the layout of params: the head's slice of the flat gradient bucket) -- stored, or added
+ *   onto what is there when accumulate is non-zero.  Sums in fp64, the batch rows in row order, no atomics. */
+typedef struct {
+    int64_t koff;       /* first float of the kernel in the bucket */
+    int32_t K, Cout;    /* the kernel as a [K, Cout] matrix */
+    int64_t uoff;       /* first float of the layer's u in the u tensor */
+} sr_sn_desc;
+int  sr_spectral_norm_bucket(sr_ctx* ctx, float* bucket, int64_t bucket_len, float* u, int64_t u_len, const sr_sn_desc* descs, int n_layers,
+                             void* stream);
+int  sr_disc_head_step(sr_ctx* ctx, const float* h, int B, int H, int W, int in_dim, int hidden, int out_dim, const float* params, float target,
+                       float* loss, float* p, float* dh, float* grads, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

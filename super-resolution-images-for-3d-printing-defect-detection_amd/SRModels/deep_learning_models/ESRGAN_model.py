@@ -20,10 +20,12 @@ from sr355.wrappers import DeviceModelMixin, load_pretrained
 
 
 class ESRGAN(DeviceModelMixin):
-    def __init__(self, compute_dtype="f32"):
+    def __init__(self, compute_dtype="f32", discriminator_update="host"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
         >= 100 dB against the fp64 oracle) or "bf16" (opt-in: bf16 storage, fp32 accumulation -- BASELINE configs[2]'s dtype and what
-        bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md)."""
+        bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md).
+        discriminator_update: where _train_step updates the discriminator -- "host" (default: NumPy, as before) or "device" (its parameters,
+        spectral-norm vectors and Adam stay on the GPU: sr355.gan_train.ESRGANTrainer); anything else raises when the trainer is built."""
         self.generator = None
         self.discriminator = None
         self.vgg_model = None
@@ -31,6 +33,7 @@ class ESRGAN(DeviceModelMixin):
         self.d_optimizer = None
         self.trained = False
         self.compute_dtype = compute_dtype
+        self.discriminator_update = discriminator_update
 
     def _mark_trained(self, v):
         self.trained = v
@@ -118,7 +121,8 @@ class ESRGAN(DeviceModelMixin):
             self._ensure_loss_networks()
             self._trainer = ESRGANTrainer(self.ctx, self.weights, self.d_weights, self.vgg_weights, self.scale_factor,
                                           self.num_rrdb_blocks, attention=self.use_attention, g_lr=1e-4, d_lr=1e-5,
-                                          allreduce=getattr(self, "grad_allreduce", None), allreduce_flat=getattr(self, "grad_allreduce_flat", None))
+                                          allreduce=getattr(self, "grad_allreduce", None), allreduce_flat=getattr(self, "grad_allreduce_flat", None),
+                                          discriminator=self.discriminator_update)
             self.g_optimizer, self.d_optimizer = self._trainer.g_opt, self._trainer.d_opt
         return self._trainer
 
@@ -144,6 +148,8 @@ class ESRGAN(DeviceModelMixin):
         tr = self._trainer
         self.set_weights(tr.gw)
         self.set_loss_network_weights(discriminator=tr.dw)
+        if tr.d_params is not None:      # device mode: tr.dw are views of the bucket's host buffer, rewritten by the next refresh; keep a snapshot, as host mode does
+            self.d_weights = {n: (k.copy(), b.copy()) for n, (k, b) in self.d_weights.items()}
 
     def _train_step(self, lr_batch, hr_batch):
         """ESRGAN_model.py:475-533 on [-1,1] batches -> {'g_loss', 'd_loss', ...} (floats)."""

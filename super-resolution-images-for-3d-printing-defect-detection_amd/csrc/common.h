@@ -60,6 +60,9 @@ struct sr_ctx {
                                         // dft_ops under the keys -(2^32 + N)
     Arena deg_work;                     // degrade.hip: the JPEG round trip's planar Y / Cb / Cr between its two kernels
     Arena crop_work;                    // crop.hip: gray / mask / filled planes, the label map, per-root areas, per-frame histograms and winners
+    Arena sn_work, sn_tab, dhead_work;  // disc_train.hip: the power iterations' t / partial column sums, the layer table, the head's per-row values between its two kernels
+    std::vector<char> sn_tab_host;      // ... the layer table as last uploaded
+    void* sn_tab_dev = nullptr;
     int* deg_status = nullptr;          // degrade.hip: {stage, row, value} of the first bad parameter-table row a kernel met (sr_degrade_status)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev

@@ -39,6 +39,11 @@ class PackDesc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("K", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("rot", C.c_int32)]
 
 
+class SnDesc(C.Structure):
+    """sr_sn_desc: one spectrally normalised kernel of a flat parameter bucket (include/sr355.h)."""
+    _fields_ = [("koff", C.c_int64), ("K", C.c_int32), ("Cout", C.c_int32), ("uoff", C.c_int64)]
+
+
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 _vw = C.POINTER(View)
 _fp = C.POINTER(C.c_float)
@@ -117,6 +122,8 @@ SIGNATURES = {
     "sr_affine_warp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_dense_head_workspace_bytes": (_i64, [_i, _i]),
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
+    "sr_spectral_norm_bucket": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(SnDesc), _i, _vp]),
+    "sr_disc_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 # the columns of sr_classic_scores (SR_SCORE_* in include/sr355.h)

@@ -6,9 +6,10 @@ import numpy as np
 import torch
 
 
-def cfg3_train_step(ctx, steps=3, batch=16, allreduce=None, allreduce_flat=None, seed_offset=0):
+def cfg3_train_step(ctx, steps=3, batch=16, allreduce=None, allreduce_flat=None, seed_offset=0, discriminator="host"):
     """BASELINE configs[3]: ESRGAN._train_step (ESRGAN_model.py:475-533) at the reference's defaults -- x4, NB = 23, G = 32, both SelfAttention
-    layers, `batch` LR patches 24 x 24 -> 96 x 96 per GPU, fp32 -- on sr355.gan_train.ESRGANTrainer.  -> dict (ms per step, losses, ...)."""
+    layers, `batch` LR patches 24 x 24 -> 96 x 96 per GPU, fp32 -- on sr355.gan_train.ESRGANTrainer; `discriminator`: where its discriminator
+    update runs ("host", the default and bench.py's row, or "device").  -> dict (ms per step, losses, ...)."""
     from .gan_train import ESRGANTrainer
     from .runtime import Model
     from .weights import condition_attention, init_weights
@@ -23,7 +24,7 @@ def cfg3_train_step(ctx, steps=3, batch=16, allreduce=None, allreduce_flat=None,
     vw = init_weights(v.layer_shapes(), scheme="he_normal", seed=6000)
     vw = {n: (k * 0.05 if n == "block1_conv1" else k, b) for n, (k, b) in vw.items()}
     del g, d, v
-    tr = ESRGANTrainer(ctx, gw, dw, vw, 4, 23, attention=True, allreduce=allreduce, allreduce_flat=allreduce_flat)
+    tr = ESRGANTrainer(ctx, gw, dw, vw, 4, 23, attention=True, allreduce=allreduce, allreduce_flat=allreduce_flat, discriminator=discriminator)
     rng = np.random.default_rng(42 + 3 + seed_offset)
     lr = rng.uniform(-1, 1, (batch, 24, 24, 3)).astype(np.float32)
     hr = rng.uniform(-1, 1, (batch, 96, 96, 3)).astype(np.float32)

@@ -11,9 +11,13 @@ The forward and backward passes are host orchestration over the C ABI's single o
     softmax-backward kernel; pooling / stride-2 sampling / depth_to_space / activations / the (W,C)-FFT loss have their own adjoint kernels;
   * a minimal reverse-mode tape (below) keeps the graph bookkeeping out of the kernels; torch is used for memory only (cat / slice /
     flip / expand: data movement).
-Tiny vectors -- the discriminator's [B,256] dense head, BCE on [B,1], spectral-norm power iteration, Adam -- run on the host in NumPy.
-Parameters are uploaded once per step and packed into MFMA fragment order on the device per layer call (sr_conv2d_dev); the
-optimisers and the tape bookkeeping stay on the host.  cfg3's throughput is recorded by tools/bench_train.py, not yet a bench line.
+The discriminator's tiny vectors -- its [B,256] dense head, BCE on [B,1], spectral-norm power iteration, Adam -- run on the host in NumPy by
+default (discriminator="host": its parameters are uploaded after every renormalisation) or, with discriminator="device", on the device:
+the parameters, u and Adam's moments stay in flat device buckets, one launch renormalises all eight kernels (sr_spectral_norm_bucket), two
+run the head with its loss and backward (sr_disc_head_step), and the step's six loss scalars come back in one copy (csrc/disc_train.hip).
+The generator's parameters are device-resident in both modes; kernels are packed into MFMA fragment order on the device per layer call
+(sr_conv2d_dev); the tape bookkeeping stays on the host.  cfg3's throughput is the `cfg3 ESRGAN _train_step` row of bench.py --full
+(sr355/bench_rows.py cfg3_train_step), and tools/bench_train.py measures it alone, in either mode.
 """
 import contextlib
 
@@ -338,11 +342,16 @@ def staircase_lr(lr0, step, decay_steps=10000, decay_rate=0.5):
 
 # ----------------------------------------------------------------------------------------------------------------- the step
 class ESRGANTrainer:
-    """Holds generator / discriminator / VGG19 weights (host fp32), the SN vectors u, the two Adam states and the step counter."""
+    """Holds generator / discriminator / VGG19 weights, the SN vectors u, the two Adam states and the step counter.  discriminator="host"
+    (default): the discriminator's weights, u and Adam live on the host in NumPy; "device": in flat device buckets (_init_device_discriminator)."""
 
     def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None):
+                 allreduce_flat=None, discriminator="host"):
+        if discriminator not in ("host", "device"):
+            raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
         self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
+        self.discriminator = discriminator
+        self.d_params = None                               # discriminator="device": the discriminator's flat device bucket (below)
         # Generator (16.9 M parameters at the default depth): resident on the device as ONE flat fp32 bucket with its Adam moments beside it;
         # the per-layer tensors the tape multiplies with are views of it, the gradients are gathered into a bucket of the same order, and
         # the optimiser is one fused kernel (round 2: NumPy Adam on the host, 65 ms of a 258 ms step, plus 70 MB each way over PCIe).
@@ -357,14 +366,70 @@ class ESRGANTrainer:
                                                for n in DISC_LAYERS}
         self.g_lr0, self.d_lr0 = g_lr, d_lr
         self.g_opt = DeviceAdam(ctx, self.g_params.flat, g_lr, epsilon=1e-7)
-        self.d_opt = None if self.dw is None else Adam(self.dw, d_lr, epsilon=1e-7)
+        if discriminator == "device" and self.dw is not None:
+            self._init_device_discriminator()
+        else:
+            self.d_opt = None if self.dw is None else Adam(self.dw, d_lr, epsilon=1e-7)
         self.step = 0
         # data parallel: `allreduce` = callable(dict of host grads) -> averaged dict (the discriminator's, whose spectral normalisation lives on
         # the host); `allreduce_flat` = callable(flat device tensor) -> averaged tensor for the generator's bucket (RCCL reduces it where it
-        # lies).  With only `allreduce` given the generator's bucket takes the dict route too (the gloo CPU tests).
+        # lies).  With only `allreduce` given the generator's bucket takes the dict route too (the gloo CPU tests).  discriminator="device":
+        # the discriminator's gradients are a flat device bucket as well and take the same two routes as the generator's.
         self.allreduce, self.allreduce_flat = allreduce, allreduce_flat
         self._last = None
         self._packs = {}
+
+    def _init_device_discriminator(self):
+        """discriminator="device": the discriminator's parameters as ONE flat device bucket in DISC_LAYERS order (the head's four arrays are its
+        last 66 049 values), u as one flat device tensor (the layers' [1,Cout] vectors one after the other: 961 floats), Adam's moments beside
+        them.  `dw` and `u` stay readable as host arrays: they are refreshed from the device when somebody reads them."""
+        ctx = self.ctx
+        dw, u = self._dw, self._u
+        self.d_params = ParamBucket(ctx, {n: dw[n] for n in DISC_LAYERS})
+        self._dw = self._u = None
+        self._u_host = np.concatenate([u[n].ravel() for n in DISC_LAYERS]).astype(np.float32)
+        self._u_views, o = {}, 0
+        for n in DISC_LAYERS:
+            self._u_views[n] = self._u_host[o:o + u[n].size].reshape(1, -1)
+            o += u[n].size
+        self.u_flat, self._u_stale = ctx.to_device(self._u_host), False
+        self._sn_table, u_len = ctx.spectral_norm_table(self.d_params, DISC_LAYERS)
+        assert u_len == self._u_host.size
+        self.d_opt = DeviceAdam(ctx, self.d_params.flat, self.d_lr0, epsilon=1e-7)
+        self._head_off = self.d_params.flat.numel() - ctx.DISC_HEAD_PARAMS
+        self._d_head_g = ctx.empty((ctx.DISC_HEAD_PARAMS,))                # the head's slice of the gradient bucket: the real pass stores, the fake pass adds
+        self._losses = ctx.empty((3,))                                     # BCE of D(real) vs 1, D(fake) vs 0, D(fake) vs 1, until the end of the step
+
+    @property
+    def dw(self):
+        """{layer: (kernel, bias)} host arrays of the discriminator's parameters (device mode: refreshed from the bucket when it has moved on)."""
+        return self._dw if self.d_params is None else self.d_params.host()
+
+    @dw.setter
+    def dw(self, weights):
+        if self.d_params is None:
+            self._dw = weights
+        else:                                              # ESRGAN.set_loss_network_weights on a live trainer: Adam's moments and u stay
+            self.d_params.load({n: weights[n] for n in DISC_LAYERS})
+
+    @property
+    def u(self):
+        """{layer: [1,Cout]} host arrays of the power-iteration vectors (device mode: refreshed from the device when they have moved on)."""
+        if self.d_params is None:
+            return self._u
+        if self._u_stale:
+            self._u_host[:] = self.u_flat.cpu().numpy()
+            self._u_stale = False
+        return self._u_views
+
+    @u.setter
+    def u(self, u):
+        if self.d_params is None:
+            self._u = u
+        else:
+            self._u_host[:] = np.concatenate([np.asarray(u[n], np.float32).ravel() for n in DISC_LAYERS])
+            self.u_flat.copy_(self.ctx.to_device(self._u_host))
+            self._u_stale = False
 
     @contextlib.contextmanager
     def _prepacked(self, with_vgg):
@@ -414,6 +479,8 @@ class ESRGANTrainer:
         if "g" not in self._last:
             full = self.g_params.split(self._last.pop("g_flat").cpu().numpy())
             self._last["g"] = {n: full[n] for n in full if n in self._last["g_names"]}     # only the variables the loss reaches, as Keras reports them
+        if "d" not in self._last:                          # discriminator="device": the same, from its bucket
+            self._last["d"] = self.d_params.split(self._last.pop("d_flat").cpu().numpy())
         return self._last
 
     def _update_generator(self, grads):
@@ -463,13 +530,84 @@ class ESRGANTrainer:
 
     def train_step(self, lr_images, hr_images):
         """-> {'g_loss', 'd_loss', parts...}; weights, u, optimiser states advance in place (ESRGAN_model.py:475-533)."""
-        if self.dw is None or self.vw is None:
+        if (self.d_params is None and self._dw is None) or self.vw is None:      # not `self.dw`: in device mode reading it downloads the bucket
             raise RuntimeError("ESRGANTrainer was built without discriminator / VGG19 weights: only pixel_step is available")
         if self._vgg_src is not self.vw:                  # the first step, or ESRGAN.set_loss_network_weights has replaced the VGG19 weights
             self._vgg, self._vgg_src = ParamBucket(self.ctx, self.vw), self.vw
             self._packs.pop(True, None)
         with self._prepacked(True):                        # the generator's weights change only in the step's last lines, VGG19's never
+            if self.d_params is not None:
+                return self._train_step_device(lr_images, hr_images)
             return self._train_step(lr_images, hr_images)
+
+    def _discriminator_pass(self, x, target, slot, wgrad=True, accumulate=False, masks=None):
+        """One training=True call of the discriminator on its device bucket: one launch renormalises the eight kernels where they lie, the six
+        convs run on the bucket's views, the head op writes the BCE against `target` into loss slot `slot` and d loss / d h, and the tape runs
+        back.  -> the tape (its grads: the six convs'; the head's are in self._d_head_g)."""
+        ctx, P = self.ctx, self.d_params
+        ctx.spectral_norm_bucket(P.flat, self.u_flat, self._sn_table)
+        P.stale = self._u_stale = True
+        t = Tape(ctx, P.arrays, wgrad=wgrad, devcache=dict(P.devcache))
+        t.masks = masks
+        h = x
+        for i, st in enumerate(DISC_STRIDES):
+            h = t.conv(h, f"disc_conv{i + 1}", act="lrelu")
+            if st == 2:
+                h = t.pick2(h)
+        _, h.g = ctx.disc_head_step(h.v, P.flat[self._head_off:], target, self._losses[slot:slot + 1], self._d_head_g if wgrad else None, accumulate)
+        t.backward()
+        return t
+
+    def _train_step_device(self, lr_images, hr_images):
+        """_train_step with the discriminator's update on the device (discriminator="device"): the step issues two uploads (the image batches) and one
+        read (the six loss scalars, at its end); the discriminator's bucket is downloaded only when somebody reads `dw` / `u` / `last_grads`."""
+        ctx, P = self.ctx, self.d_params
+        lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
+        tg = self.generator_tape()
+        collect = getattr(self, "collect_masks", False)
+        self.last_masks = {"g": {}, "d_real": {}, "d_fake": {}} if collect else None
+        if collect:
+            tg.masks = self.last_masks["g"]
+        y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
+        fake = y.v
+        # ---- discriminator update: the two passes' gradients meet in one flat bucket (the head's through its accumulate flag)
+        td = self._discriminator_pass(Var(hr_t, need=False), 1.0, 0, masks=self.last_masks["d_real"] if collect else None)          # renormalisation 1
+        g_real = P.gather(td.grads)
+        td2 = self._discriminator_pass(Var(fake, need=False), 0.0, 1, accumulate=True, masks=self.last_masks["d_fake"] if collect else None)   # renormalisation 2
+        d_flat = ctx.eltwise(L.ELT_AXPBY, g_real, P.gather(td2.grads), 1.0, 1.0)
+        d_flat[self._head_off:].copy_(self._d_head_g)
+        if self.allreduce_flat is not None:
+            d_flat = self.allreduce_flat(d_flat)
+        elif self.allreduce is not None:                   # dict route (host): the 2-rank gloo tests
+            d_flat = ctx.to_device(P.flatten(self.allreduce(P.split(d_flat.cpu().numpy()))))
+        self.d_opt.lr = staircase_lr(self.d_lr0, self.step)
+        self.d_opt.apply(P.flat, d_flat)
+        P.stale = True
+        # ---- generator update
+        yv = Var(y.v)
+        self._discriminator_pass(yv, 1.0, 2, wgrad=False)                                         # renormalisation 3
+        tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
+        fr = vgg19_features(tv, Var(hr_t, need=False))
+        tv.ops = []
+        yv2 = Var(y.v)
+        ff = vgg19_features(tv, yv2)
+        perc = ctx.mse(fr.v, ff.v)
+        ff.g = ctx.eltwise(L.ELT_AXPBY, ff.v, fr.v, 2.0 / ff.v.numel(), -2.0 / ff.v.numel())
+        tv.backward()
+        pix = ctx.l1(hr_t, y.v)
+        spec = ctx.spectral_l1(y.v, hr_t)
+        dy = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 100.0 / y.v.numel(), 0.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, ctx.spectral_l1_bwd(y.v, hr_t, 1.0), 1.0, 1.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv.g, 1.0, 1.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv2.g, 1.0, 1.0)
+        y.g = dy
+        self.last_dy = dy
+        tg.backward()
+        self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads), "d_flat": d_flat}
+        self.last_fake = fake
+        l_real, l_fake, adv, perc, pix, spec = (float(v) for v in torch.cat([self._losses, perc, pix, spec]).cpu().numpy())    # the step's one read
+        return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
+                "pixel": pix, "spectral": spec}
 
     def _train_step(self, lr_images, hr_images):
         ctx = self.ctx

@@ -783,6 +783,66 @@ class Context:
         self.check(self.lib.sr_dense_head_step(self.h, feats.data_ptr(), n, 512, 256, C_, labels.data_ptr(), ptr(keep0), ptr(keep1), float(keep_scale),
                                                params.data_ptr(), float(l2_reg), ptr(grads), stats.data_ptr(), work.data_ptr(), work.numel(), self.stream()))
 
+    # ------------------------------------------------------------------ the discriminator's update besides its convs (ESRGAN_model.py:347-377, :475-533)
+    @staticmethod
+    def spectral_norm_table(bucket, layers):
+        """The descriptor table of spectral_norm_bucket for the kernels of `layers` (names, in the order of their u vectors) of a
+        train.ParamBucket -> (ctypes array of sr_sn_desc, length of the flat u tensor: the layers' Cout one after the other)."""
+        offs, o = {}, 0
+        for n, shapes in bucket.shapes.items():
+            offs[n] = o
+            o += sum(int(np.prod(s)) for s in shapes)
+        table, uoff = (L.SnDesc * len(layers))(), 0
+        for d, n in zip(table, layers):
+            if n not in offs:
+                raise KeyError(f"spectral_norm_table: the bucket has no layer {n!r}")
+            kshape = bucket.shapes[n][0]
+            cout = int(kshape[-1])
+            d.koff, d.K, d.Cout, d.uoff = offs[n], int(np.prod(kshape)) // cout, cout, uoff
+            uoff += cout
+        return table, uoff
+
+    def spectral_norm_bucket(self, flat, u, table):
+        """tfa's SpectralNormalization (one power iteration) of every kernel `table` describes, in place in the flat fp32 bucket `flat`, by
+        one launch (sr_spectral_norm_bucket); u, the flat fp32 tensor of the layers' power-iteration vectors, moves on with it."""
+        _check_tensor(self, flat, "spectral_norm bucket")
+        _check_tensor(self, u, "spectral_norm u")
+        if flat.dim() != 1 or u.dim() != 1:
+            raise ValueError("spectral_norm_bucket: the bucket and u must be flat")
+        if not isinstance(table, C.Array) or table._type_ is not L.SnDesc or len(table) < 1:
+            raise ValueError("spectral_norm_bucket: table must be a non-empty array of sr_sn_desc (spectral_norm_table)")
+        self.check(self.lib.sr_spectral_norm_bucket(self.h, flat.data_ptr(), flat.numel(), u.data_ptr(), u.numel(), table, len(table), self.stream()))
+
+    DISC_HEAD_PARAMS = 256 * 256 + 256 + 256 + 1
+
+    def disc_head_step(self, h, params, target, loss, grads=None, accumulate=False):
+        """The discriminator's head on the last conv's map (sr_disc_head_step): h fp32 [B,H,W,256]; params the head's 66 049 values as they lie
+        in the bucket (disc_dense1 kernel, bias, disc_output kernel, bias); target 0 or 1; loss a one-element fp32 view that receives the mean
+        binary cross-entropy.  With grads (fp32, the same 66 049 positions of the flat gradient bucket) the parameter gradients are stored
+        there, or added onto it with accumulate.  -> (p [B], dh [B,H,W,256] = d loss / d h)."""
+        _check_tensor(self, h, "disc_head map")
+        _check_tensor(self, params, "disc_head params")
+        _check_tensor(self, loss, "disc_head loss")
+        if h.dim() != 4 or h.shape[0] < 1 or h.shape[1] < 1 or h.shape[2] < 1:
+            raise ValueError(f"disc_head_step: the map must be [B,H,W,256], got {tuple(h.shape)}")
+        B, H, W, Cx = h.shape
+        if params.dim() != 1 or loss.numel() != 1:
+            raise ValueError("disc_head_step: params must be flat and loss one element")
+        if Cx != 256 or params.numel() != self.DISC_HEAD_PARAMS:
+            raise ValueError(f"disc_head_step: the head is 256 -> 256 -> 1: a 256-channel map and {self.DISC_HEAD_PARAMS} parameters expected")
+        if float(target) not in (0.0, 1.0):
+            raise ValueError("disc_head_step: the target is 0 or 1")
+        if grads is not None:
+            _check_tensor(self, grads, "disc_head grads")
+            if grads.dim() != 1 or grads.numel() != params.numel():
+                raise ValueError("disc_head_step: grads must match params")
+        elif accumulate:
+            raise ValueError("disc_head_step: accumulate needs grads")
+        p, dh = self.empty((B,)), torch.empty_like(h)
+        self.check(self.lib.sr_disc_head_step(self.h, h.data_ptr(), B, H, W, 256, 256, 1, params.data_ptr(), float(target), loss.data_ptr(), p.data_ptr(),
+                                              dh.data_ptr(), None if grads is None else grads.data_ptr(), int(bool(accumulate)), self.stream()))
+        return p, dh
+
     def softmax_rows_(self, s):
         """softmax over the last axis, in place."""
         _check_tensor(self, s, "softmax input")

@@ -2,7 +2,7 @@
 x4, NB=23, G=32, both SelfAttention layers, a batch of 16 LR patches 24x24 -> 96x96 per GPU, fp32 -- on sr355.gan_train.ESRGANTrainer.
 Prints one JSON line: ms per step, patches/s, the finite-loss check, and (N>1) the time of the flat-bucket gradient all-reduce.
 
-    python tools/bench_train.py [steps=3] [batch=16]
+    python tools/bench_train.py [steps=3] [batch=16] [host|device]          # third argument: where the discriminator's update runs
     python -m torch.distributed.run --nproc-per-node N ... tools/bench_train.py     # data parallel: every rank its own batch, gradients averaged
 
 Round 3: the generator's parameters, Adam moments and gradient bucket stay on the device (one fused optimiser kernel, RCCL reduces the
@@ -24,6 +24,7 @@ from sr355.bench_rows import cfg3_train_step
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 16
+disc = sys.argv[3] if len(sys.argv) > 3 else "host"
 local = 0 if os.environ.get("SR355_ONE_DEVICE") else int(os.environ.get("LOCAL_RANK", "0"))   # SR355_ONE_DEVICE: N>1 rehearsal on a 1-GPU box
 torch.cuda.set_device(local)
 rank, world, _ = D.init_from_env(backend=os.environ.get("SR355_DIST_BACKEND"))                 # "gloo" only for that rehearsal
@@ -48,12 +49,12 @@ def allreduce_flat(flat):
 
 
 D.barrier()
-row = cfg3_train_step(ctx, steps, batch, allreduce if world > 1 else None, allreduce_flat if world > 1 else None, seed_offset=rank)
+row = cfg3_train_step(ctx, steps, batch, allreduce if world > 1 else None, allreduce_flat if world > 1 else None, seed_offset=rank, discriminator=disc)
 t = torch.tensor([row.pop("wall_s")], dtype=torch.float64, device="cuda")
 D.allreduce_max(t)
 if rank == 0:
     wall = float(t.item())
-    row.update({"n_gpus": world, "ms_per_step": 1e3 * wall / steps, "patches_per_s": batch * world * steps / wall,
+    row.update({"discriminator": disc, "n_gpus": world, "ms_per_step": 1e3 * wall / steps, "patches_per_s": batch * world * steps / wall,
                 # the warm-up step's calls (RCCL communicator set-up among them) are reported on their own, not folded into the per-step figure
                 "allreduce_ms_per_step": (sum(allreduce_ms[len(allreduce_ms) // (steps + 1):]) / steps) if allreduce_ms else None,
                 "allreduce_ms_warmup_step": sum(allreduce_ms[:len(allreduce_ms) // (steps + 1)]) if allreduce_ms else None})
