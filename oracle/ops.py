@@ -261,10 +261,11 @@ def bicubic_resize(img, out_h, out_w, dtype=np.float32):
     return out[0] if squeeze else out
 
 
-def bicubic_resize_u8(img, out_h, out_w):
+def bicubic_resize_u8(img, out_h, out_w, preclip=False):
     """uint8 path of cv2.resize INTER_CUBIC: 11-bit fixed-point coefficients
     (INTER_RESIZE_COEF_BITS=11), int32 accumulation, rounding shift by 22, saturate
-    (super_resolucion_clasica.ipynb cell 7 feeds uint8)."""
+    (super_resolucion_clasica.ipynb cell 7 feeds uint8).  preclip=True returns the shifted integer sums
+    before the saturation (tests use it to show that an input drives them past both ends of [0, 255])."""
     img = np.asarray(img)
     assert img.dtype == np.uint8
     H, W, C = img.shape
@@ -280,6 +281,8 @@ def bicubic_resize_u8(img, out_h, out_w):
     for k in range(4):
         out += tmp[iy[:, k], :, :] * iwy[:, k, None, None]
     out = (out + (1 << 21)) >> 22
+    if preclip:
+        return out
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
@@ -409,10 +412,11 @@ def cv_resize(img, out_h, out_w, interpolation):
     return out[0] if squeeze else out
 
 
-def cv_resize_u8(img, out_h, out_w, interpolation):
+def cv_resize_u8(img, out_h, out_w, interpolation, preclip=False):
     """uint8 path of cv2.resize for INTER_LINEAR / INTER_AREA (enlarging) / INTER_LANCZOS4 / INTER_CUBIC: 11-bit fixed-point taps
     (saturate_cast<short>(w * 2048)), integer horizontal pass; vertical pass = OpenCV's VResizeLinear<uchar> special form for the
-    2-tap kernels, the generic 22-bit rounding shift otherwise."""
+    2-tap kernels, the generic 22-bit rounding shift otherwise.  preclip=True (fixed-point routes only) returns the integer
+    sums before the saturation."""
     img = np.asarray(img)
     assert img.dtype == np.uint8
     H, W, C = img.shape
@@ -439,6 +443,8 @@ def cv_resize_u8(img, out_h, out_w, interpolation):
         for k in range(iy.shape[1]):
             out += tmp[iy[:, k]] * iwy[:, k, None, None]
         out = (out + (1 << 21)) >> 22
+    if preclip:
+        return out
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
@@ -617,13 +623,13 @@ def extract_patches(image, patch, stride):
     return np.asarray([image[i:i + patch, j:j + patch, :] for i, j in pos], dtype=np.float32), pos
 
 
-def overlap_add(patches, positions, padded_hw, out_hw, patch, scale=1):
+def overlap_add(patches, positions, padded_hw, out_hw, patch, scale=1, dtype=np.float32):
     """Scatter-add patches + count, divide (0 where count==0), crop, clip[0,1]
-    (SRCNN_model.py:164-188, EDSR_model.py:225-256)."""
+    (SRCNN_model.py:164-188, EDSR_model.py:225-256).  The reference accumulates in float32; dtype=np.float64 is the tests' yardstick."""
     hp, wp = padded_hw[0] * scale, padded_hw[1] * scale
     ps = patch * scale
-    rec = np.zeros((hp, wp, 3), dtype=np.float32)
-    cnt = np.zeros((hp, wp, 3), dtype=np.float32)
+    rec = np.zeros((hp, wp, 3), dtype=dtype)
+    cnt = np.zeros((hp, wp, 3), dtype=dtype)
     for p, (i, j) in zip(patches, positions):
         rec[i * scale:i * scale + ps, j * scale:j * scale + ps, :] += p
         cnt[i * scale:i * scale + ps, j * scale:j * scale + ps, :] += 1.0
