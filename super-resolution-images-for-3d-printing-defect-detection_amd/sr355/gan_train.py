@@ -11,10 +11,12 @@ The forward and backward passes are host orchestration over the C ABI's single o
     softmax-backward kernel; pooling / stride-2 sampling / depth_to_space / activations / the (W,C)-FFT loss have their own adjoint kernels;
   * a minimal reverse-mode tape (below) keeps the graph bookkeeping out of the kernels; torch is used for memory only (cat / slice /
     flip / expand: data movement).
-The discriminator's tiny vectors -- its [B,256] dense head, BCE on [B,1], spectral-norm power iteration, Adam -- run on the host in NumPy by
-default (discriminator="host": its parameters are uploaded after every renormalisation) or, with discriminator="device", on the device:
-the parameters, u and Adam's moments stay in flat device buckets, one launch renormalises all eight kernels (sr_spectral_norm_bucket), two
-run the head with its loss and backward (sr_disc_head_step), and the step's six loss scalars come back in one copy (csrc/disc_train.hip).
+ESRGANTrainer.train_step is ONE body for both homes of the discriminator's tiny vectors -- its [B,256] dense head, BCE on [B,1], spectral-norm
+power iteration, Adam.  It talks to a discriminator object: three critic() calls (one training=True call each: renormalise, six convs
+(disc_trunk), head, BCE, backward) and one update().  HostDiscriminator (discriminator="host", the default) keeps them on the host in NumPy
+and uploads its parameters after every renormalisation; DeviceDiscriminator (discriminator="device") keeps the parameters, u and Adam's
+moments in flat device buckets: one launch renormalises all eight kernels (sr_spectral_norm_bucket), two run the head with its loss and
+backward (sr_disc_head_step), and the step's six loss scalars come back in one copy (csrc/disc_train.hip).
 The generator's parameters are device-resident in both modes; kernels are packed into MFMA fragment order on the device per layer call
 (sr_conv2d_dev); the tape bookkeeping stays on the host.  cfg3's throughput is the `cfg3 ESRGAN _train_step` row of bench.py --full
 (sr355/bench_rows.py cfg3_train_step), and tools/bench_train.py measures it alone, in either mode.
@@ -267,41 +269,15 @@ def spectral_normalize(kernel, u):
     return (kernel / np.float32(sigma)).astype(np.float32), u.astype(np.float32)
 
 
-def discriminator_forward(t, x, training, u=None):
-    """ESRGAN_model.py:347-377 on the tape.  training=True first renormalises every stored kernel in place (t.w and u are updated).
-    Returns (probabilities np [B,1], backward(dp) -> None that seeds the tape with d loss / d probabilities)."""
-    ctx = t.ctx
-    if training:
-        for n in DISC_LAYERS:
-            k, nu = spectral_normalize(t.w[n][0], u[n])
-            t.w[n], u[n] = (k, t.w[n][1]), nu
+def disc_trunk(t, x):
+    """The six convs of ESRGAN_model.py:347-377 on the tape (the strided ones as a stride-1 conv and a pick of every second pixel)
+    -> Var [B,H/8,W/8,256], the map the head pools."""
     h = x
     for i, st in enumerate(DISC_STRIDES):
         h = t.conv(h, f"disc_conv{i + 1}", act="lrelu")
         if st == 2:
             h = t.pick2(h)
-    B, H, W, C = h.v.shape
-    g = ctx.spatial_op(L.SP_GAP, h.v).cpu().numpy().astype(np.float64)          # [B,256]: the head runs on the host
-    k1, b1 = (a.astype(np.float64) for a in t.w["disc_dense1"])
-    k2, b2 = (a.astype(np.float64) for a in t.w["disc_output"])
-    z1 = g @ k1 + b1
-    a1 = np.where(z1 > 0, z1, 0.2 * z1)
-    z2 = a1 @ k2 + b2
-    p = 1.0 / (1.0 + np.exp(-z2))
-
-    def seed(dp):
-        """dp = d loss / d p  [B,1]."""
-        dz2 = dp * p * (1.0 - p)
-        if t.wgrad:
-            t.grads["disc_output"] = [a1.T @ dz2, dz2.sum(axis=0)]
-        da1 = dz2 @ k2.T
-        dz1 = np.where(z1 > 0, da1, 0.2 * da1)
-        if t.wgrad:
-            t.grads["disc_dense1"] = [g.T @ dz1, dz1.sum(axis=0)]
-        dg = (dz1 @ k1.T) / float(H * W)                                         # GAP backward: spread over the H x W map
-        dgt = ctx.to_device(dg.astype(np.float32))
-        h.g = dgt[:, None, None, :].expand(B, H, W, C).contiguous()
-    return p, seed
+    return h
 
 
 VGG19_CFG = [(1, 2, 64), (2, 2, 128), (3, 4, 256), (4, 4, 512), (5, 4, 512)]
@@ -340,83 +316,114 @@ def staircase_lr(lr0, step, decay_steps=10000, decay_rate=0.5):
     return lr0 * decay_rate ** (step // decay_steps)
 
 
-# ----------------------------------------------------------------------------------------------------------------- the step
-class ESRGANTrainer:
-    """Holds generator / discriminator / VGG19 weights, the SN vectors u, the two Adam states and the step counter.  discriminator="host"
-    (default): the discriminator's weights, u and Adam live on the host in NumPy; "device": in flat device buckets (_init_device_discriminator)."""
+# ----------------------------------------------------------------------------------------------------------------- the discriminator
+# One class per home of the discriminator's state; ESRGANTrainer.train_step sees the same surface of both:
+#   weights, u, opt, params: host arrays {layer: (kernel, bias)} / {layer: [1,Cout]} to read and to write (a write keeps Adam's moments), the
+#       optimiser, and the parameters' flat device bucket or None;
+#   critic(x, target, wgrad, masks, devcache) -> loss: one training=True call -- renormalise every kernel, trunk, head, BCE against `target`,
+#       backward (x.g is set when x.need); with wgrad the call's parameter gradients are added to the step's accumulator;
+#   update(lr, allreduce, allreduce_flat): average the accumulated gradient over the ranks, apply Adam, keep the gradient for last_grads().
+class HostDiscriminator:
+    """discriminator="host": weights, u and Adam in NumPy.  The six convs run on the device -- every renormalised kernel is uploaded --, the
+    [B,256] head, its BCE and their backward on the host in fp64; critic's loss is a Python float."""
 
-    def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None, discriminator="host"):
-        if discriminator not in ("host", "device"):
-            raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
-        self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
-        self.discriminator = discriminator
-        self.d_params = None                               # discriminator="device": the discriminator's flat device bucket (below)
-        # Generator (16.9 M parameters at the default depth): resident on the device as ONE flat fp32 bucket with its Adam moments beside it;
-        # the per-layer tensors the tape multiplies with are views of it, the gradients are gathered into a bucket of the same order, and
-        # the optimiser is one fused kernel (round 2: NumPy Adam on the host, 65 ms of a 258 ms step, plus 70 MB each way over PCIe).
-        # `self.gw` stays available as host arrays: they are refreshed from the device when somebody reads them.
-        self.g_params = ParamBucket(ctx, g_weights)
-        # d_weights / vgg_weights None: a generator-only trainer (pixel_step: sr355.recipes' L1 fit); train_step then refuses
-        self.dw = None if d_weights is None else {n: (np.asarray(k, np.float32), np.asarray(b, np.float32)) for n, (k, b) in d_weights.items()}
-        self.vw = vgg_weights
-        self._vgg = self._vgg_src = None                   # the frozen VGG19 on the device (a bucket of self.vw), uploaded by train_step
-        rng = np.random.default_rng(u_seed)               # tfa initialises u ~ TruncatedNormal(stddev 0.02), shape [1, Cout]
-        self.u = None if self.dw is None else {n: np.clip(rng.normal(0, 0.02, (1, self.dw[n][0].shape[-1])), -0.04, 0.04).astype(np.float32)
-                                               for n in DISC_LAYERS}
-        self.g_lr0, self.d_lr0 = g_lr, d_lr
-        self.g_opt = DeviceAdam(ctx, self.g_params.flat, g_lr, epsilon=1e-7)
-        if discriminator == "device" and self.dw is not None:
-            self._init_device_discriminator()
-        else:
-            self.d_opt = None if self.dw is None else Adam(self.dw, d_lr, epsilon=1e-7)
-        self.step = 0
-        # data parallel: `allreduce` = callable(dict of host grads) -> averaged dict (the discriminator's, whose spectral normalisation lives on
-        # the host); `allreduce_flat` = callable(flat device tensor) -> averaged tensor for the generator's bucket (RCCL reduces it where it
-        # lies).  With only `allreduce` given the generator's bucket takes the dict route too (the gloo CPU tests).  discriminator="device":
-        # the discriminator's gradients are a flat device bucket as well and take the same two routes as the generator's.
-        self.allreduce, self.allreduce_flat = allreduce, allreduce_flat
-        self._last = None
-        self._packs = {}
+    params = None
 
-    def _init_device_discriminator(self):
-        """discriminator="device": the discriminator's parameters as ONE flat device bucket in DISC_LAYERS order (the head's four arrays are its
-        last 66 049 values), u as one flat device tensor (the layers' [1,Cout] vectors one after the other: 961 floats), Adam's moments beside
-        them.  `dw` and `u` stay readable as host arrays: they are refreshed from the device when somebody reads them."""
-        ctx = self.ctx
-        dw, u = self._dw, self._u
-        self.d_params = ParamBucket(ctx, {n: dw[n] for n in DISC_LAYERS})
-        self._dw = self._u = None
+    def __init__(self, ctx, weights, u, lr):
+        self.ctx, self.weights, self.u = ctx, weights, u
+        self.opt = Adam(weights, lr, epsilon=1e-7)
+        self._grads = self._applied = None
+
+    def critic(self, x, target, wgrad=True, masks=None, devcache=None):
+        ctx, w = self.ctx, self.weights
+        for n in DISC_LAYERS:                               # in place: `weights` stays the dict its owner handed in
+            k, self.u[n] = spectral_normalize(w[n][0], self.u[n])
+            w[n] = (k, w[n][1])
+        t = Tape(ctx, w, wgrad=wgrad, devcache=devcache)
+        t.masks = masks
+        h = disc_trunk(t, x)
+        B, H, W, C = h.v.shape
+        g = ctx.spatial_op(L.SP_GAP, h.v).cpu().numpy().astype(np.float64)          # [B,256]: the head runs on the host
+        k1, b1 = (a.astype(np.float64) for a in w["disc_dense1"])
+        k2, b2 = (a.astype(np.float64) for a in w["disc_output"])
+        z1 = g @ k1 + b1
+        a1 = np.where(z1 > 0, z1, 0.2 * z1)
+        z2 = a1 @ k2 + b2
+        p = 1.0 / (1.0 + np.exp(-z2))
+        loss, dp = bce_mean(np.full_like(p, target), p)
+        dz2 = dp * p * (1.0 - p)
+        if wgrad:
+            t.grads["disc_output"] = [a1.T @ dz2, dz2.sum(axis=0)]
+        da1 = dz2 @ k2.T
+        dz1 = np.where(z1 > 0, da1, 0.2 * da1)
+        if wgrad:
+            t.grads["disc_dense1"] = [g.T @ dz1, dz1.sum(axis=0)]
+        dg = (dz1 @ k1.T) / float(H * W)                                             # GAP backward: spread over the H x W map
+        h.g = ctx.to_device(dg.astype(np.float32))[:, None, None, :].expand(B, H, W, C).contiguous()
+        t.backward()
+        if wgrad:
+            new, acc = self._host(t.grads), self._grads
+            self._grads = new if acc is None else {n: (acc[n][0] + new[n][0], acc[n][1] + new[n][1]) for n in acc}
+        return loss
+
+    @staticmethod
+    def _host(grads):
+        """{layer: [dk, db]} (device tensors; host arrays for the dense head) -> host fp32 arrays; the device ones cross PCIe as ONE flat buffer."""
+        out = {n: [None if isinstance(a, torch.Tensor) else np.asarray(a, np.float32) for a in pair] for n, pair in grads.items()}
+        dev = [(n, s) for n in out for s in (0, 1) if out[n][s] is None]
+        flat, o = torch.cat([grads[n][s].reshape(-1) for n, s in dev]).cpu().numpy(), 0
+        for n, s in dev:
+            t = grads[n][s]
+            out[n][s] = flat[o:o + t.numel()].reshape(tuple(t.shape))
+            o += t.numel()
+        return {n: tuple(pair) for n, pair in out.items()}
+
+    def update(self, lr, allreduce=None, allreduce_flat=None):
+        """The host discriminator's gradients are a dict and take the dict route only: with `allreduce_flat` alone they stay unreduced."""
+        grads, self._grads = self._grads, None
+        if allreduce is not None:
+            grads = allreduce(grads)
+        self.opt.lr = lr
+        self.weights = self.opt.apply(self.weights, grads)
+        self._applied = grads
+
+    def last_grads(self):
+        return self._applied
+
+
+class DeviceDiscriminator:
+    """discriminator="device": the parameters as ONE flat device bucket in DISC_LAYERS order (the head's four arrays are its last 66 049
+    values), u as one flat device tensor (the layers' [1,Cout] vectors one after the other: 961 floats), Adam's moments beside them.
+    `weights`, `u` and last_grads() are host arrays refreshed from the device when somebody reads them; critic's loss is a one-element
+    device tensor, a slot of `_losses`, good until the same kind of call comes again."""
+
+    def __init__(self, ctx, weights, u, lr):
+        self.ctx = ctx
+        self.params = ParamBucket(ctx, {n: weights[n] for n in DISC_LAYERS})
         self._u_host = np.concatenate([u[n].ravel() for n in DISC_LAYERS]).astype(np.float32)
         self._u_views, o = {}, 0
         for n in DISC_LAYERS:
             self._u_views[n] = self._u_host[o:o + u[n].size].reshape(1, -1)
             o += u[n].size
         self.u_flat, self._u_stale = ctx.to_device(self._u_host), False
-        self._sn_table, u_len = ctx.spectral_norm_table(self.d_params, DISC_LAYERS)
+        self._sn_table, u_len = ctx.spectral_norm_table(self.params, DISC_LAYERS)
         assert u_len == self._u_host.size
-        self.d_opt = DeviceAdam(ctx, self.d_params.flat, self.d_lr0, epsilon=1e-7)
-        self._head_off = self.d_params.flat.numel() - ctx.DISC_HEAD_PARAMS
-        self._d_head_g = ctx.empty((ctx.DISC_HEAD_PARAMS,))                # the head's slice of the gradient bucket: the real pass stores, the fake pass adds
-        self._losses = ctx.empty((3,))                                     # BCE of D(real) vs 1, D(fake) vs 0, D(fake) vs 1, until the end of the step
+        self.opt = DeviceAdam(ctx, self.params.flat, lr, epsilon=1e-7)
+        self._head_off = self.params.flat.numel() - ctx.DISC_HEAD_PARAMS
+        self._head_g = ctx.empty((ctx.DISC_HEAD_PARAMS,))                  # the head's slice of the gradient bucket: the first critic stores, the next add
+        self._losses = ctx.empty((3,))                                     # BCE of the step's first wgrad critic, of its later ones, of the one without wgrad
+        self._grads = self._applied = None
 
     @property
-    def dw(self):
-        """{layer: (kernel, bias)} host arrays of the discriminator's parameters (device mode: refreshed from the bucket when it has moved on)."""
-        return self._dw if self.d_params is None else self.d_params.host()
+    def weights(self):
+        return self.params.host()
 
-    @dw.setter
-    def dw(self, weights):
-        if self.d_params is None:
-            self._dw = weights
-        else:                                              # ESRGAN.set_loss_network_weights on a live trainer: Adam's moments and u stay
-            self.d_params.load({n: weights[n] for n in DISC_LAYERS})
+    @weights.setter
+    def weights(self, weights):                            # ESRGAN.set_loss_network_weights on a live trainer: Adam's moments and u stay
+        self.params.load({n: weights[n] for n in DISC_LAYERS})
 
     @property
     def u(self):
-        """{layer: [1,Cout]} host arrays of the power-iteration vectors (device mode: refreshed from the device when they have moved on)."""
-        if self.d_params is None:
-            return self._u
         if self._u_stale:
             self._u_host[:] = self.u_flat.cpu().numpy()
             self._u_stale = False
@@ -424,12 +431,101 @@ class ESRGANTrainer:
 
     @u.setter
     def u(self, u):
-        if self.d_params is None:
-            self._u = u
-        else:
-            self._u_host[:] = np.concatenate([np.asarray(u[n], np.float32).ravel() for n in DISC_LAYERS])
-            self.u_flat.copy_(self.ctx.to_device(self._u_host))
-            self._u_stale = False
+        self._u_host[:] = np.concatenate([np.asarray(u[n], np.float32).ravel() for n in DISC_LAYERS])
+        self.u_flat.copy_(self.ctx.to_device(self._u_host))
+        self._u_stale = False
+
+    def critic(self, x, target, wgrad=True, masks=None, devcache=None):
+        """One launch renormalises the eight kernels where they lie, the six convs run on the bucket's views (`devcache` is not needed), the
+        head op writes the BCE and d loss / d h, and the tape runs back."""
+        ctx, P = self.ctx, self.params
+        ctx.spectral_norm_bucket(P.flat, self.u_flat, self._sn_table)
+        P.stale = self._u_stale = True
+        t = Tape(ctx, P.arrays, wgrad=wgrad, devcache=dict(P.devcache))
+        t.masks = masks
+        h = disc_trunk(t, x)
+        accumulate = wgrad and self._grads is not None
+        slot = int(accumulate) if wgrad else 2
+        loss = self._losses[slot:slot + 1]
+        _, h.g = ctx.disc_head_step(h.v, P.flat[self._head_off:], target, loss, self._head_g if wgrad else None, accumulate)
+        t.backward()
+        if wgrad:                                          # the passes' gradients meet in one flat bucket (the head's through its accumulate flag)
+            g = P.gather(t.grads)
+            self._grads = ctx.eltwise(L.ELT_AXPBY, self._grads, g, 1.0, 1.0) if accumulate else g
+        return loss
+
+    def update(self, lr, allreduce=None, allreduce_flat=None):
+        """The flat gradient bucket takes the generator's two routes: `allreduce_flat` where it lies, else `allreduce` as a host dict."""
+        P = self.params
+        d_flat, self._grads = self._grads, None
+        d_flat[self._head_off:].copy_(self._head_g)
+        if allreduce_flat is not None:
+            d_flat = allreduce_flat(d_flat)
+        elif allreduce is not None:                        # dict route (host): the 2-rank gloo tests
+            d_flat = self.ctx.to_device(P.flatten(allreduce(P.split(d_flat.cpu().numpy()))))
+        self.opt.lr = lr
+        self.opt.apply(P.flat, d_flat)
+        P.stale = True
+        self._applied = d_flat
+
+    def last_grads(self):
+        if isinstance(self._applied, torch.Tensor):        # downloaded on first use
+            self._applied = self.params.split(self._applied.cpu().numpy())
+        return self._applied
+
+
+# ----------------------------------------------------------------------------------------------------------------- the step
+def _floats(values):
+    """Python floats and one-element device tensors -> Python floats; the tensors come over in ONE read."""
+    dev = [v for v in values if isinstance(v, torch.Tensor)]
+    read = iter(torch.cat(dev).cpu().numpy())
+    return [float(next(read)) if isinstance(v, torch.Tensor) else v for v in values]
+
+
+def _discriminator_attr(name):
+    """ESRGANTrainer's `dw` / `u` / `d_opt` / `d_params`: the discriminator object's attribute; None on a generator-only trainer."""
+    return property(lambda self: getattr(self.disc, name, None), lambda self, value: setattr(self.disc, name, value))
+
+
+class ESRGANTrainer:
+    """Holds generator / discriminator / VGG19 weights, the SN vectors u, the two Adam states and the step counter.  The discriminator's share
+    lives in `disc`, a HostDiscriminator (discriminator="host", the default) or a DeviceDiscriminator ("device"); `dw`, `u`, `d_opt` and
+    `d_params` are its `weights`, `u`, `opt` and `params`."""
+
+    dw, u, d_opt, d_params = (_discriminator_attr(name) for name in ("weights", "u", "opt", "params"))
+
+    def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
+                 allreduce_flat=None, discriminator="host"):
+        if discriminator not in ("host", "device"):
+            raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
+        self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
+        self.discriminator = discriminator
+        # Generator (16.9 M parameters at the default depth): resident on the device as ONE flat fp32 bucket with its Adam moments beside it;
+        # the per-layer tensors the tape multiplies with are views of it, the gradients are gathered into a bucket of the same order, and
+        # the optimiser is one fused kernel (round 2: NumPy Adam on the host, 65 ms of a 258 ms step, plus 70 MB each way over PCIe).
+        # `self.gw` stays available as host arrays: they are refreshed from the device when somebody reads them.
+        self.g_params = ParamBucket(ctx, g_weights)
+        self.vw = vgg_weights
+        self._vgg = self._vgg_src = None                   # the frozen VGG19 on the device (a bucket of self.vw), uploaded by train_step
+        self.g_lr0, self.d_lr0 = g_lr, d_lr
+        self.g_opt = DeviceAdam(ctx, self.g_params.flat, g_lr, epsilon=1e-7)
+        # d_weights / vgg_weights None: a generator-only trainer (pixel_step: sr355.recipes' L1 fit); it has no discriminator object and train_step refuses
+        self.disc = None
+        if d_weights is not None:
+            dw = {n: (np.asarray(k, np.float32), np.asarray(b, np.float32)) for n, (k, b) in d_weights.items()}
+            rng = np.random.default_rng(u_seed)           # tfa initialises u ~ TruncatedNormal(stddev 0.02), shape [1, Cout]
+            u = {n: np.clip(rng.normal(0, 0.02, (1, dw[n][0].shape[-1])), -0.04, 0.04).astype(np.float32) for n in DISC_LAYERS}
+            self.disc = (DeviceDiscriminator if discriminator == "device" else HostDiscriminator)(ctx, dw, u, d_lr)
+        self.step = 0
+        # data parallel: `allreduce` = callable(dict of host grads) -> averaged dict (the host discriminator's, whose spectral normalisation lives
+        # there); `allreduce_flat` = callable(flat device tensor) -> averaged tensor for the generator's bucket (RCCL reduces it where it
+        # lies).  With only `allreduce` given the generator's bucket takes the dict route too (the gloo CPU tests).  The device discriminator's
+        # gradients are a flat device bucket as well and take the same two routes as the generator's.
+        self.allreduce, self.allreduce_flat = allreduce, allreduce_flat
+        self.collect_masks = False                         # tests: keep the activation branches of a step's forward passes in last_masks (oracle/train.py _masked_act)
+        self.last_masks = self.last_dy = self.last_fake = None
+        self._last = None
+        self._packs = {}
 
     @contextlib.contextmanager
     def _prepacked(self, with_vgg):
@@ -473,14 +569,13 @@ class ESRGANTrainer:
 
     @property
     def last_grads(self):
-        """{"g": {layer: (dk, db)}, "d": {...}} host arrays of the last step (the generator's are downloaded on first use)."""
+        """{"g": {layer: (dk, db)}, "d": {...}} host arrays of the last step (the generator's, and a device discriminator's, are downloaded on first use)."""
         if self._last is None:
             return None
         if "g" not in self._last:
             full = self.g_params.split(self._last.pop("g_flat").cpu().numpy())
             self._last["g"] = {n: full[n] for n in full if n in self._last["g_names"]}     # only the variables the loss reaches, as Keras reports them
-        if "d" not in self._last:                          # discriminator="device": the same, from its bucket
-            self._last["d"] = self.d_params.split(self._last.pop("d_flat").cpu().numpy())
+        self._last["d"] = self.disc.last_grads()
         return self._last
 
     def _update_generator(self, grads):
@@ -495,24 +590,6 @@ class ESRGANTrainer:
         self.g_params.stale = True
         self.step += 1
         return g_flat
-
-    def _host(self, grads):
-        """{layer: [dk, db]} (device tensors, or host arrays for the discriminator's dense head) -> host fp32 arrays; the device ones
-        cross PCIe as ONE flat buffer."""
-        dev = [(n, s) for n, pair in grads.items() for s in (0, 1) if isinstance(pair[s], torch.Tensor)]
-        out = {n: [None, None] for n in grads}
-        if dev:
-            flat = torch.cat([grads[n][s].reshape(-1) for n, s in dev]).cpu().numpy()
-            o = 0
-            for n, s in dev:
-                t = grads[n][s]
-                out[n][s] = flat[o:o + t.numel()].reshape(tuple(t.shape))
-                o += t.numel()
-        for n, pair in grads.items():
-            for s in (0, 1):
-                if out[n][s] is None:
-                    out[n][s] = np.asarray(pair[s], np.float32)
-        return {n: (a, b) for n, (a, b) in out.items()}
 
     def pixel_step(self, lr_images, hr_images):
         """One generator update on the pixel loss alone (mean |hr - G(lr)|, ESRGAN_model.py:433-445; the generator half of _train_step,
@@ -529,147 +606,59 @@ class ESRGANTrainer:
         return pix
 
     def train_step(self, lr_images, hr_images):
-        """-> {'g_loss', 'd_loss', parts...}; weights, u, optimiser states advance in place (ESRGAN_model.py:475-533)."""
-        if (self.d_params is None and self._dw is None) or self.vw is None:      # not `self.dw`: in device mode reading it downloads the bucket
+        """-> {'g_loss', 'd_loss', parts...}; weights, u, optimiser states advance in place (ESRGAN_model.py:475-533).  With a device
+        discriminator the step issues two uploads (the image batches) and one read (the six loss scalars)."""
+        if self.disc is None or self.vw is None:
             raise RuntimeError("ESRGANTrainer was built without discriminator / VGG19 weights: only pixel_step is available")
         if self._vgg_src is not self.vw:                  # the first step, or ESRGAN.set_loss_network_weights has replaced the VGG19 weights
             self._vgg, self._vgg_src = ParamBucket(self.ctx, self.vw), self.vw
             self._packs.pop(True, None)
+        ctx, disc = self.ctx, self.disc
         with self._prepacked(True):                        # the generator's weights change only in the step's last lines, VGG19's never
-            if self.d_params is not None:
-                return self._train_step_device(lr_images, hr_images)
-            return self._train_step(lr_images, hr_images)
+            lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
+            # The reference runs the generator twice per step, once under each tape (ESRGAN_model.py:490, :508); its weights do not change
+            # in between (the discriminator is updated first), so both runs are the same tensor: one taped forward serves both.
+            tg = self.generator_tape()
+            masks = {"g": {}, "d_real": {}, "d_fake": {}} if self.collect_masks else {}
+            self.last_masks = masks or None
+            tg.masks = masks.get("g")
+            y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
+            fake = y.v
+            # ---- discriminator update (tg.dev: a host discriminator's tapes add this step's uploads of its arrays, one per array)
+            l_real = disc.critic(Var(hr_t, need=False), 1.0, masks=masks.get("d_real"), devcache=tg.dev)      # renormalisation 1
+            l_fake = disc.critic(Var(fake, need=False), 0.0, masks=masks.get("d_fake"), devcache=tg.dev)      # renormalisation 2
+            disc.update(staircase_lr(self.d_lr0, self.step), self.allreduce, self.allreduce_flat)
+            # ---- generator update
+            yv = Var(fake)
+            adv = disc.critic(yv, 1.0, wgrad=False, devcache=tg.dev)                                           # renormalisation 3
+            perc, pix, spec, dy = self._content_terms(hr_t, fake, yv.g)
+            # The one place where the step's loss scalars become floats, and the step's last read.  It waits for what has been launched so far, so it
+            # stands before the generator's backward is queued (where the host mode always read perc / pix / spec), not after it: behind that backward,
+            # most of the step's launches, the same read measured 0.5-0.7 ms a step slower in host mode, 0.3 ms in device mode (profiles/one_train_step_aba.txt).
+            l_real, l_fake, adv, perc, pix, spec = _floats([l_real, l_fake, adv, perc, pix, spec])
+            y.g = self.last_dy = dy
+            tg.backward()
+            self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads)}
+            self.last_fake = fake
+        return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
+                "pixel": pix, "spectral": spec}
 
-    def _discriminator_pass(self, x, target, slot, wgrad=True, accumulate=False, masks=None):
-        """One training=True call of the discriminator on its device bucket: one launch renormalises the eight kernels where they lie, the six
-        convs run on the bucket's views, the head op writes the BCE against `target` into loss slot `slot` and d loss / d h, and the tape runs
-        back.  -> the tape (its grads: the six convs'; the head's are in self._d_head_g)."""
-        ctx, P = self.ctx, self.d_params
-        ctx.spectral_norm_bucket(P.flat, self.u_flat, self._sn_table)
-        P.stale = self._u_stale = True
-        t = Tape(ctx, P.arrays, wgrad=wgrad, devcache=dict(P.devcache))
-        t.masks = masks
-        h = x
-        for i, st in enumerate(DISC_STRIDES):
-            h = t.conv(h, f"disc_conv{i + 1}", act="lrelu")
-            if st == 2:
-                h = t.pick2(h)
-        _, h.g = ctx.disc_head_step(h.v, P.flat[self._head_off:], target, self._losses[slot:slot + 1], self._d_head_g if wgrad else None, accumulate)
-        t.backward()
-        return t
-
-    def _train_step_device(self, lr_images, hr_images):
-        """_train_step with the discriminator's update on the device (discriminator="device"): the step issues two uploads (the image batches) and one
-        read (the six loss scalars, at its end); the discriminator's bucket is downloaded only when somebody reads `dw` / `u` / `last_grads`."""
-        ctx, P = self.ctx, self.d_params
-        lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
-        tg = self.generator_tape()
-        collect = getattr(self, "collect_masks", False)
-        self.last_masks = {"g": {}, "d_real": {}, "d_fake": {}} if collect else None
-        if collect:
-            tg.masks = self.last_masks["g"]
-        y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
-        fake = y.v
-        # ---- discriminator update: the two passes' gradients meet in one flat bucket (the head's through its accumulate flag)
-        td = self._discriminator_pass(Var(hr_t, need=False), 1.0, 0, masks=self.last_masks["d_real"] if collect else None)          # renormalisation 1
-        g_real = P.gather(td.grads)
-        td2 = self._discriminator_pass(Var(fake, need=False), 0.0, 1, accumulate=True, masks=self.last_masks["d_fake"] if collect else None)   # renormalisation 2
-        d_flat = ctx.eltwise(L.ELT_AXPBY, g_real, P.gather(td2.grads), 1.0, 1.0)
-        d_flat[self._head_off:].copy_(self._d_head_g)
-        if self.allreduce_flat is not None:
-            d_flat = self.allreduce_flat(d_flat)
-        elif self.allreduce is not None:                   # dict route (host): the 2-rank gloo tests
-            d_flat = ctx.to_device(P.flatten(self.allreduce(P.split(d_flat.cpu().numpy()))))
-        self.d_opt.lr = staircase_lr(self.d_lr0, self.step)
-        self.d_opt.apply(P.flat, d_flat)
-        P.stale = True
-        # ---- generator update
-        yv = Var(y.v)
-        self._discriminator_pass(yv, 1.0, 2, wgrad=False)                                         # renormalisation 3
+    def _content_terms(self, hr_t, fake, d_adv):
+        """The generator loss beside its adversarial term: VGG19 perceptual (x 1), pixel L1 (x 100) and spectral (x 1) of `fake` against hr_t
+        -> (perc, pix, spec as one-element device tensors, d g_loss / d fake: their gradients and d_adv, the adversarial term's)."""
+        ctx = self.ctx
         tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
         fr = vgg19_features(tv, Var(hr_t, need=False))
         tv.ops = []
-        yv2 = Var(y.v)
-        ff = vgg19_features(tv, yv2)
+        yv = Var(fake)
+        ff = vgg19_features(tv, yv)
         perc = ctx.mse(fr.v, ff.v)
         ff.g = ctx.eltwise(L.ELT_AXPBY, ff.v, fr.v, 2.0 / ff.v.numel(), -2.0 / ff.v.numel())
         tv.backward()
-        pix = ctx.l1(hr_t, y.v)
-        spec = ctx.spectral_l1(y.v, hr_t)
-        dy = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 100.0 / y.v.numel(), 0.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, ctx.spectral_l1_bwd(y.v, hr_t, 1.0), 1.0, 1.0)
+        pix = ctx.l1(hr_t, fake)
+        spec = ctx.spectral_l1(fake, hr_t)
+        dy = ctx.eltwise(L.ELT_SIGN_DIFF, fake, hr_t, 100.0 / fake.numel(), 0.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, ctx.spectral_l1_bwd(fake, hr_t, 1.0), 1.0, 1.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, d_adv, 1.0, 1.0)
         dy = ctx.eltwise(L.ELT_AXPBY, dy, yv.g, 1.0, 1.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv2.g, 1.0, 1.0)
-        y.g = dy
-        self.last_dy = dy
-        tg.backward()
-        self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads), "d_flat": d_flat}
-        self.last_fake = fake
-        l_real, l_fake, adv, perc, pix, spec = (float(v) for v in torch.cat([self._losses, perc, pix, spec]).cpu().numpy())    # the step's one read
-        return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
-                "pixel": pix, "spectral": spec}
-
-    def _train_step(self, lr_images, hr_images):
-        ctx = self.ctx
-        lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
-        # The reference runs the generator twice per step, once under each tape (ESRGAN_model.py:490, :508); its weights do not change
-        # in between (the discriminator is updated first), so both runs are the same tensor: one taped forward serves both.
-        tg = self.generator_tape()
-        devc = tg.dev                                      # the discriminator's tapes add this step's uploads of its arrays (one per array)
-        collect = getattr(self, "collect_masks", False)           # tests: the activation branches of this step's forward passes (oracle/train.py _masked_act)
-        self.last_masks = {"g": {}, "d_real": {}, "d_fake": {}} if collect else None
-        if collect:
-            tg.masks = self.last_masks["g"]
-        y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
-        fake = y.v
-        # ---- discriminator update
-        td = Tape(ctx, self.dw, devcache=devc)
-        if collect:
-            td.masks = self.last_masks["d_real"]
-        p_real, seed_real = discriminator_forward(td, Var(hr_t, need=False), True, self.u)       # renormalisation 1
-        l_real, dp = bce_mean(np.ones_like(p_real), p_real)
-        seed_real(dp)
-        td.backward()
-        g_real = self._host(td.grads)
-        td2 = Tape(ctx, self.dw, devcache=devc)
-        if collect:
-            td2.masks = self.last_masks["d_fake"]
-        p_fake, seed_fake = discriminator_forward(td2, Var(fake, need=False), True, self.u)      # renormalisation 2
-        l_fake, dp = bce_mean(np.zeros_like(p_fake), p_fake)
-        seed_fake(dp)
-        td2.backward()
-        g_fake = self._host(td2.grads)
-        d_grads = {n: (g_real[n][0] + g_fake[n][0], g_real[n][1] + g_fake[n][1]) for n in g_real}
-        if self.allreduce is not None:
-            d_grads = self.allreduce(d_grads)
-        self.d_opt.lr = staircase_lr(self.d_lr0, self.step)
-        self.dw = self.d_opt.apply(self.dw, d_grads)
-        # ---- generator update
-        td3 = Tape(ctx, self.dw, wgrad=False, devcache=devc)
-        yv = Var(y.v)
-        p, seed = discriminator_forward(td3, yv, True, self.u)                                   # renormalisation 3
-        self.dw = td3.w
-        adv, dp = bce_mean(np.ones_like(p), p)
-        seed(dp)
-        td3.backward()
-        tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
-        fr = vgg19_features(tv, Var(hr_t, need=False))
-        tv.ops = []
-        yv2 = Var(y.v)
-        ff = vgg19_features(tv, yv2)
-        perc = float(ctx.mse(fr.v, ff.v).item())
-        ff.g = ctx.eltwise(L.ELT_AXPBY, ff.v, fr.v, 2.0 / ff.v.numel(), -2.0 / ff.v.numel())
-        tv.backward()
-        pix = float(ctx.l1(hr_t, y.v).item())
-        spec = float(ctx.spectral_l1(y.v, hr_t).item())
-        dy = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 100.0 / y.v.numel(), 0.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, ctx.spectral_l1_bwd(y.v, hr_t, 1.0), 1.0, 1.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv.g, 1.0, 1.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv2.g, 1.0, 1.0)
-        y.g = dy
-        self.last_dy = dy
-        tg.backward()
-        self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads), "d": d_grads}
-        self.last_fake = fake
-        return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
-                "pixel": pix, "spectral": spec}
+        return perc, pix, spec, dy

@@ -311,17 +311,17 @@ def test_device_steps_do_not_download_the_bucket(ctx):
     gw, dw, vw = _gan_setup(scale, nb, G)
     lr, hr = _batch(scale)
     tr = GT.ESRGANTrainer(ctx, gw, dw, vw, scale, nb, attention=att, u_seed=3, discriminator="device")
-    h0, u0 = tr.d_params._hflat.copy(), tr._u_host.copy()
+    h0, u0 = tr.d_params._hflat.copy(), tr.disc._u_host.copy()
     calls = []
     host = tr.d_params.host
     tr.d_params.host = lambda: (calls.append(1), host())[1]
     tr.train_step(lr, hr)
     tr.train_step(lr, hr)
-    assert not calls and tr.d_params.stale and tr._u_stale
-    assert np.array_equal(tr.d_params._hflat, h0) and np.array_equal(tr._u_host, u0)
+    assert not calls and tr.d_params.stale and tr.disc._u_stale
+    assert np.array_equal(tr.d_params._hflat, h0) and np.array_equal(tr.disc._u_host, u0)
     moved = tr.dw["disc_conv1"][0]
     assert calls == [1] and not tr.d_params.stale and not np.array_equal(tr.d_params._hflat, h0) and np.array_equal(moved.ravel(), tr.d_params.flat[:moved.size].cpu().numpy())
-    assert not np.array_equal(np.concatenate([tr.u[n].ravel() for n in GT.DISC_LAYERS]), u0) and not tr._u_stale
+    assert not np.array_equal(np.concatenate([tr.u[n].ravel() for n in GT.DISC_LAYERS]), u0) and not tr.disc._u_stale
 
 
 # ------------------------------------------------------------------------------------------------ 5. host mode and device mode
