@@ -511,6 +511,42 @@ int  sr_spectral_norm_bucket(sr_ctx* ctx, float* bucket, int64_t bucket_len, flo
 int  sr_disc_head_step(sr_ctx* ctx, const float* h, int B, int H, int W, int in_dim, int hidden, int out_dim, const float* params, float target,
                        float* loss, float* p, float* dh, float* grads, int accumulate, void* stream);
 
+/* ---- LPIPS of image pairs: the dataset EDA's first metric (reference data/EDA.ipynb, ImageDatasetAnalyzer.lpips_score / loss_fn), csrc/lpips.hip ----
+ * lpips.LPIPS(net="alex"), version 0.1, spatial = False, eval mode.  The lpips package and torchvision are installed nowhere this project runs, so
+ * this restates their documented arithmetic and is not pinned against the packages themselves (the caveat the OpenCV paths above carry); the
+ * weights are the caller's (torchvision's AlexNet checkpoint and the package's alex.pth), as VGG16's and VGG19's are.
+ *   input     uint8 BGR [B,H,W,3] (SR_DTYPE_U8, the EDA's form): x = 2 (v / 255.0) - 1 in fp64, rounded to fp32, BGR -> RGB, then the scaling layer
+ *             (x - shift) / scale in fp32 with shift (-.030, -.088, -.188), scale (.458, .448, .450) per R, G, B -- all of it one host-built
+ *             [3][256] fp32 table (sr_lpips_input_table) looked up on the device.  fp32 RGB [B,H,W,3] in [-1, 1] (SR_DTYPE_F32): the scaling
+ *             layer only, a correctly rounded fp32 subtract and divide.
+ *   trunk     torchvision AlexNet `features`, fp32 with fp32 accumulation, floor arithmetic everywhere: conv1 3 -> 64, 11x11, stride 4, zero pad 2
+ *             (the zeros pad the scaled image), ReLU = tap 1; max-pool 3x3 stride 2; conv2 64 -> 192, 5x5, pad 2, ReLU = tap 2; max-pool 3x3
+ *             stride 2; conv3 192 -> 384, conv4 384 -> 256, conv5 256 -> 256, each 3x3, pad 1, ReLU = taps 3, 4, 5.  conv1's output size is
+ *             (n - 7) / 4 + 1, a pool's (n - 3) / 2 + 1; every map needs a pixel, so the smallest image is 31 x 31 (maps 7, 3, 3, 1, 1, 1, 1).
+ *             conv1 runs as a 3x3 conv over the 48 channels of the space-to-depth(4) image (csrc/lpips.hip states the identity).
+ *   distance  per tap with features fa, fb [h,w,C] and lin weights l[C]: n = f / (sqrt(sum_c f^2) + 1e-10); term = mean_{h,w} sum_c l_c (na_c - nb_c)^2;
+ *             score = the sum of the five terms, fp32.  A pixel whose channels are all zero normalises to zeros, never to NaN.
+ * sr_lpips_shapes: the five tap sizes hw[l] = {h_l, w_l} of an H x W image.  Pure: no context, no GPU.  SR_ERR_INVALID below 31 or above the EDA's
+ *   limits (H, W <= 4096, H W <= 2^22).
+ * sr_lpips_input_table: the uint8 form's [3][256] fp32 table, [c][v] for c = R, G, B (HOST, 768 floats).  Pure.
+ * sr_lpips_set_weights: conv_w[5] HOST fp32 HWIO [11,11,3,64], [5,5,64,192], [3,3,192,384], [3,3,384,256], [3,3,256,256]; conv_b[5] their
+ *   biases; lin_w[5] HOST fp32 [64], [192], [384], [256], [256].  Copies and packs for the kernels once (no per-call packing); the caller's arrays
+ *   are not kept.  All three NULL (or every entry NULL) unloads and frees; anything between is SR_ERR_INVALID.  Waits for the device.
+ * sr_lpips: a, b DEVICE [B,H,W,3] of `dtype` -> score_B DEVICE fp32 [B].  Optional (NULL: not written): terms_Bx5 DEVICE fp32 [B,5], the five
+ *   terms; taps HOST array of five DEVICE fp32 pointers (each may be NULL), taps[l] = [2,B,h_l,w_l,C_l], the raw ReLU features of a then of b
+ *   (16-byte aligned; for tests).  SR_ERR_STATE "the weights are not set" without weights; SR_ERR_INVALID, and no launch, for a shape
+ *   sr_lpips_shapes refuses, B < 1 or B > 2^20.  The 2 n images of n pairs go through the trunk as one batch; B pairs are processed in chunks
+ *   of n = min(SR_LPIPS_CHUNK_PAIRS, SR_LPIPS_WORK_BYTES / one pair's maps) pairs, at least one, so the workspace (counted in sr_mem_info,
+ *   kept between calls, freed with the weights) stays below SR_LPIPS_WORK_BYTES unless a single pair needs more (26.6 MB per pair at 478 x 478).
+ *   Launches only, asynchronous on `stream`.  Every sum runs in an order fixed by the map sizes (no atomics, no split-K): a pair's five terms
+ *   and score are the same bits on every run, for any B and at any position in the batch -- the guarantee sr_eda_pair_stats gives. */
+enum { SR_LPIPS_CHUNK_PAIRS = 64, SR_LPIPS_WORK_BYTES = 256 << 20 };
+int  sr_lpips_shapes(int H, int W, int hw[5][2]);
+int  sr_lpips_input_table(float* table_3x256);
+int  sr_lpips_set_weights(sr_ctx* ctx, const float* const conv_w[5], const float* const conv_b[5], const float* const lin_w[5]);
+int  sr_lpips(sr_ctx* ctx, const void* a, const void* b, int dtype, int B, int H, int W, float* score_B, float* terms_Bx5, float* const taps[5],
+              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

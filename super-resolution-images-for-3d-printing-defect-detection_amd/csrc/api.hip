@@ -670,6 +670,7 @@ void sr_destroy(sr_ctx* ctx) {
     DeviceGuard dg_(ctx);
     if (!ctx) return;
     (void)hipDeviceSynchronize();
+    lpips_release(ctx);
     std::vector<void*> ps;
     for (auto& kv : ctx->allocs) ps.push_back(kv.first);
     for (void* p : ps) ctx->dfree(p);

@@ -63,6 +63,8 @@ struct sr_ctx {
     Arena sn_work, sn_tab, dhead_work;  // disc_train.hip: the power iterations' t / partial column sums, the layer table, the head's per-row values between its two kernels
     std::vector<char> sn_tab_host;      // ... the layer table as last uploaded
     void* sn_tab_dev = nullptr;
+    struct LpipsState* lpips = nullptr; // lpips.hip: the packed AlexNet convs, the lin weights and the input table while weights are set (sr_lpips_set_weights)
+    Arena lpips_work;                   // lpips.hip: one chunk's maps and partial sums
     int* deg_status = nullptr;          // degrade.hip: {stage, row, value} of the first bad parameter-table row a kernel met (sr_degrade_status)
     void* arena(Arena& a, size_t bytes, hipStream_t st);   // grow-only; growing waits for `st` first
     // sr_conv_prepack: packed fp32 weights of a list of conv uses, written by one launch and found again by conv_pack_weights_dev
@@ -116,6 +118,8 @@ struct DeviceGuard {
         if (e_ != hipSuccess)                                                                    \
             return (ctx)->fail(SR_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
     } while (0)
+
+void lpips_release(sr_ctx* ctx);   // lpips.hip: frees the LPIPS state (sr_destroy)
 
 // OpenCV's 8-bit COLOR_BGR2GRAY (include/sr355.h, the EDA section): the one statement of it, for eda.hip and crop.hip
 __device__ inline int gray_bgr(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + 8192) >> 14; }

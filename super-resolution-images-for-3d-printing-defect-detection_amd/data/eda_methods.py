@@ -13,8 +13,12 @@ Each single-image method scores the pair (img, img) through the whole device pip
 return its one number or dict: fine for a notebook cell, wasteful in a loop -- collect / collect_arrays make one pass per batch and are
 the way to score a dataset.
 
-Out of scope: LPIPS (its AlexNet and LPIPS weights exist nowhere this project runs): the rows' lpips column is NaN, lpips_score raises
-NotImplementedError and nothing here sorts by LPIPS; every matplotlib / seaborn panel.  Importing this module and its host helpers
+LPIPS needs the user's two checkpoints (torchvision's AlexNet and the lpips package's alex.pth; they exist nowhere this project runs, as
+VGG16's and VGG19's do not): after ImageDatasetAnalyzer.load_lpips(alexnet_path, lpips_path) the device scores it (csrc/lpips.hip,
+Context.lpips) -- lpips_score returns the float, collect / collect_arrays fill the rows' lpips column in the same batch pass, loss_fn()
+returns the scoring callable and StatsReporter.lpips_scenarios gives the pipeline's best / worst file names.  The loaded state is
+process-wide and nothing loads it implicitly; until then, and after unload_lpips(), the lpips column is NaN and lpips_score and loss_fn
+raise NotImplementedError.  Out of scope: every matplotlib / seaborn panel.  Importing this module and its host helpers
 (ImagePairLoader.iter_pairs, ImagePairMetrics, StatsReporter) needs no GPU."""
 import math
 import os
@@ -123,8 +127,47 @@ class ImagePairLoader:
 class ImageDatasetAnalyzer:
     """The reference's static per-image metrics."""
 
+    _lpips_ctx = None      # the context whose LPIPS weights load_lpips set; None: not loaded
+
+    @staticmethod
+    def load_lpips(alexnet_path, lpips_path=None):
+        """Reads torchvision's AlexNet checkpoint and the lpips package's alex.pth (or one .npz holding both: sr355.lpips.load_weights)
+        and sets them on the device: from here on lpips_score, loss_fn and the rows' lpips column are served.  Process-wide."""
+        from sr355.lpips import load_weights
+        w = load_weights(alexnet_path, lpips_path)
+        ctx = _context()
+        ctx.lpips_set_weights(w)
+        ImageDatasetAnalyzer._lpips_ctx = ctx
+
+    @staticmethod
+    def unload_lpips():
+        ctx, ImageDatasetAnalyzer._lpips_ctx = ImageDatasetAnalyzer._lpips_ctx, None
+        if ctx is not None:
+            ctx.lpips_set_weights(None)
+
+    @staticmethod
+    def loss_fn():
+        """The reference's name for the LPIPS model: a callable scoring two float tensors [B,3,H,W] in [-1, 1] (lpips_score's to_tensor
+        form) -> float32 [B,1,1,1] on the device.  NotImplementedError until load_lpips."""
+        ctx = ImageDatasetAnalyzer._lpips_ctx
+        if ctx is None:
+            raise NotImplementedError("loss_fn: LPIPS needs torchvision's AlexNet checkpoint and the lpips package's alex.pth: call "
+                                      "ImageDatasetAnalyzer.load_lpips(alexnet_path, lpips_path) first")
+
+        def score(a, b):
+            import torch
+            nhwc = lambda t: ctx.to_device(torch.as_tensor(t), torch.float32).permute(0, 2, 3, 1).contiguous()
+            return ctx.lpips(nhwc(a), nhwc(b)).reshape(-1, 1, 1, 1)
+
+        return score
+
     @staticmethod
     def lpips_score(lr_img, hr_img):
+        ctx = ImageDatasetAnalyzer._lpips_ctx
+        if ctx is not None:
+            lr, hr = _bgr(lr_img, "lpips_score"), _bgr(hr_img, "lpips_score")
+            return float(ctx.lpips(ctx.to_device(lr[None]), ctx.to_device(hr[None]))[0])
+        # not loaded (load_lpips): the message this method has always raised
         raise NotImplementedError("lpips_score: LPIPS needs AlexNet and LPIPS weights that are not available here; it is out of this port's scope "
                                   "(the rows' lpips column is NaN)")
 
@@ -235,8 +278,9 @@ class MetricsAggregator:
         cols = _row_columns()
         stats = ctx.eda_pair_stats(lr, hr, glcm_levels, (0, 1, 2, 3) if glcm_multi_angle else (0,))
         acc = ctx.eda_accumulate(lr, hr, device_acc)
+        lp = ImageDatasetAnalyzer._lpips_ctx.lpips(lr, hr).cpu().numpy() if ImageDatasetAnalyzer._lpips_ctx is not None else None   # same batch pass
         host = stats.cpu().numpy()
-        rows = [ImagePairMetrics(filename=names[i].replace("\\", "/"), lpips=math.nan, **{k: float(host[i, j]) for j, k in enumerate(cols)}) for i in range(B)]
+        rows = [ImagePairMetrics(filename=names[i].replace("\\", "/"), lpips=math.nan if lp is None else float(lp[i]), **{k: float(host[i, j]) for j, k in enumerate(cols)}) for i in range(B)]
         g = MetricsAggregator.new_global_data()
         g["count"] = B
         g["noise_means_lr"] = [r.color_noise_lr for r in rows]
@@ -304,6 +348,19 @@ class StatsReporter:
             numeric = all(v is None or isinstance(v, (int, float, np.integer, np.floating)) for v in vals)
             out[k] = np.array([math.nan if v is None else float(v) for v in vals], np.float64) if numeric else np.array(vals, dtype=object)
         return out
+
+    @staticmethod
+    def lpips_scenarios(df, top_k=1):
+        """run_eda_pipeline's df.sort_values("lpips") head and tail -> (best, worst) lists of file names, top_k each (fewer when there
+        are fewer rows).  The sort is stable (ties keep row order) and NaN sorts last, as pandas' does; ValueError when every value is
+        NaN (nothing was scored: load_lpips)."""
+        vals = np.asarray(df["lpips"], dtype=np.float64)
+        if vals.size == 0 or np.isnan(vals).all():
+            raise ValueError("lpips_scenarios: the lpips column holds no score (ImageDatasetAnalyzer.load_lpips was not called)")
+        order = np.argsort(vals, kind="stable")
+        k = min(max(int(top_k), 0), vals.size)
+        names = [str(f) for f in np.asarray(df["filename"], dtype=object)]
+        return [names[i] for i in order[:k]], [names[i] for i in order[vals.size - k:]]
 
     @staticmethod
     def summary(df):

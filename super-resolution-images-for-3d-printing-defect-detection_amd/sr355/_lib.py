@@ -124,6 +124,10 @@ SIGNATURES = {
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
     "sr_spectral_norm_bucket": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(SnDesc), _i, _vp]),
     "sr_disc_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sr_lpips_shapes": (_i, [_i, _i, C.POINTER(_i)]),
+    "sr_lpips_input_table": (_i, [_fp]),
+    "sr_lpips_set_weights": (_i, [_vp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]),
+    "sr_lpips": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), _vp]),
 }
 
 # the columns of sr_classic_scores (SR_SCORE_* in include/sr355.h)

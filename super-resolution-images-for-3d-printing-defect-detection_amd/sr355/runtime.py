@@ -424,6 +424,37 @@ class Context:
                                               acc["grad_hr_sum"].data_ptr(), acc["glcm_sum"].data_ptr(), acc["sat_counts"].data_ptr(), self.stream()))
         return acc
 
+    # ------------------------------------------------------------------ LPIPS (data/EDA.ipynb lpips_score; csrc/lpips.hip)
+    def lpips_set_weights(self, weights):
+        """Sets (a dict from sr355.lpips.load_weights / seeded_weights) or, with None, unloads the weights of lpips / sr_lpips on this context.
+        The library copies and packs them once."""
+        if weights is None:
+            self.check(self.lib.sr_lpips_set_weights(self.h, None, None, None))
+            return
+        from .lpips import check_weights
+        w = check_weights(weights)
+        arr = lambda k: (C.POINTER(C.c_float) * 5)(*[_fptr(a) for a in w[k]])
+        self.check(self.lib.sr_lpips_set_weights(self.h, arr("conv_w"), arr("conv_b"), arr("lin_w")))
+
+    def lpips(self, a, b, raw=False):
+        """LPIPS (AlexNet, version 0.1) of the pairs (a[i], b[i]) -> float32 [B] on the device.  a, b: device tensors [B,H,W,3] of one shape, both
+        uint8 BGR (the EDA's images) or both float32 RGB in [-1, 1]; 31 <= H, W.  raw=True -> (score, terms float32 [B,5], taps: five float32
+        tensors [2,B,h,w,C], the raw ReLU features of a then b).  RuntimeError while no weights are set (lpips_set_weights)."""
+        _check_tensor(self, a, "lpips a", (torch.uint8, torch.float32))
+        _check_tensor(self, b, "lpips b", (a.dtype,))
+        if a.shape != b.shape or a.dim() != 4 or a.shape[3] != 3 or a.shape[0] < 1:
+            raise ValueError(f"lpips: expected two batches [B,H,W,3] of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        B, H, W = (int(v) for v in a.shape[:3])
+        from .lpips import TAP_CHANNELS, tap_shapes
+        hw = tap_shapes(H, W)
+        score = self.empty((B,))
+        terms = self.empty((B, 5)) if raw else None
+        taps = [self.empty((2, B, h, w, c)) for (h, w), c in zip(hw, TAP_CHANNELS)] if raw else None
+        tp = (C.c_void_p * 5)(*[t.data_ptr() for t in taps]) if raw else None
+        self.check(self.lib.sr_lpips(self.h, a.data_ptr(), b.data_ptr(), _TORCH2DT[a.dtype], B, H, W, score.data_ptr(), terms.data_ptr() if raw else None, tp,
+                                     self.stream()))
+        return (score, terms, taps) if raw else score
+
     # ------------------------------------------------------------------ dataset synthesis: degrade_image's per-pixel stages (common_methods.py:52-107)
     @staticmethod
     def degrade_params(records):
