@@ -547,6 +547,46 @@ int  sr_lpips_set_weights(sr_ctx* ctx, const float* const conv_w[5], const float
 int  sr_lpips(sr_ctx* ctx, const void* a, const void* b, int dtype, int B, int H, int W, float* score_B, float* terms_Bx5, float* const taps[5],
               void* stream);
 
+/* ---- training batches cut from device-resident image stacks (reference SRModels/loading_methods.py:40-191, load_dataset_as_patches and its
+ * add_padding), csrc/patch_dataset.hip ----
+ * sr_gather_patch_pairs: ONE launch writes a batch of aligned LR / HR patches.  Each side (sr_patch_side) is a stack src DEVICE [N,H,W,3] of
+ *   `dtype` SR_DTYPE_U8 or SR_DTYPE_F32 (chosen per side) and a destination out DEVICE fp32: lr->out [B,patch_h,patch_w,3], hr->out
+ *   [B,patch_h*scale,patch_w*scale,3].  hr may be NULL (one-sided: the whole-image conversion below).  windows DEVICE int32 [n_windows,3]: image
+ *   index, y, x in LR-side pixels of the padded image; order DEVICE int32 [n_order]: rows of `windows`; batch element b is window
+ *   order[offset + b], 0 <= offset, offset + B <= n_order.  The HR window starts at (y*scale, x*scale).  Per element:
+ *     padding  add_padding's bottom / right reflect as np.pad(mode="reflect") indexes it: row i >= H of the padded image is row 2 (H - 1) - i.
+ *              pad_h / pad_w are the caller's, per side; a pad > H - 1 (W - 1) would reflect twice and is SR_ERR_INVALID, as is a patch
+ *              larger than the padded image.
+ *     order    swap_rb != 0 exchanges channels 0 and 2 (BGR stacks -> the loader's RGB).
+ *     uint8    float(u) / 255.0f, a correctly rounded fp32 division: np.float32(u) / 255.0 for all 256 codes (u * (1 / 255.0f) is not: it differs
+ *              in 126 of them).
+ *     scaling  then v * mul + add, product and sum rounded separately, skipped when mul == 1 and add == 0 (ESRGAN's x * 2 - 1).
+ *   One whole-image window per image (patch_h = H, patch_w = W, pads 0) converts a uint8 stack to fp32 [0,1].
+ *   Safety: the kernel clamps every order entry, image index and window origin into range, so no table reads outside the stacks, whatever it
+ *   holds (a clamped entry gives another valid window, not an error: the host validates tables before upload).  SR_ERR_INVALID, and no
+ *   launch, for a null pointer, a dtype other than the two, N, H, W, B, patch or scale < 1, offset < 0 or offset + B > n_order, n_windows < 1,
+ *   a pad outside 0 .. n - 1, a patch larger than a side's padded image, or a batch of 2^31 values or more.
+ * sr_clip_by_norm_bucket: tf.clip_by_norm per variable of a flat fp32 gradient bucket, in place (sr355/train.py Adam.apply): table DEVICE
+ *   int64 [n_vars,2] = (offset, length) per variable; nrm = sqrt(sum g^2) accumulated in fp64 from the fp32 values; where nrm > clipnorm,
+ *   g *= float(clipnorm / nrm) (fp64 division, rounded to fp32, one fp32 product per element); scales_out DEVICE fp32 [n_vars] receives the
+ *   factor, 1 where the variable was left alone.  One workgroup of 1024 threads per variable: thread t sums elements t, t + 1024, ... in
+ *   index order, the 1024 partial sums are added pairwise in a fixed tree (no atomics): the same bucket gives the same bits on every run.
+ *   A table entry is clamped into [0, bucket_len]; overlapping entries are the caller's error (the host builds the table from the bucket's
+ *   shapes).  SR_ERR_INVALID for a null pointer, n_vars outside 1 .. 65535, bucket_len < 1 or a clipnorm that is not finite and positive. */
+typedef struct {
+    const void* src;            /* DEVICE [N,H,W,3] */
+    float* out;                 /* DEVICE fp32 batch */
+    int32_t dtype;              /* SR_DTYPE_U8 or SR_DTYPE_F32 */
+    int32_t N, H, W;            /* the stack, unpadded */
+    int32_t pad_h, pad_w;       /* bottom / right reflect padding */
+    int32_t swap_rb;
+    float mul, add;
+} sr_patch_side;
+int  sr_gather_patch_pairs(sr_ctx* ctx, const sr_patch_side* lr, const sr_patch_side* hr, const int32_t* windows, int n_windows,
+                           const int32_t* order, int64_t n_order, int64_t offset, int B, int patch_h, int patch_w, int scale, void* stream);
+int  sr_clip_by_norm_bucket(sr_ctx* ctx, float* flat_g, int64_t bucket_len, const int64_t* table, int n_vars, double clipnorm, float* scales_out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

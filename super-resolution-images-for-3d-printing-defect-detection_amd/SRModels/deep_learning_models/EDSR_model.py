@@ -14,12 +14,20 @@ from sr355.wrappers import DeviceModelMixin, evaluate_sr, load_pretrained
 
 class EDSR(DeviceModelMixin):
     _init_scheme = "he_normal"   # kernel_initializer="he_normal" (EDSR_model.py:61)
+    clipnorm = 1.0               # Adam(clipnorm=1.0) (EDSR_model.py:130-136)
 
-    def __init__(self, compute_dtype="f32"):
+    def __init__(self, compute_dtype="f32", update="host"):
+        """update: where fit() applies Adam and its per-variable clip-by-norm -- "host" (NumPy on downloaded gradients, the default) or "device"
+        (one flat parameter bucket for the whole fit: sr_clip_by_norm_bucket, then sr_adam, in place).  The device clip factor can differ from
+        the host's by one fp32 ulp (its fp64 norm is summed in another order); where no factor differs the weights are the same bits."""
+        if update not in ("host", "device"):
+            raise ValueError("update must be 'host' or 'device'")
         self.model = None
         self.scale_factor = None
         self.trained = False
         self.compute_dtype = compute_dtype
+        self.update = update
+        self.clip_scales_log = None      # a list: fit() appends every step's clip factors (host: fp32 arrays; device: device tensors)
 
     def _mark_trained(self, v):
         self.trained = v
@@ -44,6 +52,8 @@ class EDSR(DeviceModelMixin):
     def fit(self, X_train, Y_train, X_val, Y_val, batch_size=16, epochs=300, shuffle=True, verbose=True):
         """Train the model (EDSR_model.py:127-176): Adam(lr, eps 1e-8, clipnorm 1.0), loss = mean_squared_error whatever `loss` said
         at setup (reference quirk, :137), EarlyStopping(patience 5, restore_best_weights), ReduceLROnPlateau(0.5, patience 3, 1e-7).
+        (X_train, Y_train) and (X_val, Y_val) are arrays or the .X / .Y views of a device-resident sr355.patches.PatchPairs
+        (load_dataset_as_patches(..., mode="scale", on_device=True)): the same batches, cut on the device.
         Returns (history, epoch-time record, epoch-memory record)."""
         if self.model is None:
             raise ValueError("Model is not built yet.")
@@ -52,9 +62,15 @@ class EDSR(DeviceModelMixin):
         from functools import partial
         from sr355 import train as T
         print("Training on GPU:", torch.cuda.get_device_name(self.ctx.torch_device))
-        opt = T.Adam(self.weights, learning_rate=self.learning_rate, epsilon=1e-8, clipnorm=1.0)
+        if self.update == "device":
+            start = T.ParamBucket(self.ctx, self.weights)
+            opt = T.DeviceAdam(self.ctx, start.flat, learning_rate=self.learning_rate, epsilon=1e-8, clipnorm=self.clipnorm, clip_table=self.ctx.clip_table(start))
+        else:
+            start, opt = self.weights, T.Adam(self.weights, learning_rate=self.learning_rate, epsilon=1e-8, clipnorm=self.clipnorm)
+        opt.scales_log = self.clip_scales_log
+        self._optimizer = opt
         lg = partial(T.edsr_loss_and_grads, scale=self.scale_factor, num_res_blocks=self.num_res_blocks, res_scaling=self.res_scaling)
-        weights, history, tcb, mcb = T.fit(self.ctx, self.weights, lg, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
+        weights, history, tcb, mcb = T.fit(self.ctx, start, lg, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
                                            batch_size=batch_size, epochs=epochs, es_patience=5, lr_patience=3, shuffle=shuffle, verbose=verbose)
         self.set_weights(weights)
         self.trained = True

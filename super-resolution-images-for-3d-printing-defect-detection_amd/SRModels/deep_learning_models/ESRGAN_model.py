@@ -19,6 +19,12 @@ from sr355 import pipeline as P
 from sr355.wrappers import DeviceModelMixin, load_pretrained
 
 
+class _Normalised:
+    """A batch fit() cut from a PatchPairs: a device tensor already in the generator's range (what `norm` returns for a host batch)."""
+    def __init__(self, t):
+        self.t = t
+
+
 class ESRGAN(DeviceModelMixin):
     def __init__(self, compute_dtype="f32", discriminator_update="host"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
@@ -161,10 +167,19 @@ class ESRGAN(DeviceModelMixin):
         partial -- or `train_dataset`, a re-iterable of (lr, hr) batches that is cycled (steps_per_epoch then mandatory).  Per step:
         _train_step, then PSNR / SSIM of generator(lr, training=False) against hr in [0,1], and the two decayed learning rates.
         Validation (arrays or an iterable of batches) reports the generator loss with the discriminator / VGG19 at inference.
+        (X_train, Y_train) and (X_val, Y_val) may also be the .X / .Y views of a device-resident sr355.patches.PatchPairs: the epoch's order (the
+        same generator calls, so the same batches) is uploaded once and each batch is cut on the device already normalised (the gather's
+        mul = 2, add = -1 in place of `norm`).  The [0,1] HR batch of the step's PSNR / SSIM is then to01 of that batch, 0.5 t + 0.5 on the
+        device: t / 2 is exact, so it rounds once, to the value the host path's (hr_b + 1) / 2 rounds to -- a second gather with mul = 1
+        would return v itself, which (2 v - 1 + 1) / 2 does not always give back.  A view mixed with an array raises ValueError.
         With save_dir a 5x5 grid of generator outputs is written per epoch.  Returns (epoch_losses of the LAST epoch -- per-step lists,
         val_* scalars -- as the reference does, EpochTimeTracker, EpochMemoryTracker)."""
         from sr355.gan_train import Tape, Var, generator_forward, staircase_lr
         from sr355.train import EpochMemoryTracker, EpochTimeTracker
+        from sr355.patches import views_dataset
+        ds_train = views_dataset(X_train, Y_train, "(X_train, Y_train)") if X_train is not None and Y_train is not None else None
+        ds_val = views_dataset(X_val, Y_val, "(X_val, Y_val)") if X_val is not None and Y_val is not None else None
+        mul_add = (2.0, -1.0) if normalize else (1.0, 0.0)
         if train_dataset is None and (X_train is None or Y_train is None):
             raise ValueError("Debe aportar (X_train,Y_train) o un train_dataset")
         if self.generator is None:
@@ -174,15 +189,23 @@ class ESRGAN(DeviceModelMixin):
         print("Training on GPU:", [f"MI355X:{self.ctx.device}"])
         tr = self._ensure_trainer()
         rng = np.random.default_rng(shuffle_seed)
-        norm = (lambda a: np.asarray(a, np.float32) * 2.0 - 1.0) if normalize else (lambda a: np.asarray(a, np.float32))
+        host_norm = (lambda a: np.asarray(a, np.float32) * 2.0 - 1.0) if normalize else (lambda a: np.asarray(a, np.float32))
+        norm = lambda a: a if isinstance(a, _Normalised) else host_norm(a)
         if train_dataset is None:
-            X_train, Y_train = np.asarray(X_train, np.float32), np.asarray(Y_train, np.float32)
+            if ds_train is None:
+                X_train, Y_train = np.asarray(X_train, np.float32), np.asarray(Y_train, np.float32)
             if steps_per_epoch is None:
                 steps_per_epoch = int(np.ceil(len(X_train) / batch_size))
 
             def batches():                                  # from_tensor_slices().shuffle(len).batch(bs).repeat()
                 while True:
                     order = rng.permutation(len(X_train))
+                    if ds_train is not None:
+                        order_dev = ds_train.set_order(order)
+                        for i in range(0, len(order), batch_size):
+                            x, y = ds_train.batch(order_dev, i, min(batch_size, len(order) - i), *mul_add)
+                            yield _Normalised(x), _Normalised(y)
+                        continue
                     for i in range(0, len(order), batch_size):
                         yield X_train[order[i:i + batch_size]], Y_train[order[i:i + batch_size]]
         else:
@@ -197,6 +220,12 @@ class ESRGAN(DeviceModelMixin):
         stream = batches()
         if val_dataset is not None:
             val_batches = lambda: iter(val_dataset)
+        elif ds_val is not None:
+            order_val = ds_val.set_order(np.arange(len(ds_val))) if len(ds_val) else None
+            val_batches = lambda: (tuple(_Normalised(t) for t in ds_val.batch(order_val, i, min(batch_size, len(ds_val) - i), *mul_add))
+                                   for i in range(0, len(ds_val), batch_size))
+            if val_steps is None:
+                val_steps = int(np.ceil(len(ds_val) / batch_size))
         elif X_val is not None and Y_val is not None:
             X_val, Y_val = np.asarray(X_val, np.float32), np.asarray(Y_val, np.float32)
             val_batches = lambda: ((X_val[i:i + batch_size], Y_val[i:i + batch_size]) for i in range(0, len(X_val), batch_size))
@@ -210,7 +239,8 @@ class ESRGAN(DeviceModelMixin):
 
         def generate_f32(lr_pm1):
             t = tr.generator_tape(wgrad=False)          # multiplies with the trainer's device-resident parameters
-            out = generator_forward(t, Var(self.ctx.to_device(np.asarray(lr_pm1, np.float32)), need=False), tr.scale, tr.nb, tr.att).v
+            lr_t = lr_pm1.t if isinstance(lr_pm1, _Normalised) else self.ctx.to_device(np.asarray(lr_pm1, np.float32))
+            out = generator_forward(t, Var(lr_t, need=False), tr.scale, tr.nb, tr.att).v
             t.ops = []
             return out
 
@@ -222,10 +252,11 @@ class ESRGAN(DeviceModelMixin):
             if save_dir is None:
                 return
             if preview is None:
+                first25 = lambda ds, X: ds.subset(np.arange(min(25, len(ds)))).X.numpy() if ds is not None else np.asarray(X[:25], np.float32)
                 if X_val is not None and len(X_val) > 0:
-                    preview = (np.asarray(X_val[:25], np.float32), False)
+                    preview = (first25(ds_val, X_val), False)
                 elif X_train is not None and len(X_train) > 0:
-                    preview = (np.asarray(X_train[:25], np.float32), False)
+                    preview = (first25(ds_train, X_train), False)
                 else:
                     src = val_batches() if val_batches is not None else iter(train_dataset)
                     first = next(src, None)
@@ -252,11 +283,14 @@ class ESRGAN(DeviceModelMixin):
             for step in range(steps_per_epoch):
                 lr_b, hr_b = next(stream)
                 lr_b, hr_b = norm(lr_b), norm(hr_b)
-                losses = tr.train_step(lr_b, hr_b)
+                if isinstance(lr_b, _Normalised):
+                    losses = tr.train_step(lr_b.t, hr_b.t)
+                else:
+                    losses = tr.train_step(lr_b, hr_b)
                 epoch_losses["g_loss"].append(float(losses["g_loss"]))
                 epoch_losses["d_loss"].append(float(losses["d_loss"]))
                 gen01 = to01(generate_f32(lr_b))
-                real01 = self.ctx.to_device((hr_b + 1.0) / 2.0)
+                real01 = to01(hr_b.t) if isinstance(hr_b, _Normalised) else self.ctx.to_device((hr_b + 1.0) / 2.0)
                 epoch_losses["psnr"].append(float(self.ctx.psnr(real01, gen01).mean().item()))
                 epoch_losses["ssim"].append(float(self.ctx.ssim(real01, gen01).mean().item()))
                 epoch_losses["g_lr"].append(float(np.float32(staircase_lr(tr.g_lr0, tr.step))))
@@ -273,7 +307,7 @@ class ESRGAN(DeviceModelMixin):
                     if val_steps is not None and i >= val_steps:
                         break
                     lr_v, hr_v = norm(lr_v), norm(hr_v)
-                    fake, real = generate_f32(lr_v), self.ctx.to_device(hr_v)
+                    fake, real = generate_f32(lr_v), hr_v.t if isinstance(hr_v, _Normalised) else self.ctx.to_device(hr_v)
                     vg.append(float(self.generator_loss(real, fake)[0]))
                     g01, r01 = to01(fake), to01(real)
                     vp.append(float(self.ctx.psnr(r01, g01).mean().item()))

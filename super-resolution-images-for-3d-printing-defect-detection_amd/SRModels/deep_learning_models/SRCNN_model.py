@@ -16,10 +16,15 @@ INTER_CUBIC = 2   # cv2.INTER_CUBIC
 
 
 class SRCNNModel(DeviceModelMixin):
-    def __init__(self, compute_dtype="f32"):
+    def __init__(self, compute_dtype="f32", update="host"):
+        """update: where fit() applies Adam -- "host" (NumPy on downloaded gradients, the default) or "device" (one flat parameter bucket updated
+        in place by sr_adam for the whole fit; the same weights and history bit for bit)."""
+        if update not in ("host", "device"):
+            raise ValueError("update must be 'host' or 'device'")
         self.model = None
         self._trained = False
         self.compute_dtype = compute_dtype
+        self.update = update
 
     def _mark_trained(self, v):
         self._trained = v
@@ -40,6 +45,8 @@ class SRCNNModel(DeviceModelMixin):
     def fit(self, X_train, Y_train, X_val, Y_val, batch_size=16, epochs=50, shuffle=True, verbose=True):
         """Trains the model (SRCNN_model.py:62-98): Adam(learning_rate), loss = mean_squared_error, metrics psnr / ssim,
         EarlyStopping(val_loss, patience 3, restore_best_weights), ReduceLROnPlateau(val_loss, factor 0.5, patience 2, min_lr 1e-7).
+        (X_train, Y_train) and (X_val, Y_val) are arrays or the .X / .Y views of a device-resident sr355.patches.PatchPairs
+        (load_dataset_as_patches(..., on_device=True)): the same batches, cut on the device.
         Returns (history, epoch-time record, epoch-memory record) like the reference's (history, callbacks[2], callbacks[3])."""
         if self.model is None:
             raise ValueError("Model has not been set up.")
@@ -47,8 +54,13 @@ class SRCNNModel(DeviceModelMixin):
             raise ValueError("training runs in fp32 (the reference's precision); build the model with compute_dtype='f32'")
         from sr355 import train as T
         print("Training on GPU:", torch.cuda.get_device_name(self.ctx.torch_device))
-        opt = T.Adam(self.weights, learning_rate=self.learning_rate, epsilon=1e-7)
-        weights, history, tcb, mcb = T.fit(self.ctx, self.weights, T.srcnn_loss_and_grads, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
+        if self.update == "device":
+            start = T.ParamBucket(self.ctx, self.weights)
+            opt = T.DeviceAdam(self.ctx, start.flat, learning_rate=self.learning_rate, epsilon=1e-7)
+        else:
+            start, opt = self.weights, T.Adam(self.weights, learning_rate=self.learning_rate, epsilon=1e-7)
+        self._optimizer = opt
+        weights, history, tcb, mcb = T.fit(self.ctx, start, T.srcnn_loss_and_grads, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
                                            batch_size=batch_size, epochs=epochs, es_patience=3, lr_patience=2, shuffle=shuffle, verbose=verbose)
         self.set_weights(weights)
         self._trained = True

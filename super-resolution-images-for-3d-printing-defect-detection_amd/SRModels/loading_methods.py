@@ -58,9 +58,15 @@ def _resize_up(lr_img, hr_h, hr_w, code=2):
     return ctx.resize(ctx.to_device(lr_img[None]), hr_h, hr_w, code)[0].cpu().numpy()
 
 
-def load_dataset_as_patches(hr_root, lr_root, mode="srcnn", patch_size=33, stride=14, scale_factor=2, interpolation_map_path=None):
+def load_dataset_as_patches(hr_root, lr_root, mode="srcnn", patch_size=33, stride=14, scale_factor=2, interpolation_map_path=None, on_device=False):
     """Aligned LR/HR patch pairs.  'srcnn': LR bicubic-upscaled to HR size, equal-size patches, returns
-    (X, Y, hr_h, hr_w); 'scale': LR patches of patch_size, HR patches of patch_size*scale, returns (X, Y)."""
+    (X, Y, hr_h, hr_w); 'scale': LR patches of patch_size, HR patches of patch_size*scale, returns (X, Y).
+    on_device=True: X and Y are the views ds.X / ds.Y of one sr355.patches.PatchPairs -- the same patches in the same order, cut on the
+    device from resident image stacks when a fit asks for a batch (X.ds is the dataset: subset(), batch(), .numpy())."""
+    if on_device:
+        from sr355.patches import PatchPairs
+        ds = PatchPairs.from_dirs(hr_root, lr_root, mode, patch_size, stride, scale_factor, interpolation_map_path)
+        return (ds.X, ds.Y) + (ds.hr_size if mode == "srcnn" else ())
     if mode not in ("srcnn", "scale"):
         raise ValueError("mode must be 'srcnn' or 'scale'")
     _check_dirs(hr_root, lr_root)

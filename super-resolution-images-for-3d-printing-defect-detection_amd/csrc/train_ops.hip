@@ -10,6 +10,8 @@
 //   * element-wise backward ops and the space_to_depth that undoes depth_to_space (TF "DCR" order).
 #include "common.h"
 
+#include <cmath>
+
 namespace {
 
 constexpr int WG_SPLIT_PIX = 2048;        // pixels per workgroup slice of the reduction axis
@@ -531,7 +533,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ w, const 
         const float vi = __fadd_rn(__fmul_rn(b2, v[i]), __fmul_rn(__fmul_rn(omb2, gi), gi));
         m[i] = mi;
         v[i] = vi;
-        w[i] = __fsub_rn(w[i], __fdiv_rn(__fmul_rn(lr_t, mi), __fadd_rn(__fsqrt_rn(vi), eps)));
+        w[i] = __fsub_rn(w[i], __fdiv_rn(__fmul_rn(lr_t, mi), __fadd_rn(sqrtf(vi), eps)));      // sqrtf: correctly rounded, as np.sqrt is (__fsqrt_rn is the 1-ulp v_sqrt_f32)
     }
 }
 
@@ -539,6 +541,47 @@ int adam_launch(sr_ctx* ctx, float* w, const float* g, float* m, float* v, int64
                 float gscale, hipStream_t st) {
     if (n <= 0) return ctx->fail(SR_ERR_INVALID, "adam: empty bucket");
     hipLaunchKernelGGL(adam_kernel, dim3(grid_n(n)), dim3(256), 0, st, w, g, m, v, n, lr_t, b1, omb1, b2, omb2, eps, gscale);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+// tf.clip_by_norm per variable of a flat gradient bucket, in place, as sr355.train.Adam.apply computes it on the host: nrm = sqrt(sum g^2) in fp64 on
+// the widened fp32 values, and where nrm > clipnorm every element is multiplied by float(clipnorm / nrm).  One workgroup of CLIP_THREADS per variable
+// (EDSR: 74 variables of 3 .. 147 456 elements, 5.5 MB in all -- the launch is over in microseconds and the second pass finds the variable in L2).  The
+// reduction has a fixed shape: thread t adds elements t, t + CLIP_THREADS, ... in index order, the partial sums are added pairwise through LDS in a
+// fixed tree; no atomics, so the norm -- and with it every scaled element -- is the same bits on every run.  NumPy's pairwise sum adds in another
+// order: the two fp64 norms differ by rounding far below fp32's half-ulp, so the fp32 factor differs from the host's by at most one ulp.
+constexpr int CLIP_THREADS = 1024;
+
+__global__ void __launch_bounds__(CLIP_THREADS) clip_by_norm_kernel(float* __restrict__ g, int64_t bucket_len, const int64_t* __restrict__ table, double clipnorm,
+                                                                    float* __restrict__ scales) {
+    __shared__ double red[CLIP_THREADS];
+    const int v = blockIdx.x, tid = threadIdx.x;
+    int64_t off = table[2 * (int64_t)v], len = table[2 * (int64_t)v + 1];
+    off = off < 0 ? 0 : (off > bucket_len ? bucket_len : off);            // a table entry never reaches outside the bucket
+    len = len < 0 ? 0 : (len > bucket_len - off ? bucket_len - off : len);
+    float* p = g + off;
+    double s = 0.0;
+    for (int64_t i = tid; i < len; i += CLIP_THREADS) { const double x = (double)p[i]; s = __dadd_rn(s, __dmul_rn(x, x)); }
+    red[tid] = s;
+    __syncthreads();
+    for (int o = CLIP_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = __dadd_rn(red[tid], red[tid + o]);
+        __syncthreads();
+    }
+    const double nrm = __dsqrt_rn(red[0]);
+    const bool clip = nrm > clipnorm;
+    const float f = clip ? (float)__ddiv_rn(clipnorm, nrm) : 1.f;
+    if (tid == 0) scales[v] = f;
+    if (!clip) return;                                                    // uniform per workgroup
+    for (int64_t i = tid; i < len; i += CLIP_THREADS) p[i] = __fmul_rn(p[i], f);
+}
+
+int clip_by_norm_launch(sr_ctx* ctx, float* g, int64_t bucket_len, const int64_t* table, int n_vars, double clipnorm, float* scales, hipStream_t st) {
+    if (n_vars < 1 || n_vars > 65535) return ctx->fail(SR_ERR_INVALID, "clip_by_norm_bucket: need 1 <= n_vars <= 65535");
+    if (bucket_len < 1) return ctx->fail(SR_ERR_INVALID, "clip_by_norm_bucket: empty bucket");
+    if (!(clipnorm > 0.0) || !std::isfinite(clipnorm)) return ctx->fail(SR_ERR_INVALID, "clip_by_norm_bucket: clipnorm must be finite and positive");
+    hipLaunchKernelGGL(clip_by_norm_kernel, dim3((unsigned)n_vars), dim3(CLIP_THREADS), 0, st, g, bucket_len, table, clipnorm, scales);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
 }
@@ -611,4 +654,12 @@ int spectral_l1_bwd_launch(sr_ctx* ctx, const float* a, const float* b, int B, i
     hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(256), lds, st, a, b, W, scale / (float)((double)rows * W * 3), da);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
+}
+
+extern "C" int sr_clip_by_norm_bucket(sr_ctx* ctx, float* flat_g, int64_t bucket_len, const int64_t* table, int n_vars, double clipnorm, float* scales_out,
+                                      void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!flat_g || !table || !scales_out) return ctx->fail(SR_ERR_INVALID, "clip_by_norm_bucket: null pointer");
+    return clip_by_norm_launch(ctx, flat_g, bucket_len, table, n_vars, clipnorm, scales_out, static_cast<hipStream_t>(stream));
 }

@@ -44,6 +44,12 @@ class SnDesc(C.Structure):
     _fields_ = [("koff", C.c_int64), ("K", C.c_int32), ("Cout", C.c_int32), ("uoff", C.c_int64)]
 
 
+class PatchSide(C.Structure):
+    """sr_patch_side: one side (LR or HR) of sr_gather_patch_pairs (include/sr355.h)."""
+    _fields_ = [("src", C.c_void_p), ("out", C.c_void_p), ("dtype", C.c_int32), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("pad_h", C.c_int32), ("pad_w", C.c_int32), ("swap_rb", C.c_int32), ("mul", C.c_float), ("add", C.c_float)]
+
+
 _vp, _i, _f, _i64 = C.c_void_p, C.c_int, C.c_float, C.c_int64
 _vw = C.POINTER(View)
 _fp = C.POINTER(C.c_float)
@@ -128,6 +134,8 @@ SIGNATURES = {
     "sr_lpips_input_table": (_i, [_fp]),
     "sr_lpips_set_weights": (_i, [_vp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]),
     "sr_lpips": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), _vp]),
+    "sr_gather_patch_pairs": (_i, [_vp, C.POINTER(PatchSide), C.POINTER(PatchSide), _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
+    "sr_clip_by_norm_bucket": (_i, [_vp, _vp, _i64, _vp, _i, C.c_double, _vp, _vp]),
 }
 
 # the columns of sr_classic_scores (SR_SCORE_* in include/sr355.h)

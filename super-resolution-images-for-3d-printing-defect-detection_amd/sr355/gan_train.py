@@ -475,6 +475,14 @@ class DeviceDiscriminator:
 
 
 # ----------------------------------------------------------------------------------------------------------------- the step
+def _device_batch(ctx, images):
+    """A step's image batch -> fp32 device tensor: a host array is uploaded, a tensor already on the device (a batch cut from
+    sr355.patches.PatchPairs) is taken as it is."""
+    if isinstance(images, torch.Tensor):
+        return ctx.to_device(images, torch.float32)
+    return ctx.to_device(np.asarray(images, np.float32))
+
+
 def _floats(values):
     """Python floats and one-element device tensors -> Python floats; the tensors come over in ONE read."""
     dev = [v for v in values if isinstance(v, torch.Tensor)]
@@ -595,7 +603,7 @@ class ESRGANTrainer:
         """One generator update on the pixel loss alone (mean |hr - G(lr)|, ESRGAN_model.py:433-445; the generator half of _train_step,
         :506-531, without the adversarial / perceptual / spectral terms): sr355.recipes' fit.  -> the L1 value before the update."""
         ctx = self.ctx
-        lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
+        lr_t, hr_t = _device_batch(ctx, lr_images), _device_batch(ctx, hr_images)
         tg = self.generator_tape()
         with self._prepacked(False):
             y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
@@ -615,7 +623,7 @@ class ESRGANTrainer:
             self._packs.pop(True, None)
         ctx, disc = self.ctx, self.disc
         with self._prepacked(True):                        # the generator's weights change only in the step's last lines, VGG19's never
-            lr_t, hr_t = ctx.to_device(np.asarray(lr_images, np.float32)), ctx.to_device(np.asarray(hr_images, np.float32))
+            lr_t, hr_t = _device_batch(ctx, lr_images), _device_batch(ctx, hr_images)
             # The reference runs the generator twice per step, once under each tape (ESRGAN_model.py:490, :508); its weights do not change
             # in between (the discriminator is updated first), so both runs are the same tensor: one taped forward serves both.
             tg = self.generator_tape()

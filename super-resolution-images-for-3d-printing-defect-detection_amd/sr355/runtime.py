@@ -844,6 +844,84 @@ class Context:
             raise ValueError("spectral_norm_bucket: table must be a non-empty array of sr_sn_desc (spectral_norm_table)")
         self.check(self.lib.sr_spectral_norm_bucket(self.h, flat.data_ptr(), flat.numel(), u.data_ptr(), u.numel(), table, len(table), self.stream()))
 
+    # ------------------------------------------------------------------ training batches from resident stacks (loading_methods.py:40-191)
+    def _patch_side(self, side, ph, pw, B, who):
+        """side: dict(stack, pad=(pad_h, pad_w), swap, mul, add) -> (sr_patch_side, the fp32 batch tensor [B,ph,pw,3])."""
+        stack = side["stack"]
+        _check_tensor(self, stack, f"gather_patch_pairs {who} stack", (torch.float32, torch.uint8))
+        if stack.dim() != 4 or stack.shape[3] != 3:
+            raise ValueError(f"gather_patch_pairs: the {who} stack must be [N,H,W,3]")
+        N, H, W, _ = (int(v) for v in stack.shape)
+        pad_h, pad_w = (int(v) for v in side.get("pad", (0, 0)))
+        if not (0 <= pad_h <= H - 1 and 0 <= pad_w <= W - 1):
+            raise ValueError(f"gather_patch_pairs: {who} reflect padding ({pad_h}, {pad_w}) must lie in 0 .. size - 1 of a {H} x {W} image")
+        if ph > H + pad_h or pw > W + pad_w:
+            raise ValueError(f"gather_patch_pairs: a {ph} x {pw} patch does not fit the padded {who} image")
+        out = self.empty((B, ph, pw, 3), torch.float32)
+        s = L.PatchSide(stack.data_ptr(), out.data_ptr(), dtype_code(stack.dtype), N, H, W, pad_h, pad_w, int(bool(side.get("swap", False))),
+                        float(side.get("mul", 1.0)), float(side.get("add", 0.0)))
+        return s, out
+
+    def gather_patch_pairs(self, lr, hr, windows, order, offset, B, patch, scale=1):
+        """One batch of aligned patches cut from device-resident stacks by one launch (sr_gather_patch_pairs).  lr / hr: dict(stack=[N,H,W,3]
+        uint8 or fp32 device tensor, pad=(pad_h, pad_w) bottom / right reflect padding, swap=BGR->RGB, mul=1, add=0); hr may be None.
+        windows int32 device [n,3] (image, y, x in LR-side pixels), order int32 device [m] rows of windows; the batch is windows
+        order[offset : offset + B].  patch: int or (h, w) on the LR side.  -> (X fp32 [B,h,w,3], Y fp32 [B,h*scale,w*scale,3] or None).
+        The tables' CONTENTS are the caller's to validate before upload (sr355.patches does); the kernel clamps what it reads."""
+        ph, pw = (int(patch), int(patch)) if isinstance(patch, (int, np.integer)) else (int(patch[0]), int(patch[1]))
+        offset, B, scale = int(offset), int(B), int(scale)
+        _check_tensor(self, windows, "gather_patch_pairs windows", (torch.int32,))
+        _check_tensor(self, order, "gather_patch_pairs order", (torch.int32,))
+        if windows.dim() != 2 or windows.shape[1] != 3 or windows.shape[0] < 1 or order.dim() != 1:
+            raise ValueError("gather_patch_pairs: windows must be int32 [n,3] and order int32 [m]")
+        if B < 1 or offset < 0 or offset + B > order.numel():
+            raise ValueError(f"gather_patch_pairs: batch [{offset}, {offset + B}) reaches outside an order of {order.numel()} entries")
+        if ph < 1 or pw < 1 or scale < 1:
+            raise ValueError("gather_patch_pairs: patch and scale must be >= 1")
+        a, X = self._patch_side(lr, ph, pw, B, "LR")
+        b, Y = self._patch_side(hr, ph * scale, pw * scale, B, "HR") if hr is not None else (None, None)
+        if hr is not None and hr["stack"].shape[0] != lr["stack"].shape[0]:
+            raise ValueError("gather_patch_pairs: the two stacks hold different numbers of images")
+        self.check(self.lib.sr_gather_patch_pairs(self.h, C.byref(a), C.byref(b) if b is not None else None, windows.data_ptr(), int(windows.shape[0]),
+                                                  order.data_ptr(), order.numel(), offset, B, ph, pw, scale, self.stream()))
+        return X, Y
+
+    def u8_to_unit(self, stack, swap=False):
+        """uint8 [N,H,W,3] device stack -> fp32 [N,H,W,3] in [0,1], float(u) / 255.0f per element: sr_gather_patch_pairs with one whole-image
+        window per image."""
+        _check_tensor(self, stack, "u8_to_unit input", (torch.uint8,))
+        N, H, W, _ = stack.shape
+        win = np.zeros((N, 3), np.int32)
+        win[:, 0] = np.arange(N)
+        return self.gather_patch_pairs(dict(stack=stack, swap=swap), None, self.to_device(win), self.to_device(np.arange(N, dtype=np.int32)), 0, N, (H, W))[0]
+
+    def clip_table(self, bucket):
+        """The (offset, length) table of clip_by_norm_bucket for every array of a train.ParamBucket, in parameter order -> int64 device [n_vars,2]."""
+        rows, o = [], 0
+        for shapes in bucket.shapes.values():
+            for shape in shapes:
+                size = int(np.prod(shape))
+                rows.append((o, size))
+                o += size
+        return self.to_device(np.asarray(rows, np.int64))
+
+    def clip_by_norm_bucket(self, flat_g, table, clipnorm, scales_out=None):
+        """tf.clip_by_norm per variable of the flat fp32 gradient bucket, in place (sr_clip_by_norm_bucket) -> the factors, fp32 device [n_vars]
+        (1 where a variable's norm was within clipnorm)."""
+        _check_tensor(self, flat_g, "clip_by_norm bucket")
+        _check_tensor(self, table, "clip_by_norm table", (torch.int64,))
+        if flat_g.dim() != 1 or table.dim() != 2 or table.shape[1] != 2 or table.shape[0] < 1:
+            raise ValueError("clip_by_norm_bucket: a flat bucket and an int64 [n_vars,2] table (clip_table)")
+        n_vars = int(table.shape[0])
+        if scales_out is None:
+            scales_out = self.empty((n_vars,), torch.float32)
+        _check_tensor(self, scales_out, "clip_by_norm scales")
+        if scales_out.numel() != n_vars:
+            raise ValueError("clip_by_norm_bucket: scales_out holds one fp32 per variable")
+        self.check(self.lib.sr_clip_by_norm_bucket(self.h, flat_g.data_ptr(), flat_g.numel(), table.data_ptr(), n_vars, float(clipnorm), scales_out.data_ptr(),
+                                                   self.stream()))
+        return scales_out
+
     DISC_HEAD_PARAMS = 256 * 256 + 256 + 256 + 1
 
     def disc_head_step(self, h, params, target, loss, grads=None, accumulate=False):

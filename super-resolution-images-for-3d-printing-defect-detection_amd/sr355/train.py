@@ -6,8 +6,13 @@ the reference trains), loss = mean_squared_error, the backward pass layer by lay
 their element-wise or permutation inverses (csrc/train_ops.hip) -- and Adam exactly as Keras applies it (optimizer_v2 dense update:
 lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); var -= lr_t m / (sqrt(v) + eps); EDSR: per-variable clip-by-norm 1.0, eps 1e-8), plus the two
 callbacks that change the result (EarlyStopping with restore_best_weights, ReduceLROnPlateau) and the two that only record
-(epoch time, device memory).  Optimiser state and master weights live on the host (28 931 / 1.37 M parameters); every step re-packs the
-updated kernels for the device through the single-op entry points.
+(epoch time, device memory).  Two places for the update, chosen by the model's `update` keyword: "host" (the default) keeps optimiser state and
+master weights on the host (28 931 / 1.37 M parameters) -- every step uploads the weights into a fresh ParamBucket, downloads every gradient and
+runs `Adam.apply` in NumPy; "device" keeps ONE ParamBucket and a DeviceAdam for the whole fit -- gradients are gathered into a flat bucket,
+clipped per variable (EDSR, sr_clip_by_norm_bucket) and applied by sr_adam, and the host reads one block of per-step statistics per epoch plus
+the weights for validation and the callbacks.  The training data is either the loader's host arrays, indexed and uploaded per step, or the
+`.X` / `.Y` views of a device-resident sr355.patches.PatchPairs, from which each step's batch is cut by one launch; the batches are the same
+bits either way.
 """
 import time
 
@@ -95,6 +100,12 @@ class ParamBucket:
         return self.ctx.conv2d_dev(dy, k, None, k.shape[2], rot=True)
 
 
+def as_bucket(ctx, w):
+    """A *_loss_and_grads weight argument -> ParamBucket: the caller's own (device update: one bucket for the whole fit) or a fresh upload of a
+    host weight dict."""
+    return w if isinstance(w, ParamBucket) else ParamBucket(ctx, w)
+
+
 def _next_lr_t(opt):
     """Advance an Adam's step count -> that step's bias-corrected rate lr sqrt(1 - b2^t) / (1 - b1^t) in fp32 (both Adams below)."""
     opt.t += 1
@@ -107,48 +118,65 @@ class Adam:
     def __init__(self, weights, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
         self.lr, self.b1, self.b2, self.eps, self.clipnorm = float(learning_rate), beta_1, beta_2, epsilon, clipnorm
         self.t = 0
+        self.scales_log = None          # a list: every apply() appends its clip factors, fp32 [variables] in parameter order (1 = not clipped)
         self.m = {n: [np.zeros_like(k), np.zeros_like(b)] for n, (k, b) in weights.items()}
         self.v = {n: [np.zeros_like(k), np.zeros_like(b)] for n, (k, b) in weights.items()}
 
     def apply(self, weights, grads):
         lr_t = _next_lr_t(self)
-        out = {}
+        out, scales = {}, []
         for n, (k, b) in weights.items():
             if n not in grads:                                     # a variable the loss does not reach: Keras skips None gradients
                 out[n] = (k, b)
+                scales += [np.float32(1.0)] * 2
                 continue
             new = []
             for slot, (var, g) in enumerate(((k, grads[n][0]), (b, grads[n][1]))):
                 g = np.asarray(g, np.float32)
+                scales.append(np.float32(1.0))
                 if self.clipnorm is not None:                      # tf.clip_by_norm per variable
                     nrm = float(np.sqrt(np.sum(g.astype(np.float64) ** 2)))
                     if nrm > self.clipnorm:
+                        scales[-1] = np.float32(self.clipnorm / nrm)
                         g = g * np.float32(self.clipnorm / nrm)
                 m = self.m[n][slot] = np.float32(self.b1) * self.m[n][slot] + np.float32(1.0 - self.b1) * g
                 v = self.v[n][slot] = np.float32(self.b2) * self.v[n][slot] + np.float32(1.0 - self.b2) * g * g
                 new.append((var - lr_t * m / (np.sqrt(v) + np.float32(self.eps))).astype(np.float32))
             out[n] = (new[0], new[1])
+        if self.scales_log is not None:
+            self.scales_log.append(np.array(scales, np.float32))
         return out
 
 
 class DeviceAdam:
     """The same optimiser with its state on the device: parameters, both moments and the gradient are flat fp32 buckets and one fused kernel
     (sr_adam) updates them in place -- no parameter leaves the GPU between steps.  Bit for bit the update of `Adam.apply` on the same numbers
-    (the kernel rounds every operation separately, in NumPy's order)."""
+    (the kernel rounds every operation separately, in NumPy's order).  clipnorm with clip_table (Context.clip_table of the parameters' bucket):
+    tf.clip_by_norm per variable first, in place in flat_grads (sr_clip_by_norm_bucket; its fp64 norm is summed in another order than NumPy's, so a
+    clip factor may differ from the host's by one fp32 ulp)."""
 
-    def __init__(self, ctx, flat_weights, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+    def __init__(self, ctx, flat_weights, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None, clip_table=None):
         self.ctx, self.lr, self.b1, self.b2, self.eps = ctx, float(learning_rate), beta_1, beta_2, epsilon
         self.t = 0
         self.m, self.v = torch.zeros_like(flat_weights), torch.zeros_like(flat_weights)
+        if (clipnorm is None) != (clip_table is None):
+            raise ValueError("DeviceAdam: clipnorm and clip_table go together")
+        self.clipnorm, self.clip_table = clipnorm, clip_table
+        self.scales_log = None          # a list: every apply() appends its clip factors, fp32 device [variables] (no host read)
 
     def apply(self, flat_weights, flat_grads, grad_scale=1.0):
+        if self.clipnorm is not None:
+            scales = self.ctx.clip_by_norm_bucket(flat_grads, self.clip_table, self.clipnorm)
+            if self.scales_log is not None:
+                self.scales_log.append(scales)
         self.ctx.adam_step(flat_weights, flat_grads, self.m, self.v, _next_lr_t(self), self.b1, self.b2, self.eps, grad_scale)
 
 
 # ---------------------------------------------------------------------------------------------------------------- graphs
 def srcnn_loss_and_grads(ctx, w, x, t):
-    """SRCNN_model.py:48-53 + mean_squared_error.  x, t device fp32 [B,H,W,3].  -> (prediction, loss tensor [1], {layer: (dw, db)})."""
-    dw = ParamBucket(ctx, w)
+    """SRCNN_model.py:48-53 + mean_squared_error.  w: host weight dict, or the fit's ParamBucket.  x, t device fp32 [B,H,W,3].
+    -> (prediction, loss tensor [1], {layer: (dw, db)})."""
+    dw = as_bucket(ctx, w)
     a1 = dw.conv(x, "conv2d", act="relu")
     a2 = dw.conv(a1, "conv2d_1", act="relu")
     y = dw.conv(a2, "conv2d_2")
@@ -168,7 +196,7 @@ def edsr_loss_and_grads(ctx, w, x, t, scale=2, num_res_blocks=16, res_scaling=0.
     names = ["conv2d"] + [f"conv2d_{i}" for i in range(1, 2 * num_res_blocks + 5)]
     it = iter(names)
     n_head = next(it)
-    dw = ParamBucket(ctx, w)
+    dw = as_bucket(ctx, w)
     h0 = dw.conv(x, n_head)
     cur, blocks = h0, []
     for _ in range(num_res_blocks):
@@ -296,33 +324,65 @@ def fit(ctx, weights, loss_and_grads, predict, optimizer, X_train, Y_train, X_va
         lr_patience=2, lr_factor=0.5, min_lr=1e-7, shuffle=True, seed=42, verbose=True):
     """model.fit(X, Y, batch_size, epochs, validation_data, callbacks=[EarlyStopping(val_loss, patience, restore_best_weights=True),
     ReduceLROnPlateau(val_loss, factor, patience, min_lr), EpochTimeCallback, EpochMemoryCallback]).
-    weights: {layer: (kernel, bias)} host fp32 (updated copy returned).  -> (weights, History, EpochTimeTracker, EpochMemoryTracker)."""
-    X_train, Y_train = np.asarray(X_train, np.float32), np.asarray(Y_train, np.float32)
-    X_val, Y_val = np.asarray(X_val, np.float32), np.asarray(Y_val, np.float32)
+    weights: {layer: (kernel, bias)} host fp32 with an `Adam` (host update), or a ParamBucket with a `DeviceAdam` over its flat tensor (device
+    update: the bucket is trained in place; per epoch the host reads the steps' loss / sum psnr / sum ssim in one copy and the weights for
+    validation and the callbacks).  (X_train, Y_train) and (X_val, Y_val): arrays, or the .X / .Y views of one sr355.patches.PatchPairs each --
+    the epoch's order then goes up once and every batch is one gather launch; the order comes from the same generator calls, so the batches
+    are the array path's.  -> (updated copy of the weights as a host dict, History, EpochTimeTracker, EpochMemoryTracker)."""
+    from .patches import views_dataset
+    ds_train, ds_val = views_dataset(X_train, Y_train, "(X_train, Y_train)"), views_dataset(X_val, Y_val, "(X_val, Y_val)")
+    if ds_train is None:
+        X_train, Y_train = np.asarray(X_train, np.float32), np.asarray(Y_train, np.float32)
+    if ds_val is None:
+        X_val, Y_val = np.asarray(X_val, np.float32), np.asarray(Y_val, np.float32)
+    bucket = weights if isinstance(weights, ParamBucket) else None
+    if (bucket is not None) != isinstance(optimizer, DeviceAdam):
+        raise ValueError("fit: a ParamBucket trains with a DeviceAdam, a host weight dict with an Adam")
     hist, tcb, mcb = History(("loss", "psnr", "ssim", "val_loss", "val_psnr", "val_ssim", "lr")), EpochTimeTracker(), EpochMemoryTracker(ctx)
     callbacks = PlateauCallbacks(optimizer, es_patience, lr_patience, lr_factor, min_lr, verbose)
     rng = np.random.default_rng(seed)
-    n = len(X_train)
+    n, n_val = len(X_train), len(X_val)
+    spans = [(i, min(i + batch_size, n)) for i in range(0, n, batch_size)]
+    order_val = ds_val.set_order(np.arange(n_val)) if ds_val is not None and n_val else None
+    stats = ctx.empty((max(len(spans), 1), 3), torch.float32) if bucket is not None else None
     for ep in range(epochs):
         mcb.begin_epoch()
         tcb.begin_epoch()
         order = rng.permutation(n) if shuffle else np.arange(n)
+        order_dev = ds_train.set_order(order) if ds_train is not None and n else None
         tot = np.zeros(3, np.float64)
-        for i in range(0, n, batch_size):
-            idx = order[i:i + batch_size]
-            x, t = ctx.to_device(X_train[idx]), ctx.to_device(Y_train[idx])
+        for s, (i, j) in enumerate(spans):
+            if ds_train is not None:
+                x, t = ds_train.batch(order_dev, i, j - i)
+            else:
+                idx = order[i:j]
+                x, t = ctx.to_device(X_train[idx]), ctx.to_device(Y_train[idx])
             y, loss, grads = loss_and_grads(ctx, weights, x, t)
-            k = len(idx)
-            tot += [float(loss.item()) * k, float(ctx.psnr(t, y).sum().item()), float(ctx.ssim(t, y).sum().item())]
-            host_g = {name: (dw.cpu().numpy(), db.cpu().numpy()) for name, (dw, db) in grads.items()}
-            weights = optimizer.apply(weights, host_g)
+            if bucket is None:
+                tot += [float(loss.item()) * (j - i), float(ctx.psnr(t, y).sum().item()), float(ctx.ssim(t, y).sum().item())]
+                host_g = {name: (dw.cpu().numpy(), db.cpu().numpy()) for name, (dw, db) in grads.items()}
+                weights = optimizer.apply(weights, host_g)
+            else:
+                stats[s, 0:1].copy_(loss)
+                stats[s, 1].copy_(ctx.psnr(t, y).sum())
+                stats[s, 2].copy_(ctx.ssim(t, y).sum())
+                optimizer.apply(bucket.flat, bucket.gather(grads))
+                bucket.stale = True
+        if bucket is not None:
+            st = stats.cpu().numpy()                                     # the epoch's statistics, one copy; then the host path's fp64 sums
+            for s, (i, j) in enumerate(spans):
+                tot += [float(st[s, 0]) * (j - i), float(st[s, 1]), float(st[s, 2])]
+        host_w = dict(bucket.host()) if bucket is not None else weights   # (a new dict per epoch: predict() reloads the model when it sees one)
         vt = np.zeros(3, np.float64)
-        for i in range(0, len(X_val), batch_size):
-            x, t = ctx.to_device(X_val[i:i + batch_size]), ctx.to_device(Y_val[i:i + batch_size])
-            y = predict(ctx, weights, x)
+        for i in range(0, n_val, batch_size):
+            if ds_val is not None:
+                x, t = ds_val.batch(order_val, i, min(batch_size, n_val - i))
+            else:
+                x, t = ctx.to_device(X_val[i:i + batch_size]), ctx.to_device(Y_val[i:i + batch_size])
+            y = predict(ctx, host_w, x)
             vt += [float(ctx.mse(t, y).item()) * len(x), float(ctx.psnr(t, y).sum().item()), float(ctx.ssim(t, y).sum().item())]
         torch.cuda.synchronize(ctx.torch_device)
-        tr, va = tot / max(n, 1), vt / max(len(X_val), 1)
+        tr, va = tot / max(n, 1), vt / max(n_val, 1)
         for key, val in zip(("loss", "psnr", "ssim", "val_loss", "val_psnr", "val_ssim"), list(tr) + list(va)):
             hist.history[key].append(float(val))
         hist.history["lr"].append(optimizer.lr)
@@ -332,10 +392,14 @@ def fit(ctx, weights, loss_and_grads, predict, optimizer, X_train, Y_train, X_va
         if verbose:
             print(f"Epoch {ep + 1}/{epochs} - loss: {tr[0]:.4f} - psnr: {tr[1]:.4f} - ssim: {tr[2]:.4f} - val_loss: {va[0]:.4f} - "
                   f"val_psnr: {va[1]:.4f} - val_ssim: {va[2]:.4f} - lr: {optimizer.lr:.2e}")
-        best_w = callbacks.end_epoch(ep, va[0], weights)
+        best_w = callbacks.end_epoch(ep, va[0], host_w)
         if best_w is not None:
+            if bucket is not None:
+                bucket.load(best_w)
             weights = best_w
             break
+    if bucket is not None:
+        weights = {name: (k.copy(), b.copy()) for name, (k, b) in bucket.host().items()}
     return weights, hist, tcb, mcb
 
 
