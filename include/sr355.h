@@ -271,6 +271,28 @@ int  sr_extract_patches(sr_ctx* ctx, const float* img, int H, int W, int C, int 
 int  sr_overlap_add(sr_ctx* ctx, const void* patches, int in_dtype, int H, int W, int C, int patch,
                     int stride, int scale, float mul, float add, float* out, void* stream);
 
+/* ---- classifying a stack of frames and scoring a comparison of SR methods (VGG16_model.py:168-270 for F frames at once;
+ *      deep_lerning_visualizations.py:230-314, 454-495) ----
+ * sr_extract_patches_batch: sr_extract_patches for F frames of one size in one launch.  imgs [F,H,W,C] of in_dtype (SR_DTYPE_F32 or
+ *   SR_DTYPE_U8, the value float(u8)); out [F*P,patch,patch,C] of out_dtype (f32 or bf16), frame-major, a frame's P patches in
+ *   sr_extract_patches' order with its reflect padding (bottom/right, from (patch,stride)) and its v*mul+add.  Frame f's slice is bit for bit
+ *   what sr_extract_patches writes for frame f alone (for u8 input: for float(u8)).  *patches_per_image receives P; out may be NULL to query P
+ *   only.  out_capacity counts elements; too small -> SR_ERR_CAPACITY and nothing is written.  Element indices are 64-bit.
+ * sr_patch_vote: the majority vote of VGG16_model.py:252-268 for F frames.  probs f32 [F*P,K], 1 <= K <= 64 (else SR_ERR_INVALID).  Per frame:
+ *   each patch votes for its argmax (first maximum); the class with the most votes wins; on a tie of votes, the tied class with the highest
+ *   mean probability over the frame's P patches, the lowest index on equal means.  cls_F int32 [F]; conf_F f32 [F] = the winner's mean
+ *   probability, accumulated in fp64 in a fixed order (one workgroup per frame, a tree, no float atomics: the same bits on every run) and
+ *   rounded once to fp32; votes_FxK int32 [F,K] (may be NULL) the vote counts.
+ * sr_classification_counts: for each of A methods the K x K confusion matrix (rows = true class, columns = predicted class; int64
+ *   [A,K,K], zeroed by the call) of preds_AxN int32 [A,N] against y_true_N int32 [N], and conf_sums_Ax2 f64 [A,2] = (sum of conf, sum of conf
+ *   over the correct predictions) of conf_AxN f32 [A,N] (may be NULL: the sums are 0), fixed-order fp64.  A pair with a label outside [0,K)
+ *   is counted in no cell.  The correct counts are the matrices' traces: a whole study ends in one small read-back. */
+int  sr_extract_patches_batch(sr_ctx* ctx, const void* imgs, int in_dtype, int F, int H, int W, int C, int patch, int stride,
+                              float mul, float add, int out_dtype, void* out, int64_t out_capacity, int* patches_per_image, void* stream);
+int  sr_patch_vote(sr_ctx* ctx, const float* probs, int F, int P, int K, int32_t* cls_F, float* conf_F, int32_t* votes_FxK, void* stream);
+int  sr_classification_counts(sr_ctx* ctx, const int32_t* y_true_N, const int32_t* preds_AxN, const float* conf_AxN, int A, int N, int K,
+                              int64_t* confusion_AxKxK, double* conf_sums_Ax2, void* stream);
+
 /* ---- the classical study's other four up-scalers (classic_algorithms.py:23-108), 2-D uint8 grayscale, B images of one size ----
  * sr_back_projection: back_projection (classic_algorithms.py:23-43).  hr_u8 [B,H,W] is the starting estimate (the reference starts
  *   from its first argument), lr_u8 [B,h,w] the observation, H >= h, W >= w.  Each of `iterations` rounds: diff = float32(lr) -

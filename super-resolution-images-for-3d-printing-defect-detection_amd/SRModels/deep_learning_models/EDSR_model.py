@@ -98,6 +98,17 @@ class EDSR(DeviceModelMixin):
         sr, metrics = P.patchwise_sr(self.model, lr, patch_size_lr, stride, self.scale_factor, chunk=256)
         return (sr.cpu().numpy() if is_np else sr), metrics
 
+    def super_resolve_images(self, lr_imgs, patch_size_lr=48, stride=24, timed=True):
+        """super_resolve_image over several equally sized LR images in one go (not in the reference; same results image by image, their
+        patches share the predict calls).  Returns ([sr_img...], inference_metrics)."""
+        if not self.trained:
+            raise RuntimeError("Model has not been trained.")
+        if self.scale_factor is None:
+            raise ValueError("scale_factor is not set. Call setup_model first.")
+        conv = [P.as_device_image(self.ctx, im) for im in lr_imgs]
+        srs, metrics = P.patchwise_sr_many(self.model, [c[0] for c in conv], patch_size_lr, stride, self.scale_factor, chunk=256, timed=timed)
+        return [sr.cpu().numpy() if c[1] else sr for sr, c in zip(srs, conv)], metrics
+
     def save(self, directory, timestamp, fmt="npz"):
         """EDSR_model.py:317-328; fmt="h5" writes Keras' weight layout (sr355.h5lite), "npz" this build's container."""
         if not self.trained:

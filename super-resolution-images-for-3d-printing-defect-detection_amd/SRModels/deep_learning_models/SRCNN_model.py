@@ -91,6 +91,16 @@ class SRCNNModel(DeviceModelMixin):
         sr, metrics = P.patchwise_sr(self.model, up, patch_size, stride, 1, chunk=256)
         return (sr.cpu().numpy() if is_np else sr), metrics
 
+    def super_resolve_images(self, lr_imgs, hr_h, hr_w, patch_size=33, stride=14, interpolation=INTER_CUBIC, timed=True):
+        """super_resolve_image over several equally sized LR images in one go (not in the reference; same results image by image, their
+        patches share the predict calls).  Returns ([sr_img...], inference_metrics)."""
+        if not self._trained:
+            raise RuntimeError("Model has not been trained.")
+        conv = [P.as_device_image(self.ctx, im) for im in lr_imgs]
+        ups = [self.ctx.resize(c[0][None], int(hr_h), int(hr_w), interpolation)[0] for c in conv]
+        srs, metrics = P.patchwise_sr_many(self.model, ups, patch_size, stride, 1, chunk=256, timed=timed)
+        return [sr.cpu().numpy() if c[1] else sr for sr, c in zip(srs, conv)], metrics
+
     def save(self, directory, timestamp, fmt="npz"):
         """SRCNN_model.py:249-260 writes SRCNN_<timestamp>.h5; fmt="h5" writes that name in Keras' weight layout (sr355.h5lite),
         the default "npz" this build's own container.  Both load back through setup_model(from_pretrained=True)."""

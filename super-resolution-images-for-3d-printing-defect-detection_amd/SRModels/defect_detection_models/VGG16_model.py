@@ -191,6 +191,71 @@ class FineTunedVGG16(DeviceModelMixin):
         probs = self.model.predict(patches, batch_size=max(int(batch_size), 128))
         return P.majority_vote(probs.float().cpu().numpy())
 
+    # Bytes of fp32 patches one chunk of classify_defects_batch may hold.  Model.predict keeps its whole input and output resident and only
+    # forwards `batch_size` patches at a time, so the patch tensor is the one allocation that grows with the number of frames; 1 GiB is
+    # 9 709 patches of 96 x 96 x 3 fp32: 119 dataset frames (478 x 478, 81 patches) per chunk, and a single 1080p x4 frame (14 400 patches,
+    # 1.5 GiB) is a chunk of its own -- a chunk is never less than one frame.
+    patch_budget_bytes = 1 << 30
+
+    def _frame_stack(self, images):
+        """[F,H,W,3] ndarray / device tensor / list of equally sized images -> contiguous device stack, uint8 (values as they are) when every
+        frame is uint8, else fp32 (`as_device_image`'s conversion per frame)."""
+        ctx = self.ctx
+        if images is None:
+            raise ValueError("images must be provided")
+        if isinstance(images, (list, tuple)):
+            if not images:
+                raise ValueError("images must hold at least one frame")
+            shapes = {tuple(f.shape) for f in images}
+            if len(shapes) != 1:
+                raise ValueError(f"images must all have the same size, got {sorted(shapes)}")
+            if any(len(s) != 3 or s[2] != 3 for s in shapes):
+                raise ValueError("every image must be HxWx3 RGB array")
+            if all(not isinstance(f, torch.Tensor) for f in images):
+                images = np.stack([np.asarray(f) for f in images])
+            else:
+                return torch.stack([P.as_device_image(ctx, f)[0] for f in images])
+        shape = tuple(images.shape)
+        if len(shape) != 4 or shape[3] != 3 or shape[0] < 1:
+            raise ValueError("images must be an [F,H,W,3] RGB stack")
+        if isinstance(images, torch.Tensor):
+            return images.to(ctx.torch_device, torch.uint8 if images.dtype == torch.uint8 else torch.float32).contiguous()
+        a = np.asarray(images)
+        return ctx.to_device(a if a.dtype == np.uint8 else a.astype(np.float32, copy=False))
+
+    def classify_defects_batch(self, images, patch_size=None, stride=None, batch_size=32, raw=False):
+        """classify_defects_method for F equally sized frames with one host read: one batched patch extraction, one predict over all F*P
+        patches, one vote on the device (sr_patch_vote: the reference's rule, fp64 means), one read at the end.
+
+        images: [F,H,W,3] ndarray (uint8 [0,255] or float), device tensor, or list of equally sized images (ValueError otherwise).  Defaults and
+        exceptions are classify_defects_method's.  Returns (classes int64 [F], confidences float64 [F]); raw=True returns the int32 / fp32
+        device tensors and reads nothing.  F is cut into chunks whose fp32 patch tensor stays within `patch_budget_bytes` (1 GiB: predict
+        keeps its whole input resident, see the attribute), at least one frame per chunk; chunks change no frame's result."""
+        if self.model is None:
+            raise ValueError("Model is not built yet.")
+        if patch_size is None:
+            if self.input_shape is None or self.input_shape[0] is None:
+                raise ValueError("Model input size is dynamic; please set patch_size.")
+            patch_size = int(self.input_shape[0])
+        if stride is None:
+            stride = max(1, patch_size // 2)
+        stack = self._frame_stack(images)
+        F, H, W, _ = stack.shape
+        per_frame = self.ctx.num_patches(H, W, 3, patch_size, stride)
+        chunk = max(1, int(self.patch_budget_bytes) // max(1, per_frame * patch_size * patch_size * 3 * 4))
+        cls, conf = [], []
+        for i in range(0, F, chunk):
+            patches = self.ctx.extract_patches_batch(stack[i:i + chunk], patch_size, stride)
+            probs = self.model.predict(patches, batch_size=max(int(batch_size), 128))
+            c, p, _ = self.ctx.patch_vote(probs, len(stack[i:i + chunk]), per_frame, raw=True)
+            cls.append(c)
+            conf.append(p)
+        cls, conf = (cls[0], conf[0]) if len(cls) == 1 else (torch.cat(cls), torch.cat(conf))
+        if raw:
+            return cls, conf
+        both = torch.stack([cls.to(torch.float32), conf]).cpu().numpy()              # a class index is exact in fp32: one read for both
+        return both[0].astype(np.int64), both[1].astype(np.float64)
+
     def save(self, directory, timestamp, fmt="npz"):
         """VGG16_model.py:272-283; fmt="h5" writes Keras' weight layout (sr355.h5lite), "npz" this build's container."""
         if not self.trained:

@@ -110,6 +110,9 @@ SIGNATURES = {
     "sr_spectral_l1": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_extract_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _i64, C.POINTER(_i), _vp]),
     "sr_overlap_add": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
+    "sr_extract_patches_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _vp, _i64, C.POINTER(_i), _vp]),
+    "sr_patch_vote": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "sr_classification_counts": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sr_back_projection": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_noise_sigma": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "sr_nl_means": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp]),

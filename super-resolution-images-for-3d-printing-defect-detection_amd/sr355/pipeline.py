@@ -102,7 +102,7 @@ def sr_then_classify(sr_model, classifier, lr_img, sr_kwargs=None, patch_size=96
 
 
 def stream_sr_classify(sr_model, classifier, frames, sr_kwargs=None, patch_size=96, stride=48, batch_size=512, rank=0, world=1,
-                       keep_sr=False):
+                       keep_sr=False, vote="host"):
     """BASELINE configs[4]: a stream of LR frames -> x4 super-resolution -> VGG16 patch vote per frame, everything between the host
     frame and the (class, confidence) pair resident on the GPU.
 
@@ -115,9 +115,17 @@ def stream_sr_classify(sr_model, classifier, frames, sr_kwargs=None, patch_size=
     * double-buffered ingest: frame i+1 crosses PCIe (pinned staging, a second HIP stream) while frame i is in the generator;
     * the SR frame never leaves HBM: the classifier's 96x96 patches are cut from it on the device.
 
+    vote="host" (the default) votes on the host per frame: `classify_defects_method` reads the frame's probabilities back, so every
+    frame ends in a synchronising copy.  vote="device" runs `classify_defects_batch(raw=True)` on the frame: its (class, confidence) stay on
+    the device, the loop never reads, and the results are gathered in one read after the last frame -- the next frame's ingest then overlaps
+    the whole frame, not only its SR.  With vote="device", `host_ms_per_frame_classify` is enqueue time only (the work is still in flight
+    when the clock is read); the records and the stats keys are the same in both modes.
+
     frames: sequence of [H,W,3] arrays (uint8 [0,255] or float [0,1]) or device tensors.  Returns
     ([{'frame', 'class', 'confidence', 'sr' (only if keep_sr)}...] for this rank's frames, stats dict)."""
     from .dist import shard_range
+    if vote not in ("host", "device"):
+        raise ValueError(f"vote must be 'host' or 'device', got {vote!r}")
     ctx = sr_model.ctx
     dev = ctx.torch_device
     lo, hi = shard_range(len(frames), rank, world)
@@ -142,7 +150,7 @@ def stream_sr_classify(sr_model, classifier, frames, sr_kwargs=None, patch_size=
             ev.record(copy_stream)
         staged[slot] = (t, ev, host)                        # keep the pinned buffer alive until the copy has been consumed
 
-    results = []
+    results, pending = [], []
     t_sr = t_cls = 0.0
     out_pix = 0
     torch.cuda.synchronize(dev)
@@ -161,8 +169,12 @@ def stream_sr_classify(sr_model, classifier, frames, sr_kwargs=None, patch_size=
         a = time.perf_counter()
         sr, _ = sr_model.super_resolve_image(lr.contiguous(), **(sr_kwargs or {}))
         b = time.perf_counter()
-        cls, conf = classifier.classify_defects_method(sr, patch_size=patch_size, stride=stride, batch_size=batch_size)
-        c = time.perf_counter()                             # the vote needs the probabilities on the host: the frame is complete here
+        if vote == "device":
+            pending.append(classifier.classify_defects_batch(sr[None], patch_size=patch_size, stride=stride, batch_size=batch_size, raw=True))
+            cls = conf = -1                                 # filled in after the loop
+        else:
+            cls, conf = classifier.classify_defects_method(sr, patch_size=patch_size, stride=stride, batch_size=batch_size)
+        c = time.perf_counter()                             # vote="host": the vote needs the probabilities on the host, the frame is complete here
         t_sr += b - a
         t_cls += c - b
         out_pix += int(sr.shape[0]) * int(sr.shape[1])
@@ -171,6 +183,10 @@ def stream_sr_classify(sr_model, classifier, frames, sr_kwargs=None, patch_size=
             rec["sr"] = sr
         results.append(rec)
         staged[k & 1] = None
+    if pending:                                             # vote="device": every frame's pair in one read
+        got = torch.stack([torch.cat([c.to(torch.float32), p]) for c, p in pending]).cpu().numpy()
+        for rec, (c, p) in zip(results, got):
+            rec["class"], rec["confidence"] = int(c), float(p)
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
     n = max(len(mine), 1)

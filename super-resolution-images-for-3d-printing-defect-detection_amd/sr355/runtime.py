@@ -1025,6 +1025,76 @@ class Context:
                                                dtype_code(out_dtype), out.data_ptr(), out.numel(), C.byref(cnt), self.stream()))
         return out
 
+    def extract_patches_batch(self, imgs, patch, stride, mul=1.0, add=0.0, out_dtype=torch.float32):
+        """extract_patches for a stack: imgs [F,H,W,C] fp32 or uint8 (the value float(u8)) -> [F*P,patch,patch,C], frame-major, one launch.
+        Frame f's slice is bit for bit extract_patches(imgs[f].float(), ...)."""
+        _check_tensor(self, imgs, "extract_patches_batch images", (torch.float32, torch.uint8))
+        if imgs.dim() != 4:
+            raise ValueError("extract_patches_batch images: expected [F,H,W,C]")
+        F, H, W, Cx = imgs.shape
+        if F == 0:
+            raise ValueError("extract_patches_batch images: empty stack")
+        n = C.c_int()
+        args = (self.h, imgs.data_ptr(), dtype_code(imgs.dtype), F, H, W, Cx, int(patch), int(stride), float(mul), float(add), dtype_code(out_dtype))
+        self.check(self.lib.sr_extract_patches_batch(*args, None, 0, C.byref(n), None))
+        out = self.empty((F * n.value, patch, patch, Cx), out_dtype)
+        self.check(self.lib.sr_extract_patches_batch(*args, out.data_ptr(), out.numel(), C.byref(n), self.stream()))
+        return out
+
+    def patch_vote(self, probs, F, P, raw=False):
+        """The majority vote of VGG16_model.py:252-268 for F frames of P patches: probs [F*P,K] device tensor (1 <= K <= 64) ->
+        (classes [F], confidences [F], votes [F,K]).  raw=True: the int32 / fp32 / int32 device tensors, nothing is read; otherwise NumPy
+        int64 / float64 / int64 (one synchronising read each).  The confidence is the winner's fp64 mean rounded once to fp32."""
+        _check_tensor(self, probs, "patch_vote probs", (torch.float32, torch.bfloat16))
+        if probs.dtype != torch.float32:
+            probs = probs.float()
+        F, P = int(F), int(P)
+        if probs.dim() != 2 or F < 1 or P < 1 or probs.shape[0] != F * P:
+            raise ValueError("patch_vote probs: expected [F*P,K] with F, P >= 1")
+        K = int(probs.shape[1])
+        cls, conf, votes = self.empty((F,), torch.int32), self.empty((F,), torch.float32), self.empty((F, max(K, 1)), torch.int32)
+        self.check(self.lib.sr_patch_vote(self.h, probs.data_ptr(), F, P, K, cls.data_ptr(), conf.data_ptr(), votes.data_ptr(), self.stream()))
+        if raw:
+            return cls, conf, votes
+        return cls.cpu().numpy().astype(np.int64), conf.cpu().numpy().astype(np.float64), votes.cpu().numpy().astype(np.int64)
+
+    def _labels(self, a, name, num_classes):
+        """int32 device labels; labels the host supplies are checked against [0, num_classes) here, device labels are taken as they are."""
+        if isinstance(a, torch.Tensor) and a.device == self.torch_device:
+            return _check_tensor(self, a if a.dtype == torch.int32 else a.to(torch.int32), name, (torch.int32,))
+        h = np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
+        if h.size and (h.min() < 0 or h.max() >= num_classes):
+            raise ValueError(f"{name}: labels must lie in [0, {num_classes})")
+        return self.to_device(h.astype(np.int32))
+
+    def classification_counts(self, y_true, preds, conf=None, num_classes=None):
+        """y_true [N], preds [A,N] (and conf [A,N]) -> (confusion int64 [A,K,K], rows = true class; conf_sums float64 [A,2] = sum of conf, sum
+        of conf over the correct predictions), both device tensors (nothing is read here: sr355.study gathers them with the labels into one read).  Host arrays are validated against [0,K) and uploaded; device tensors (as sr_patch_vote writes them) are
+        used in place.  num_classes may be omitted only when y_true and preds are host arrays (1 + their largest label)."""
+        on_dev = lambda t: isinstance(t, torch.Tensor) and t.device == self.torch_device
+        if num_classes is None:
+            if on_dev(y_true) or on_dev(preds):
+                raise ValueError("classification_counts: num_classes is required with device labels (finding it would need a read)")
+            num_classes = 1 + max(int(np.max(np.asarray(y_true), initial=0)), int(np.max(np.asarray(preds), initial=0)))
+        K = int(num_classes)
+        y = self._labels(y_true, "classification_counts y_true", K).reshape(-1)
+        p = self._labels(preds, "classification_counts preds", K)
+        p = p.reshape(1, -1) if p.dim() == 1 else p
+        A, N = int(p.shape[0]), int(y.shape[0])
+        if p.dim() != 2 or p.shape[1] != N or A < 1 or N < 1 or K < 1:
+            raise ValueError("classification_counts: y_true [N] and preds [A,N] with A, N, K >= 1")
+        cf = None
+        if conf is not None:
+            cf = conf if on_dev(conf) else self.to_device(np.asarray(conf.cpu() if isinstance(conf, torch.Tensor) else conf, np.float32))
+            cf = _check_tensor(self, cf.reshape(p.shape) if cf.numel() == p.numel() else cf, "classification_counts conf")
+            if cf.shape != p.shape:
+                raise ValueError("classification_counts: conf must have the shape of preds")
+        words = self.empty((A * K * K + 2 * A,), torch.int64)
+        cm, sums = words[:A * K * K].view(A, K, K), words[A * K * K:].view(torch.float64).view(A, 2)
+        self.check(self.lib.sr_classification_counts(self.h, y.data_ptr(), p.data_ptr(), None if cf is None else cf.data_ptr(), A, N, K,
+                                                     cm.data_ptr(), sums.data_ptr(), self.stream()))
+        return cm, sums
+
     def overlap_add(self, patches, H, W, patch, stride, scale=1, mul=1.0, add=0.0):
         _check_tensor(self, patches, "overlap_add patches", (torch.float32, torch.bfloat16))
         Cx = patches.shape[-1]
