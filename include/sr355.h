@@ -588,6 +588,20 @@ int  sr_lpips(sr_ctx* ctx, const void* a, const void* b, int dtype, int B, int H
  *   holds (a clamped entry gives another valid window, not an error: the host validates tables before upload).  SR_ERR_INVALID, and no
  *   launch, for a null pointer, a dtype other than the two, N, H, W, B, patch or scale < 1, offset < 0 or offset + B > n_order, n_windows < 1,
  *   a pad outside 0 .. n - 1, a patch larger than a side's padded image, or a batch of 2^31 values or more.
+ * sr_gather_warp_patches: ONE launch writes an augmented batch y DEVICE fp32 [B,patch_h,patch_w,3] of the classifier's fit
+ *   (load_defects_dataset_as_patches, loading_methods.py:194-285, then VGG16_model.py:129-134) from a frame stack src DEVICE [N,H,W,3] of
+ *   `dtype` SR_DTYPE_U8 or SR_DTYPE_F32.  windows, order, n_order, offset, B and swap_rb as in sr_gather_patch_pairs (no padding: the
+ *   defects loader's windows never reach it); params DEVICE fp32 [B,16] in sr_affine_warp's layout (fp64 values split hi / lo, flip flag at
+ *   [12]).  Batch element b is, bit for bit, what sr_affine_warp returns for the patch a one-sided sr_gather_patch_pairs (pads 0) cuts for
+ *   window order[offset + b]: output pixel (oy, ox) samples PATCH coordinates (a00 oy + a01 ox + o0, a10 oy + a11 ox + o1) in the same
+ *   double-float arithmetic, both tap indices clamped to the patch ([0, patch_h - 1], [0, patch_w - 1]: the frame's pixels next to the window
+ *   never enter), the flip mirrors over patch_w, a uint8 tap is float(u) / 255.0f correctly rounded (an fp32 tap its stored bits), and the
+ *   four taps are combined by the same rounded products and sums.  An integer sample point (identity, flip, integer shift) copies the
+ *   gathered value exactly.  The coordinates are computed once per pixel and serve its three channels.
+ *   Safety: every order entry and image index is clamped into range and the window origin into [0, H - patch_h] x [0, W - patch_w], so no
+ *   table reads outside the stack (the host validates tables before upload).  SR_ERR_INVALID, and no launch, for a null pointer, a dtype
+ *   other than the two, N, H, W, B or a patch size < 1, a patch larger than the frame (or >= 2^24), offset < 0 or offset + B > n_order,
+ *   n_windows < 1, B > 65535, or a batch of 2^31 values or more.
  * sr_clip_by_norm_bucket: tf.clip_by_norm per variable of a flat fp32 gradient bucket, in place (sr355/train.py Adam.apply): table DEVICE
  *   int64 [n_vars,2] = (offset, length) per variable; nrm = sqrt(sum g^2) accumulated in fp64 from the fp32 values; where nrm > clipnorm,
  *   g *= float(clipnorm / nrm) (fp64 division, rounded to fp32, one fp32 product per element); scales_out DEVICE fp32 [n_vars] receives the
@@ -606,6 +620,9 @@ typedef struct {
 } sr_patch_side;
 int  sr_gather_patch_pairs(sr_ctx* ctx, const sr_patch_side* lr, const sr_patch_side* hr, const int32_t* windows, int n_windows,
                            const int32_t* order, int64_t n_order, int64_t offset, int B, int patch_h, int patch_w, int scale, void* stream);
+int  sr_gather_warp_patches(sr_ctx* ctx, const void* src, int dtype, int N, int H, int W, const int32_t* windows, int n_windows,
+                            const int32_t* order, int64_t n_order, int64_t offset, int B, int patch_h, int patch_w, int swap_rb,
+                            const float* params, float* y, void* stream);
 int  sr_clip_by_norm_bucket(sr_ctx* ctx, float* flat_g, int64_t bucket_len, const int64_t* table, int n_vars, double clipnorm, float* scales_out,
                             void* stream);
 

@@ -118,23 +118,37 @@ class FineTunedVGG16(DeviceModelMixin):
         features (2 KiB per image, kept) are computed, once.  The random draws stay
         the host's, draw for draw those of the host path (_augment / fit_head): per epoch the permutation and the augmentation parameters on
         this generator, uploaded with the dropout masks in one copy.  The base is frozen with and without base_trainable, as in the reference
-        (setup_model).  With augmentation the batches are 32 images, as the reference's datagen.flow(..., batch_size=32) hard-codes."""
+        (setup_model).  With augmentation the batches are 32 images, as the reference's datagen.flow(..., batch_size=32) hard-codes.
+        X_train and / or X_val may be the X view of a sr355.patches.LabeledPatches (load_defects_dataset_as_patches(..., on_device=True)):
+        then no fp32 patch array of that set exists anywhere -- each epoch's permutation goes up through set_order, a training batch is one
+        sr_gather_warp_patches launch on the resident uint8 frames (the identity parameters without augmentation) and the validation
+        features come from batch() chunks of 256 -- and the history and the head are, bit for bit, those of the equivalent arrays."""
         from sr355.train import fit_head_device
         if self.model is None:
             raise ValueError("Model is not built yet.")
-        X_train, y_train = np.asarray(X_train, np.float32), np.asarray(y_train, np.int64).reshape(-1)
-        X_val, y_val = np.asarray(X_val, np.float32), np.asarray(y_val, np.int64).reshape(-1)
+        from sr355.patches import labeled_dataset
+        ds_train, ds_val = labeled_dataset(X_train), labeled_dataset(X_val)
+        y_train, y_val = np.asarray(y_train, np.int64).reshape(-1), np.asarray(y_val, np.int64).reshape(-1)
+        if ds_train is None:
+            X_train = np.asarray(X_train, np.float32)
+        if ds_val is None:
+            X_val = np.asarray(X_val, np.float32)
         nc = int(np.asarray(self.weights["predictions"][0]).shape[-1])
         if len(y_train) != len(X_train) or (len(y_train) and (y_train.min() < 0 or y_train.max() >= nc)):
             raise ValueError(f"y_train: one label in [0, {nc}) per training image")
         rng = np.random.default_rng(seed)
         bs = 32 if use_augmentation else int(batch_size)
         n, (h, w) = len(X_train), X_train.shape[1:3]
-        Xd = self.ctx.to_device(X_train)
-        Xv = self.ctx.to_device(X_val)
-        g_val = [self._gap_device(Xv[i:i + 256]) for i in range(0, len(X_val), 256)]
+        Xd = self.ctx.to_device(X_train) if ds_train is None else None
+        if ds_val is None:
+            Xv = self.ctx.to_device(X_val)
+            g_val = [self._gap_device(Xv[i:i + 256]) for i in range(0, len(X_val), 256)]
+            del Xv
+        else:
+            ov = ds_val.set_order(np.arange(len(ds_val))) if len(ds_val) else None
+            g_val = [self._gap_device(ds_val.batch(ov, i, min(256, len(ds_val) - i))) for i in range(0, len(ds_val), 256)]
         g_val = g_val[0] if len(g_val) == 1 else (torch.cat(g_val) if g_val else self.ctx.empty((0, 512)))
-        del Xv
+        epoch_order = {}
 
         def draw_epoch(epoch):
             order = rng.permutation(n)
@@ -142,10 +156,17 @@ class FineTunedVGG16(DeviceModelMixin):
                 rot, off, flip = self._augment_params(rng, n, h, w)
             else:
                 rot, off, flip = np.broadcast_to(np.eye(2), (n, 2, 2)), np.zeros((n, 2)), np.zeros(n, bool)
-            return {"idx": order.astype(np.int32), "labels": y_train[order].astype(np.int32), "warp": self.ctx.warp_params(rot, off, flip)}
+            plan = {"labels": y_train[order].astype(np.int32), "warp": self.ctx.warp_params(rot, off, flip)}
+            if ds_train is None:
+                plan["idx"] = order.astype(np.int32)
+            else:
+                epoch_order["dev"] = ds_train.set_order(order)          # validated on the host, as table rows
+            return plan
 
         def features(dev, i, j):
-            return self._gap_device(self.ctx.affine_warp(Xd, dev["idx"][i:j], dev["warp"][i:j]))
+            if ds_train is None:
+                return self._gap_device(self.ctx.affine_warp(Xd, dev["idx"][i:j], dev["warp"][i:j]))
+            return self._gap_device(ds_train.warped_batch(epoch_order["dev"], i, j - i, dev["warp"][i:j]))
 
         head, history = fit_head_device(self.ctx, features, self.weights, draw_epoch, n, g_val, y_val, learning_rate=self.learning_rate, batch_size=bs,
                                         epochs=epochs, dropout_rate=self.dropout_rate, l2_reg=self.l2_reg, seed=seed)
@@ -160,7 +181,8 @@ class FineTunedVGG16(DeviceModelMixin):
         from sr355.train import sparse_cce
         if not self.trained:
             raise RuntimeError("Model has not been trained.")
-        p = np.asarray(self.predict(np.asarray(X_test, np.float32)), np.float64)
+        from sr355.patches import labeled_dataset
+        p = np.asarray(self.predict(X_test if labeled_dataset(X_test) is not None else np.asarray(X_test, np.float32)), np.float64)
         loss, acc = sparse_cce(p, np.asarray(y_test, np.int64).reshape(-1))
         if self.l2_reg > 0:
             loss += self.l2_reg * float(np.sum(np.asarray(self.weights["dense"][0], np.float64) ** 2))
@@ -168,7 +190,19 @@ class FineTunedVGG16(DeviceModelMixin):
         return [loss, acc]
 
     def predict(self, patches, batch_size=32):
-        return self.model.predict(patches, batch_size=batch_size)
+        """model.predict.  A view of a sr355.patches.LabeledPatches is gathered on the device in chunks that are multiples of batch_size, so
+        every forward sees the patches it would see in the array, and gives the array's result."""
+        from sr355.patches import labeled_dataset
+        ds = labeled_dataset(patches)
+        if ds is None:
+            return self.model.predict(patches, batch_size=batch_size)
+        bs = max(1, int(batch_size))
+        chunk, n = bs * max(1, 4096 // bs), len(ds)
+        if n == 0:
+            return np.zeros((0, int(np.asarray(self.weights["predictions"][0]).shape[-1])), np.float32)
+        order = ds.set_order(np.arange(n))
+        return np.concatenate([self.model.predict(ds.batch(order, i, min(chunk, n - i)), batch_size=bs).float().cpu().numpy()
+                               for i in range(0, n, chunk)])
 
     def classify_defects_method(self, image, patch_size=None, stride=None, batch_size=32):
         """Patch the image, classify every patch, majority vote (VGG16_model.py:168-270).

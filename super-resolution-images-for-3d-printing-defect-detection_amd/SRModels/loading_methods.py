@@ -123,8 +123,15 @@ def _load_class_map(class_map_path):
     return m
 
 
-def load_defects_dataset_as_patches(hr_root, patch_size=33, stride=14, class_map_path=None):
-    """HR patches + the class id of their image (loading_methods.py:194-285)."""
+def load_defects_dataset_as_patches(hr_root, patch_size=33, stride=14, class_map_path=None, on_device=False):
+    """HR patches + the class id of their image (loading_methods.py:194-285).
+    on_device=True: X is the view ds.X of a sr355.patches.LabeledPatches -- the same patches in the same order, cut (and augmented) on the
+    device from the resident uint8 frames when FineTunedVGG16.fit asks for a batch -- and y the same int64 array (X.ds is the dataset;
+    X[idx] and sklearn's train_test_split(X, y) give views of subsets)."""
+    if on_device:
+        from sr355.patches import LabeledPatches
+        ds = LabeledPatches.from_dirs(hr_root, patch_size, stride, class_map_path)
+        return ds.X, ds.y
     if not os.path.exists(hr_root):
         raise ValueError("HR root directory must exist.")
     if not os.path.isdir(hr_root):

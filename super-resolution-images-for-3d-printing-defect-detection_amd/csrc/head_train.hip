@@ -16,6 +16,7 @@
 //     No float atomics: the gradients and the statistics are the same bits on every run.  At 32 x 512 x 256 the products are 4 MFLOP per step,
 //     ~1 us of VALU work spread over the grid: the step is bound by its launches, not by its arithmetic.
 #include "common.h"
+#include "warp_sample.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,31 +24,6 @@
 namespace {
 
 constexpr int HIN = 512, HHID = 256, HROWS = 8;
-constexpr int WARP_PRM = 16;          // per image: hi(a00 a01 a10 a11 o0 o1), lo(same), flip, 3 unused
-
-__device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
-    s = __fadd_rn(a, b);
-    const float bb = __fsub_rn(s, a);
-    e = __fadd_rn(__fsub_rn(a, __fsub_rn(s, bb)), __fsub_rn(b, bb));
-}
-
-// ah * u + bh * v + oh (+ the lo halves) for integer u, v -> floor and fraction in [0, 1)
-__device__ __forceinline__ void coord(const float* h, const float* l, int k, float u, float v, int lim, int& i0, float& t) {
-    const float p1 = __fmul_rn(h[2 * k], u), e1 = __fmaf_rn(h[2 * k], u, -p1);
-    const float p2 = __fmul_rn(h[2 * k + 1], v), e2 = __fmaf_rn(h[2 * k + 1], v, -p2);
-    float s, t1, s2, t2;
-    two_sum(p1, p2, s, t1);
-    two_sum(s, h[4 + k], s2, t2);
-    const float lo = __fadd_rn(__fadd_rn(__fadd_rn(t1, t2), __fadd_rn(e1, e2)),
-                               __fadd_rn(__fadd_rn(__fmul_rn(l[2 * k], u), __fmul_rn(l[2 * k + 1], v)), l[4 + k]));
-    float f = floorf(s2);
-    float fr = __fadd_rn(__fsub_rn(s2, f), lo);
-    if (fr < 0.f) { f = __fsub_rn(f, 1.f); fr = __fadd_rn(fr, 1.f); }
-    if (fr >= 1.f) { f = __fadd_rn(f, 1.f); fr = __fsub_rn(fr, 1.f); }
-    f = fminf(fmaxf(f, -1.f), (float)lim);          // beyond the border both taps clamp to the edge; keeps the int conversion in range
-    i0 = (int)f;
-    t = fr;
-}
 
 template <int VEC>
 __global__ void __launch_bounds__(256) affine_warp_kernel(const float* __restrict__ x, int N, int H, int W, int C, const int* __restrict__ idx,
@@ -75,18 +51,10 @@ __global__ void __launch_bounds__(256) affine_warp_kernel(const float* __restric
                 const int oy = (int)(pix / W);
                 int ox = (int)(pix - (int64_t)oy * W);
                 if (flip) ox = W - 1 - ox;
-                int y0, x0;
-                float ty, tx;
-                coord(hi, lo, 0, (float)oy, (float)ox, H, y0, ty);
-                coord(hi, lo, 1, (float)oy, (float)ox, W, x0, tx);
-                const int ya = min(max(y0, 0), H - 1), yb = min(max(y0 + 1, 0), H - 1);
-                const int xa = min(max(x0, 0), W - 1), xb = min(max(x0 + 1, 0), W - 1);
-                const float v00 = xi[((int64_t)ya * W + xa) * C + c], v01 = xi[((int64_t)ya * W + xb) * C + c];
-                const float v10 = xi[((int64_t)yb * W + xa) * C + c], v11 = xi[((int64_t)yb * W + xb) * C + c];
-                const float wy0 = __fsub_rn(1.f, ty), wx0 = __fsub_rn(1.f, tx);
-                const float top = __fadd_rn(__fmul_rn(wx0, v00), __fmul_rn(tx, v01));
-                const float bot = __fadd_rn(__fmul_rn(wx0, v10), __fmul_rn(tx, v11));
-                val = __fadd_rn(__fmul_rn(wy0, top), __fmul_rn(ty, bot));
+                const WarpTaps t = warp_taps(hi, lo, oy, ox, H, W);
+                const float v00 = xi[((int64_t)t.ya * W + t.xa) * C + c], v01 = xi[((int64_t)t.ya * W + t.xb) * C + c];
+                const float v10 = xi[((int64_t)t.yb * W + t.xa) * C + c], v11 = xi[((int64_t)t.yb * W + t.xb) * C + c];
+                val = bilerp(v00, v01, v10, v11, t.ty, t.tx);
             }
             out[q] = val;
         }

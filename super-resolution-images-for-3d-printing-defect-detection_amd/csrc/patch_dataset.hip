@@ -11,8 +11,12 @@
 //     the identity, so the default batch is a copy of the stored values.
 // Memory-bound and small (a batch is a few hundred KB): one thread per pixel (three channels), no LDS.  Every table entry is clamped into
 // range before it is used as an index: whatever the window table and the order hold, no thread reads outside the stacks.
+// sr_gather_warp_patches does the same for the classifier's fit (load_defects_dataset_as_patches: one stack, no padding) and applies the
+// augmentation warp of sr_affine_warp on the way, with that kernel's own arithmetic (warp_sample.h): no fp32 patch ever lies in memory.
 #include "common.h"
+#include "warp_sample.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace {
@@ -71,6 +75,61 @@ __global__ void __launch_bounds__(256) gather_patch_pairs_kernel(Side lr, Side h
     }
 }
 
+// sr_gather_warp_patches: the classifier fit's augmented batch straight from the frame stack.  Workgroups (x, b) share batch element b: its
+// window and its sixteen parameters are read once per thread, then each thread takes whole pixels -- the two coordinates are computed once
+// and serve the three channels.  The taps are clamped to the PATCH, so the window's neighbours in the frame never enter the result.
+struct WarpSrc {
+    const void* src;
+    int u8, N, H, W, swap, ph, pw;
+};
+
+__device__ __forceinline__ void load_tap(const WarpSrc& s, int64_t pix, float (&v)[3]) {
+    if (s.u8) {
+        const uint8_t* p = static_cast<const uint8_t*>(s.src) + pix * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = __fdiv_rn((float)p[c], 255.0f);
+    } else {
+        const float* p = static_cast<const float*>(s.src) + pix * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = p[c];
+    }
+}
+
+__global__ void __launch_bounds__(256) gather_warp_patches_kernel(WarpSrc s, const int32_t* __restrict__ windows, int n_windows,
+                                                                  const int32_t* __restrict__ order, int64_t offset, const float* __restrict__ prm,
+                                                                  float* __restrict__ y) {
+    const int b = blockIdx.y;
+    const int k = clampi(order[offset + b], 0, n_windows - 1);
+    const int img = clampi(windows[3 * (int64_t)k], 0, s.N - 1);
+    const int y0 = clampi(windows[3 * (int64_t)k + 1], 0, s.H - s.ph), x0 = clampi(windows[3 * (int64_t)k + 2], 0, s.W - s.pw);
+    const float* p = prm + (int64_t)b * WARP_PRM;
+    float hi[6], lo[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) { hi[q] = p[q]; lo[q] = p[6 + q]; }
+    const bool flip = p[12] != 0.f;
+    const int64_t origin = ((int64_t)img * s.H + y0) * s.W + x0;          // the window's first pixel in the stack
+    const int per = s.ph * s.pw;
+    float* yo = y + (int64_t)b * per * 3;
+    for (int pix = blockIdx.x * 256 + threadIdx.x; pix < per; pix += gridDim.x * 256) {
+        const int oy = pix / s.pw;
+        int ox = pix - oy * s.pw;
+        if (flip) ox = s.pw - 1 - ox;
+        const WarpTaps t = warp_taps(hi, lo, oy, ox, s.ph, s.pw);          // indices within the patch: 0 .. ph - 1, 0 .. pw - 1
+        float v00[3], v01[3], v10[3], v11[3];
+        load_tap(s, origin + (int64_t)t.ya * s.W + t.xa, v00);
+        load_tap(s, origin + (int64_t)t.ya * s.W + t.xb, v01);
+        load_tap(s, origin + (int64_t)t.yb * s.W + t.xa, v10);
+        load_tap(s, origin + (int64_t)t.yb * s.W + t.xb, v11);
+        float* o = yo + (int64_t)pix * 3;
+        float r[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = bilerp(v00[c], v01[c], v10[c], v11[c], t.ty, t.tx);
+        o[0] = s.swap ? r[2] : r[0];
+        o[1] = r[1];
+        o[2] = s.swap ? r[0] : r[2];
+    }
+}
+
 // -> nullptr when the side is usable, else what is wrong with it
 const char* side_problem(const sr_patch_side& s, int ph, int pw) {
     if (!s.src || !s.out) return "gather_patch_pairs: null stack or batch";
@@ -115,6 +174,29 @@ int sr_gather_patch_pairs(sr_ctx* ctx, const sr_patch_side* lr, const sr_patch_s
     const int64_t g = (n_lr + n_hr + 255) / 256;
     hipLaunchKernelGGL(gather_patch_pairs_kernel, dim3((unsigned)(g > 8192 ? 8192 : g)), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, windows,
                        n_windows, order, offset, n_lr, n_hr);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+int sr_gather_warp_patches(sr_ctx* ctx, const void* src, int dtype, int N, int H, int W, const int32_t* windows, int n_windows, const int32_t* order,
+                           int64_t n_order, int64_t offset, int B, int patch_h, int patch_w, int swap_rb, const float* params, float* y, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!src || !windows || !order || !params || !y) return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: null pointer");
+    if (dtype != SR_DTYPE_U8 && dtype != SR_DTYPE_F32) return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: the stack is uint8 or fp32");
+    if (N < 1 || H < 1 || W < 1 || B < 1 || patch_h < 1 || patch_w < 1 || n_windows < 1)
+        return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: N, H, W, B, patch and n_windows must be >= 1");
+    if (patch_h > H || patch_w > W) return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: the patch is larger than the frame");
+    if (offset < 0 || n_order < 1 || offset > n_order - B) return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: the batch reaches outside the order array");
+    if (patch_h >= (1 << 24) || patch_w >= (1 << 24)) return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: patch too large");      // exact as fp32
+    const int64_t vals = (int64_t)patch_h * patch_w * 3;
+    if (B > 65535 || vals >= ((int64_t)1 << 31) || B * vals >= ((int64_t)1 << 31))
+        return ctx->fail(SR_ERR_INVALID, "gather_warp_patches: a batch holds at most 65535 patches and fewer than 2^31 values");
+    const WarpSrc s{src, dtype == SR_DTYPE_U8, N, H, W, swap_rb != 0, patch_h, patch_w};
+    const int per = patch_h * patch_w;
+    const unsigned gx = (unsigned)std::min((per + 255) / 256, 1024);
+    hipLaunchKernelGGL(gather_warp_patches_kernel, dim3(gx, (unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), s, windows, n_windows, order,
+                       offset, params, y);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
 }

@@ -138,6 +138,7 @@ SIGNATURES = {
     "sr_lpips_set_weights": (_i, [_vp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]),
     "sr_lpips": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(_vp), _vp]),
     "sr_gather_patch_pairs": (_i, [_vp, C.POINTER(PatchSide), C.POINTER(PatchSide), _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp]),
+    "sr_gather_warp_patches": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_clip_by_norm_bucket": (_i, [_vp, _vp, _i64, _vp, _i, C.c_double, _vp, _vp]),
 }
 

@@ -13,6 +13,11 @@ Window rules (`window_table`), copied from the loader with its quirks:
     slice would come out short;
   * `srcnn` mode pads both (equal-size) sides alike and walks the padded extents.
 Everything in this module up to the first `batch()` / `.numpy()` runs without a GPU (scale mode: the stacks are uploaded on first use).
+
+`LabeledPatches` is the classifier's counterpart (reference: loading_methods.py:194-285, load_defects_dataset_as_patches): one frame stack, the
+loader's windows over the UNPADDED extents (`window_table_defects`: that loader pads but never walks the padding, so the dataset needs none),
+one class id per frame.  `batch()` cuts the loader's patches and `warped_batch()` the augmented ones FineTunedVGG16.fit trains on
+(sr_gather_warp_patches), so the fit holds the distinct pixels once, as uint8, instead of every overlapping window in fp32.
 """
 import os
 import pickle
@@ -292,6 +297,219 @@ class PatchPairs:
         lr = dict(stack=s.lr, pad=s.lr_pad, swap=s.swap[0], mul=mul, add=add)
         hr = dict(stack=s.hr, pad=s.hr_pad, swap=s.swap[1], mul=mul, add=add)
         return s.ctx.gather_patch_pairs(lr, hr, s.table_dev, order_dev, offset, B, s.patch_size, s.scale)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the classifier's dataset
+def window_table_defects(n_images, hw, patch_size, stride):
+    """load_defects_dataset_as_patches' windows (loading_methods.py:194-285) for n_images frames of size hw: range(0, n - patch + 1, stride)
+    over the UNPADDED extents (the loader pads and then walks the unpadded size, so no window touches the padding), image by image, rows
+    then columns -> int32 [n,3] rows (image, y, x).  Pure host code.  ValueError where the patch exceeds the frame: no windows."""
+    for v, name in ((patch_size, "patch_size"), (stride, "stride")):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
+            raise ValueError(f"{name} must be positive int.")
+    h, w = (int(v) for v in hw)
+    if patch_size > h or patch_size > w:
+        raise ValueError(f"a {patch_size} x {patch_size} patch exceeds the {h} x {w} frame: the dataset would hold no windows")
+    per = np.array([(i, j) for i in range(0, h - patch_size + 1, stride) for j in range(0, w - patch_size + 1, stride)], np.int32).reshape(-1, 2)
+    table = np.zeros((int(n_images) * len(per), 3), np.int32)
+    table[:, 0] = np.repeat(np.arange(int(n_images), dtype=np.int32), len(per))
+    table[:, 1:] = np.tile(per, (int(n_images), 1))
+    return table
+
+
+class _LabeledStore:
+    """What every subset of one LabeledPatches shares: the frame stack (a host array until its first device use), the full window table and
+    the label of every window."""
+
+    def __init__(self, frames, table, labels, patch_size, swap, ctx=None):
+        self.frames, self.table, self.labels, self.patch_size, self.swap, self.ctx = frames, table, labels, int(patch_size), bool(swap), ctx
+        self.table_dev = None
+
+    def on_device(self):
+        """Uploads what is still on the host: the stack, once, and the table."""
+        import torch
+        from . import Context
+        if self.ctx is None:
+            self.ctx = Context.get()
+        if not isinstance(self.frames, torch.Tensor):
+            self.frames = self.ctx.to_device(self.frames)
+        if self.table_dev is None:
+            self.table_dev = self.ctx.to_device(self.table)
+        return self
+
+
+class LabeledView:
+    """`ds.X`: what load_defects_dataset_as_patches' X array is to a caller that passes it on or splits it -- shape, dtype, ndim, len, and
+    X[idx] for a 1-D integer array or a slice (the view of ds.subset(idx), so sklearn's train_test_split(X, y) works on it as on the array) --
+    and `.numpy()` for the values.  FineTunedVGG16.fit / evaluate / predict recognise it and batch from the dataset directly."""
+    dtype = np.dtype(np.float32)
+
+    def __init__(self, ds):
+        self.ds = ds
+
+    def __len__(self):
+        return len(self.ds)
+
+    @property
+    def shape(self):
+        return (len(self.ds), self.ds.patch_size, self.ds.patch_size, 3)
+
+    @property
+    def ndim(self):
+        return 4
+
+    def __getitem__(self, idx):
+        if isinstance(idx, tuple):          # X[idx, ...] / X[idx, :]: scikit-learn indexes the first axis this way
+            if not idx or any(not (k is Ellipsis or (isinstance(k, slice) and k == slice(None))) for k in idx[1:]):
+                raise ValueError("a patch view is indexed along its first axis only")
+            idx = idx[0]
+        if isinstance(idx, slice):
+            idx = np.arange(len(self.ds))[idx]
+        return self.ds.subset(idx).X
+
+    def numpy(self, chunk=4096):
+        ds = self.ds
+        out = np.empty(self.shape, np.float32)
+        if len(ds):
+            order = ds.set_order(np.arange(len(ds)))
+            for i in range(0, len(ds), chunk):
+                k = min(chunk, len(ds) - i)
+                out[i:i + k] = ds.batch(order, i, k).cpu().numpy()
+        return out
+
+    def __repr__(self):
+        return f"<LabeledView {self.shape} float32 of {self.ds!r}>"
+
+
+def labeled_dataset(X):
+    """An image argument of FineTunedVGG16.fit / evaluate / predict -> the LabeledPatches it is a view of, or None for an array."""
+    return X.ds if isinstance(X, LabeledView) else None
+
+
+class LabeledPatches:
+    """The classifier's training patches with the class id of their frame, cut on demand from ONE device-resident frame stack: the device
+    form of load_defects_dataset_as_patches' (X, y).  All frames share one size (the reference's dataset is uniform: 478 x 478 crops); a
+    directory that mixes sizes raises ValueError naming the first file that differs.  `len(ds)` patches; `ds.X` stands in for the loader's X
+    and `ds.y` IS the loader's y (int64, host); `ds.subset(indices)` shares the stack; `ds.set_order(permutation)` uploads an epoch's order,
+    `ds.batch(order, offset, B)` cuts the plain patches (sr_gather_patch_pairs, one-sided) and `ds.warped_batch(order, offset, B, params)`
+    the augmented ones (sr_gather_warp_patches), each by one launch."""
+
+    def __init__(self, store, index=None):
+        self._s = store
+        self.index = None if index is None else _check_indices(index, len(store.table), "LabeledPatches index")
+        self.X = LabeledView(self)
+
+    # ---- constructors
+    @classmethod
+    def from_stacks(cls, frames, labels, patch_size, stride, swap_rb=False, ctx=None):
+        """frames [N,H,W,3]: a uint8 or fp32 [0,1] stack, NumPy (uploaded on first use) or a device tensor, channels in the order the
+        patches should have unless swap_rb; labels: one class id per frame."""
+        if len(frames.shape) != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+            raise ValueError("the frame stack must be [N,H,W,3] with N >= 1")
+        if str(frames.dtype).replace("torch.", "") not in ("uint8", "float32"):
+            raise ValueError("the frame stack must be uint8 or float32")
+        labels = np.asarray(labels)
+        if labels.ndim != 1 or len(labels) != frames.shape[0] or not (np.issubdtype(labels.dtype, np.integer) or labels.dtype == bool):
+            raise ValueError("labels: one integer class id per frame")
+        table = window_table_defects(int(frames.shape[0]), frames.shape[1:3], patch_size, stride)
+        return cls(_LabeledStore(frames, table, labels.astype(np.int64)[table[:, 0]], patch_size, swap_rb, ctx))
+
+    @classmethod
+    def from_dirs(cls, hr_root, patch_size=33, stride=14, class_map_path=None):
+        """The dataset load_defects_dataset_as_patches(...) returns for the same arguments: the same validation and messages, the same file
+        order, KeyError for a basename the class map lacks, PIL decode to uint8, one upload."""
+        from SRModels import loading_methods as LM
+        from PIL import Image
+        if not os.path.exists(hr_root):
+            raise ValueError("HR root directory must exist.")
+        if not os.path.isdir(hr_root):
+            raise ValueError("HR root path must be a directory.")
+        if not isinstance(patch_size, int) or patch_size <= 0:
+            raise ValueError("patch_size must be positive int.")
+        if not isinstance(stride, int) or stride <= 0:
+            raise ValueError("stride must be positive int.")
+        class_map = LM._load_class_map(class_map_path)
+        paths = LM.get_all_image_paths(hr_root)
+        if not paths:
+            raise ValueError("No images found under HR root directory.")
+        paths = sorted(paths, key=os.path.basename)
+        imgs, labels = [], []
+        for path in paths:
+            with Image.open(path) as im:
+                a = np.asarray(im.convert("RGB"), dtype=np.uint8)
+            base = os.path.basename(path)
+            if base not in class_map:
+                raise KeyError(f"Missing class id for image basename in class_labels_map: {base}")
+            if imgs and a.shape != imgs[0].shape:
+                raise ValueError(f"image {path} is {a.shape[0]} x {a.shape[1]}, the first ({paths[0]}) is {imgs[0].shape[0]} x "
+                                 f"{imgs[0].shape[1]}: a LabeledPatches needs one frame size")
+            imgs.append(a)
+            labels.append(int(class_map[base]))
+        return cls.from_stacks(np.stack(imgs), np.array(labels, np.int64), patch_size, stride)
+
+    @classmethod
+    def from_device(cls, frames_u8, labels, channel_order="bgr", patch_size=33, stride=14):
+        """Device crops (data.common_methods.square_crop_batch: uint8 [N,S,S,3], BGR) and their class ids as a dataset, without a PNG in
+        between.  channel_order "bgr" is swapped to the loader's RGB in the gather."""
+        if channel_order not in ("bgr", "rgb"):
+            raise ValueError("channel_order must be 'bgr' or 'rgb'")
+        return cls.from_stacks(frames_u8, labels, patch_size, stride, swap_rb=channel_order == "bgr")
+
+    # ---- the loader's surface
+    def __len__(self):
+        return len(self._s.table) if self.index is None else len(self.index)
+
+    def __repr__(self):
+        return f"LabeledPatches({len(self)} patches, patch={self._s.patch_size})"
+
+    patch_size = property(lambda self: self._s.patch_size)
+    frame_size = property(lambda self: (int(self._s.frames.shape[1]), int(self._s.frames.shape[2])))
+
+    @property
+    def y(self):
+        """int64 [len]: the class id of every patch's frame -- the loader's y."""
+        return self._s.labels.copy() if self.index is None else self._s.labels[self.index]
+
+    @property
+    def windows(self):
+        """int32 [len,3]: (image, y, x) of this dataset's patches."""
+        return self._s.table if self.index is None else self._s.table[self.index]
+
+    def rows(self, indices):
+        """Patch numbers of THIS dataset -> rows of the shared window table."""
+        idx = _check_indices(indices, len(self), "patch indices")
+        return idx if self.index is None else self.index[idx]
+
+    def subset(self, indices):
+        """The dataset of patches `indices` (in that order), sharing the stack and the table."""
+        return LabeledPatches(self._s, self.rows(indices))
+
+    def host_bytes(self):
+        """Bytes this dataset holds on the host: the window table, the labels, the subset's index, and the stack while it is not uploaded."""
+        s = self._s
+        return s.table.nbytes + s.labels.nbytes + (0 if self.index is None else self.index.nbytes) + (s.frames.nbytes if isinstance(s.frames, np.ndarray) else 0)
+
+    def device_bytes(self):
+        """Bytes this dataset holds (or, before its first batch, will hold) on the device: the stack and the window table."""
+        f = self._s.frames
+        return int(np.prod([int(v) for v in f.shape])) * (1 if str(f.dtype).replace("torch.", "") == "uint8" else 4) + self._s.table.nbytes
+
+    # ---- batches
+    def set_order(self, host_permutation):
+        """An order over this dataset's patches (an epoch's permutation), validated on the host -> int32 device tensor of table rows."""
+        s = self._s.on_device()
+        return s.ctx.to_device(self.rows(host_permutation).astype(np.int32))
+
+    def batch(self, order_dev, offset, B):
+        """Patches order_dev[offset : offset + B] (order_dev from set_order) -> fp32 device [B,p,p,3], the loader's values."""
+        s = self._s.on_device()
+        return s.ctx.gather_patch_pairs(dict(stack=s.frames, swap=s.swap), None, s.table_dev, order_dev, offset, B, s.patch_size)[0]
+
+    def warped_batch(self, order_dev, offset, B, params):
+        """The same patches through the augmentation warp (params fp32 [B,16]: Context.warp_params) -> fp32 device [B,p,p,3]: bit for bit
+        ctx.affine_warp of the loader's array at those patches, without the array."""
+        s = self._s.on_device()
+        return s.ctx.gather_warp_patches(s.frames, s.table_dev, order_dev, offset, B, s.patch_size, params, swap=s.swap)
 
 
 def _resized_unit(ctx, lr_u8, H, W, codes, swap):

@@ -886,6 +886,40 @@ class Context:
                                                   order.data_ptr(), order.numel(), offset, B, ph, pw, scale, self.stream()))
         return X, Y
 
+    def gather_warp_patches(self, stack, windows, order, offset, B, patch, params, swap=False, out=None):
+        """One augmented batch of the classifier's fit cut from a device-resident frame stack by one launch (sr_gather_warp_patches): stack
+        [N,H,W,3] uint8 or fp32, windows int32 device [n,3] (image, y, x), order int32 device [m] rows of windows, params fp32 [B,16]
+        (warp_params; a device tensor or a host array) -> fp32 [B,h,w,3]: element b is affine_warp of the patch gather_patch_pairs cuts for
+        window order[offset + b], bit for bit, with every tap clamped to the patch.  patch: int or (h, w).  The tables' CONTENTS are the
+        caller's to validate before upload (sr355.patches does); the kernel clamps what it reads."""
+        ph, pw = (int(patch), int(patch)) if isinstance(patch, (int, np.integer)) else (int(patch[0]), int(patch[1]))
+        offset, B = int(offset), int(B)
+        _check_tensor(self, stack, "gather_warp_patches stack", (torch.float32, torch.uint8))
+        if stack.dim() != 4 or stack.shape[3] != 3 or stack.shape[0] < 1:
+            raise ValueError("gather_warp_patches: the stack must be [N,H,W,3]")
+        N, H, W, _ = (int(v) for v in stack.shape)
+        _check_tensor(self, windows, "gather_warp_patches windows", (torch.int32,))
+        _check_tensor(self, order, "gather_warp_patches order", (torch.int32,))
+        if windows.dim() != 2 or windows.shape[1] != 3 or windows.shape[0] < 1 or order.dim() != 1:
+            raise ValueError("gather_warp_patches: windows must be int32 [n,3] and order int32 [m]")
+        if B < 1 or offset < 0 or offset + B > order.numel():
+            raise ValueError(f"gather_warp_patches: batch [{offset}, {offset + B}) reaches outside an order of {order.numel()} entries")
+        if ph < 1 or pw < 1 or ph > H or pw > W:
+            raise ValueError(f"gather_warp_patches: a {ph} x {pw} patch does not fit a {H} x {W} frame")
+        if not isinstance(params, torch.Tensor):
+            params = self.to_device(np.asarray(params, np.float32))
+        _check_tensor(self, params, "gather_warp_patches params")
+        if tuple(params.shape) != (B, 16):
+            raise ValueError(f"gather_warp_patches: params [{B},16] expected, got {tuple(params.shape)}")
+        y = self.empty((B, ph, pw, 3)) if out is None else out
+        _check_tensor(self, y, "gather_warp_patches out")
+        if tuple(y.shape) != (B, ph, pw, 3):
+            raise ValueError("gather_warp_patches: out has the wrong shape")
+        self.check(self.lib.sr_gather_warp_patches(self.h, stack.data_ptr(), dtype_code(stack.dtype), N, H, W, windows.data_ptr(), int(windows.shape[0]),
+                                                   order.data_ptr(), order.numel(), offset, B, ph, pw, int(bool(swap)), params.data_ptr(), y.data_ptr(),
+                                                   self.stream()))
+        return y
+
     def u8_to_unit(self, stack, swap=False):
         """uint8 [N,H,W,3] device stack -> fp32 [N,H,W,3] in [0,1], float(u) / 255.0f per element: sr_gather_patch_pairs with one whole-image
         window per image."""
