@@ -343,6 +343,30 @@ int  sr_classic_scores(sr_ctx* ctx, const void* hr, int hr_dtype, const void* sr
                        const double* data_range_f64, double hf_radius_frac, double* scores_f64, float* gray_f32, float* sobel_f32,
                        int* hist_luma_i32, int* hist_color_i32, void* stream);
 
+/* ---- the classical study's loop glue (super_resolucion_clasica.ipynb cell 8) and its SSIM similarity maps (visualization_methods.py:
+ *      553-591), B images of one shape, csrc/metrics.hip.  Asynchronous on `stream`; on a refusal (negative code, sr_last_error) nothing
+ *      is written ----
+ * sr_rgb2gray_u8: cv2.cvtColor(x, COLOR_RGB2GRAY) as the notebook calls it on uint8 images (cell 8; visualization_methods.py:554-555):
+ *   x_u8 DEVICE [B,H,W,3] -> y_u8 DEVICE [B,H,W], (4899 R + 9617 G + 1868 B + 8192) >> 14, the device function sr_classic_scores' gray
+ *   columns use.  Any H, W and any pointer alignment (a tensor that is not 4-byte aligned takes a byte path).
+ * sr_freq_to_u8: cell 8's normalisation of frequency_extrapolation's output, `(f / np.max(f) * 255.0).astype(np.uint8) if np.max(f) > 0
+ *   else f.astype(np.uint8)`: f_f64 DEVICE [B,H,W] (what sr_freq_extrapolate writes) -> y_u8 DEVICE [B,H,W] and max_f64 DEVICE [B], each
+ *   image's maximum (a fixed-order reduction; a NaN, once met, is the maximum, as for np.max).  The quotient and then the product are
+ *   rounded fp64 operations in that order (no reciprocal, no fused multiply-add) and the result is truncated toward zero: bit for bit
+ *   NumPy's expression.  B <= 65535, H W <= 2^28.
+ * sr_ssim_map: skimage.metrics.structural_similarity(a, b, data_range=..., full=True) with its defaults (visualization_methods.py:578-579):
+ *   a, b DEVICE [B,H,W,C], C 1 or 3, each SR_DTYPE_U8 or SR_DTYPE_F32 (mixed pairs allowed); data_range_f64 DEVICE [B]; H, W >= 7,
+ *   B <= 65535.  map_f64 DEVICE [B,H,W,C] receives S over the WHOLE image: fp64, 7 x 7 uniform window, K1 0.01, K2 0.03, covariances x
+ *   49/48, the window means at the border as scipy.ndimage.uniform_filter's default mode='reflect' takes them (d c b a | a b c d: the
+ *   edge pixel repeated, NumPy's 'symmetric' -- not the BORDER_REFLECT_101 of this library's Sobel and resize code).  mean_f64 DEVICE [B]
+ *   receives mssim: the mean of S over the centres 3 pixels inside the border, for C = 3 the mean of the per-channel means -- the sums
+ *   sr_classic_scores' ssim column is made of.  Every reduction runs in a fixed order: a pair's outputs are bitwise the same on every run
+ *   and for any B. */
+int  sr_rgb2gray_u8(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, uint8_t* y_u8, void* stream);
+int  sr_freq_to_u8(sr_ctx* ctx, const double* f_f64, int B, int H, int W, uint8_t* y_u8, double* max_f64, void* stream);
+int  sr_ssim_map(sr_ctx* ctx, const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int C,
+                 const double* data_range_f64, double* map_f64, double* mean_f64, void* stream);
+
 /* ---- the dataset EDA's per-pair image statistics and global accumulators (reference data/EDA.ipynb: ImageDatasetAnalyzer, cell
  * 87582ba8; MetricsAggregator.collect, cell eb5cc926), csrc/eda.hip.  B aligned pairs of one shape, lr_u8 and hr_u8 DEVICE uint8
  * [B,H,W,3] in BGR order (lr already resized to hr's size); 7 <= H, W <= 4096, H W <= 2^22, B <= 32767 (anything else: SR_ERR_INVALID).

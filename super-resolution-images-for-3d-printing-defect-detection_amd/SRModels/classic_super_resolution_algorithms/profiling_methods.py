@@ -170,15 +170,24 @@ def peak_signal_noise_ratio(image_true, image_test, *, data_range=None, **kwargs
     return _score(image_true, image_test, "psnr", _skimage_range(image_true, data_range, "peak_signal_noise_ratio"))
 
 
-def structural_similarity(im1, im2, *, data_range=None, channel_axis=None, **kwargs):
+def structural_similarity(im1, im2, *, data_range=None, channel_axis=None, full=False, **kwargs):
     """skimage.metrics.structural_similarity with its default window (7 x 7 uniform, sample covariance, K1 0.01, K2 0.03): 2-D images,
-    or [H, W, 3] with channel_axis 2 / -1 (the mean of the per-channel means)."""
+    or [H, W, 3] with channel_axis 2 / -1 (the mean of the per-channel means).  full=True -> (mssim, S) as skimage returns them: S the
+    float64 similarity map of the images' shape, the window means at the border by scipy's 'reflect' rule (sr_ssim_map)."""
     if kwargs:
         raise NotImplementedError(f"structural_similarity: {sorted(kwargs)} not supported (default window only)")
     nd = np.ndim(im1)
     if not ((channel_axis is None and nd == 2) or (channel_axis in (2, -1) and nd == 3)):
         raise NotImplementedError("structural_similarity: 2-D images, or [H, W, 3] with channel_axis=2")
-    return _score(im1, im2, "ssim", _skimage_range(im1, data_range, "structural_similarity"))
+    dr = _skimage_range(im1, data_range, "structural_similarity")
+    if not full:
+        return _score(im1, im2, "ssim", dr)
+    a, b = _image(im1, "ssim"), _image(im2, "ssim")
+    if a.shape != b.shape:
+        raise ValueError(f"ssim: images of shapes {a.shape} and {b.shape}")
+    ctx = _context()
+    smap, mean = ctx.ssim_map(ctx.to_device(a[None]), ctx.to_device(b[None]), dr)
+    return float(mean[0]), smap[0].cpu().numpy()
 
 
 # ------------------------------------------------------------------ statistics, bootstrap and ranking (host)

@@ -16,6 +16,9 @@
 //      epilogue, one partial per workgroup), in chunks of images that bound the intermediates.
 //   4. finalize: one workgroup per pair sums the per-tile partials in a fixed order and applies the logs and divisions.
 // No float atomics anywhere: a pair's scores are the same bits on every run and do not depend on B or on the other pairs.
+//
+//   5. (below the scores) the study's loop glue and similarity maps, entry points of their own: sr_rgb2gray_u8, sr_freq_to_u8 and
+//      sr_ssim_map, the pair-statistics pass's SSIM part over the whole image with scipy's 'reflect' border.
 #include "cgemm_f64.h"
 #include "common.h"
 
@@ -50,12 +53,15 @@ __device__ inline float ld_val(const void* p, int dt, int64_t i) {
     return dt == SR_DTYPE_U8 ? (float)static_cast<const uint8_t*>(p)[i] : static_cast<const float*>(p)[i];
 }
 
+// OpenCV's 8-bit COLOR_RGB2GRAY of one interleaved RGB pixel: common.h's fixed-point statement with the channels in RGB order.  The one
+// gray conversion of this file: the scores' gray-derived columns and sr_rgb2gray_u8 both go through it.
+__device__ inline int gray_rgb_u8(const uint8_t* q) { return gray_bgr((int)q[2], (int)q[1], (int)q[0]); }
+
 // the gray value the gray-derived columns see at pixel `pix` of one image, unscaled: the value itself for one channel; for uint8 RGB
 // OpenCV's COLOR_RGB2GRAY fixed point (14-bit coefficients, rounded).  Float RGB never reaches here (gray_ok is false).
 __device__ inline float gray_val(const void* img, int dt, int C, int64_t pix) {
     if (C == 1) return ld_val(img, dt, pix);
-    const uint8_t* q = static_cast<const uint8_t*>(img) + pix * 3;
-    return (float)((4899 * (int)q[0] + 9617 * (int)q[1] + 1868 * (int)q[2] + 8192) >> 14);
+    return (float)gray_rgb_u8(static_cast<const uint8_t*>(img) + pix * 3);
 }
 
 // what np.histogram(range=(0, 255)) bins: uint8 as float32, float as clip(x, 0, 1) * 255 in float32
@@ -314,9 +320,237 @@ __global__ void __launch_bounds__(256) scores_finalize_kernel(const double* part
     o[SR_SCORE_KL_COLOR] = C == 3 ? kl_c / 3.0 : nan;
 }
 
+// ------------------------------------------------------------------------------------------------
+// 5. the classical study's loop glue (super_resolucion_clasica.ipynb cell 8) and the SSIM similarity maps (visualization_methods.py:553-591)
+// ------------------------------------------------------------------------------------------------
+// cv2.cvtColor(x, COLOR_RGB2GRAY) on B uint8 images, taken as one run of npix interleaved pixels: a thread converts four pixels.  VEC: both
+// pointers are 4-byte aligned, so the twelve input bytes are three dword loads and the four gray bytes one dword store; a row length
+// plays no part (the images are dense), and a misaligned tensor takes the byte path.
+template <bool VEC>
+__global__ void __launch_bounds__(256) rgb2gray_kernel(const uint8_t* x, uint8_t* y, int64_t npix) {
+    const int64_t ngroups = (npix + 3) / 4;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ngroups; i += (int64_t)gridDim.x * 256) {
+        const int64_t p = i * 4;
+        if (VEC && p + 4 <= npix) {
+            const uint32_t* q = reinterpret_cast<const uint32_t*>(x + p * 3);
+            const uint32_t w[3] = {q[0], q[1], q[2]};
+            uint8_t px[12];
+            for (int k = 0; k < 12; ++k) px[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+            uint32_t o = 0;
+            for (int k = 0; k < 4; ++k) o |= (uint32_t)gray_rgb_u8(px + 3 * k) << (8 * k);
+            *reinterpret_cast<uint32_t*>(y + p) = o;
+        } else {
+            for (int k = 0; k < 4 && p + k < npix; ++k) y[p + k] = (uint8_t)gray_rgb_u8(x + (p + k) * 3);
+        }
+    }
+}
+
+// np.max's answer for two values: the larger one, a NaN once met stays
+__device__ inline double max_nan(double m, double v) { return (v > m || v != v) ? v : m; }
+
+__device__ double block_max(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = max_nan(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+constexpr int FQ_PER_WG = 256 * 16;   // elements of one image a workgroup of the two freq_to_u8 kernels covers
+
+// pmax[b * nchunk + chunk] = max over the chunk's elements of image b; grid (nchunk, B)
+__global__ void __launch_bounds__(256) freq_chunk_max_kernel(const double* f, int64_t per, double* pmax) {
+    __shared__ double red[256];
+    const double* img = f + (int64_t)blockIdx.y * per;
+    const int64_t i0 = (int64_t)blockIdx.x * FQ_PER_WG, e = min(i0 + FQ_PER_WG, per);
+    double m = img[i0];                                                // i0 < per: the grid has ceil(per / FQ_PER_WG) chunks
+    for (int64_t i = i0 + threadIdx.x; i < e; i += 256) m = max_nan(m, img[i]);
+    m = block_max(m, red);
+    if (threadIdx.x == 0) pmax[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = m;
+}
+
+// cell 8's `(f / np.max(f) * 255.0).astype(np.uint8) if np.max(f) > 0 else f.astype(np.uint8)`: every workgroup folds the image's chunk
+// maxima in one fixed order, then divides and multiplies in fp64 (correctly rounded, in that order) and truncates toward zero
+__global__ void __launch_bounds__(256) freq_to_u8_kernel(const double* f, int64_t per, const double* pmax, uint8_t* y, double* mx_out) {
+    __shared__ double red[256];
+    const int b = blockIdx.y, nchunk = gridDim.x;
+    double m = pmax[(int64_t)b * nchunk];
+    for (int t = threadIdx.x; t < nchunk; t += 256) m = max_nan(m, pmax[(int64_t)b * nchunk + t]);
+    const double mx = block_max(m, red);
+    if (blockIdx.x == 0 && threadIdx.x == 0) mx_out[b] = mx;
+    const bool scale = mx > 0.0;
+    const double* img = f + (int64_t)b * per;
+    uint8_t* out = y + (int64_t)b * per;
+    for (int64_t i = (int64_t)blockIdx.x * FQ_PER_WG + threadIdx.x, e = min((int64_t)(blockIdx.x + 1) * FQ_PER_WG, per); i < e; i += 256) {
+        const double v = img[i];
+        out[i] = (uint8_t)(long long)(scale ? __dmul_rn(__ddiv_rn(v, mx), 255.0) : v);
+    }
+}
+
+// scipy.ndimage.uniform_filter's default mode='reflect' (d c b a | a b c d, NumPy's 'symmetric'): the edge pixel is repeated.  One
+// reflection reaches every coordinate the 7 x 7 window asks for (-3 .. n + 2) because n >= 7.
+__device__ inline int refl_sym(int i, int n) {
+    if (i < 0) return -1 - i;
+    if (i >= n) return 2 * n - 1 - i;
+    return i;
+}
+
+constexpr int SPART = 3;   // per-tile partials of ssim_map_kernel: sum of S over the tile's cropped centres, per channel
+
+// skimage's S over the WHOLE image and the per-tile sums behind mssim.  The tile, LDS layout, window loops and the order of every sum are
+// pair_stats_kernel's, so the interior of the map and the mean are the numbers the ssim score is made of; the halo is resolved by
+// refl_sym at load instead of being left out.  map [B,H,W,C]; part[(b * ntiles + tile) * SPART + c].
+template <bool INT>
+__global__ void __launch_bounds__(256) ssim_map_kernel(const void* a, int a_dt, const void* bimg, int b_dt, int H, int W, int C, const double* dr,
+                                                       double* map, double* part) {
+    using S = typename std::conditional<INT, int, float>::type;
+    __shared__ S raw[2][3][MR * MR];
+    __shared__ double red[256];
+    const int b = blockIdx.z;
+    const int y0 = blockIdx.y * MT, x0 = blockIdx.x * MT;
+    const int tid = threadIdx.x;
+    const int64_t HW = (int64_t)H * W;
+    int dts[2];
+    const void* img[2] = {image_of(a, a_dt, bimg, b_dt, 2 * b, HW * C, &dts[0]), image_of(a, a_dt, bimg, b_dt, 2 * b + 1, HW * C, &dts[1])};
+    for (int i = tid; i < MR * MR * C; i += 256) {
+        const int p = i / C, c = i - p * C;
+        const int r = p / MR, cc = p - r * MR;
+        const int y = y0 - MHW + r, x = x0 - MHW + cc;
+        const bool used = y < H + MHW && x < W + MHW;                   // beyond the reach of the image's last row / column: never read
+        const int64_t o = ((int64_t)refl_sym(y, H) * W + refl_sym(x, W)) * C + c;
+        for (int k = 0; k < 2; ++k) raw[k][c][p] = used ? (S)ld_val(img[k], dts[k], o) : (S)0;
+    }
+    __syncthreads();
+
+    const double R = dr[b];
+    const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
+    const double cov_norm = 49.0 / 48.0;
+    double acc[SPART] = {0, 0, 0};
+    for (int q = 0; q < 4; ++q) {
+        const int p = tid + 256 * q, r = p >> 5, cc = p & 31;
+        const int y = y0 + r, x = x0 + cc;
+        if (y >= H || x >= W) continue;
+        const bool centre = y >= MHW && y < H - MHW && x >= MHW && x < W - MHW;
+        for (int c = 0; c < C; ++c) {
+            double ux, uy, uxx, uyy, uxy;
+            if (INT) {
+                int sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;
+                for (int i = 0; i < 7; ++i)
+                    for (int j = 0; j < 7; ++j) {
+                        const int u = raw[0][c][(r + i) * MR + cc + j], v = raw[1][c][(r + i) * MR + cc + j];
+                        sa += u; sb += v; saa += u * u; sbb += v * v; sab += u * v;
+                    }
+                ux = sa / 49.0; uy = sb / 49.0; uxx = saa / 49.0; uyy = sbb / 49.0; uxy = sab / 49.0;
+            } else {
+                double sa = 0, sb = 0, saa = 0, sbb = 0, sab = 0;
+                for (int i = 0; i < 7; ++i)
+                    for (int j = 0; j < 7; ++j) {
+                        const double u = raw[0][c][(r + i) * MR + cc + j], v = raw[1][c][(r + i) * MR + cc + j];
+                        sa += u; sb += v; saa += u * u; sbb += v * v; sab += u * v;
+                    }
+                ux = sa / 49.0; uy = sb / 49.0; uxx = saa / 49.0; uyy = sbb / 49.0; uxy = sab / 49.0;
+            }
+            const double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
+            const double A1 = 2.0 * ux * uy + C1, A2 = 2.0 * vxy + C2, B1 = ux * ux + uy * uy + C1, B2 = vx + vy + C2;
+            const double s = (A1 * A2) / (B1 * B2);
+            map[(((int64_t)b * H + y) * W + x) * C + c] = s;
+            if (centre) acc[c] += s;
+        }
+    }
+    const int64_t tile = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    double* out = part + ((int64_t)b * gridDim.x * gridDim.y + tile) * SPART;
+    for (int k = 0; k < SPART; ++k) {
+        const double s = block_sum(acc[k], red);
+        if (tid == 0) out[k] = s;
+    }
+}
+
+// mssim: the tiles' sums in one fixed order, then scores_finalize_kernel's expression; one workgroup per pair
+__global__ void __launch_bounds__(256) ssim_mean_kernel(const double* part, int ntiles, int H, int W, int C, double* mean) {
+    __shared__ double red[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double s[SPART];
+    for (int k = 0; k < SPART; ++k) {
+        double v = 0.0;
+        for (int t = tid; t < ntiles; t += 256) v += part[((int64_t)b * ntiles + t) * SPART + k];
+        s[k] = block_sum(v, red);
+    }
+    if (tid != 0) return;
+    const double ncen = (double)(H - 2 * MHW) * (double)(W - 2 * MHW);
+    mean[b] = C == 1 ? s[0] / ncen : ((s[0] / ncen + s[1] / ncen) + s[2] / ncen) / 3.0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sr_rgb2gray_u8(sr_ctx* ctx, const uint8_t* x_u8, int B, int H, int W, uint8_t* y_u8, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!x_u8 || !y_u8) return ctx->fail(SR_ERR_INVALID, "rgb2gray_u8: null tensor");
+    if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W >= ((int64_t)1 << 40)) return ctx->fail(SR_ERR_INVALID, "rgb2gray_u8: empty or oversized batch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t npix = (int64_t)B * H * W;
+    const bool vec = ((reinterpret_cast<uintptr_t>(x_u8) | reinterpret_cast<uintptr_t>(y_u8)) & 3) == 0;
+    const int rec = ctx->prof_open("rgb2gray_u8", 0.0, (double)npix * 4.0, st);
+    if (vec)
+        hipLaunchKernelGGL(rgb2gray_kernel<true>, dim3(met_grid((npix + 3) / 4)), dim3(256), 0, st, x_u8, y_u8, npix);
+    else
+        hipLaunchKernelGGL(rgb2gray_kernel<false>, dim3(met_grid((npix + 3) / 4)), dim3(256), 0, st, x_u8, y_u8, npix);
+    ctx->prof_close(rec, st);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+int sr_freq_to_u8(sr_ctx* ctx, const double* f_f64, int B, int H, int W, uint8_t* y_u8, double* max_f64, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!f_f64 || !y_u8 || !max_f64) return ctx->fail(SR_ERR_INVALID, "freq_to_u8: null tensor");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (int64_t)B * H * W >= ((int64_t)1 << 40)) return ctx->fail(SR_ERR_INVALID, "freq_to_u8: empty or oversized batch (1 <= B <= 65535)");
+    const int64_t per = (int64_t)H * W;
+    if (per > (int64_t)FQ_PER_WG * 65535) return ctx->fail(SR_ERR_INVALID, "freq_to_u8: images above 2^28 pixels are not supported");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned nchunk = (unsigned)((per + FQ_PER_WG - 1) / FQ_PER_WG);
+    double* pmax = static_cast<double*>(ctx->arena(ctx->met_work, sizeof(double) * (size_t)B * nchunk, st));
+    if (!pmax) return SR_ERR_OOM;
+    const int rec = ctx->prof_open("freq_to_u8", 0.0, (double)B * per * (8.0 + 8.0 + 1.0), st);      // f read by both kernels, y written once
+    hipLaunchKernelGGL(freq_chunk_max_kernel, dim3(nchunk, B), dim3(256), 0, st, f_f64, per, pmax);
+    hipLaunchKernelGGL(freq_to_u8_kernel, dim3(nchunk, B), dim3(256), 0, st, f_f64, per, pmax, y_u8, max_f64);
+    ctx->prof_close(rec, st);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+int sr_ssim_map(sr_ctx* ctx, const void* a, int a_dtype, const void* b, int b_dtype, int B, int H, int W, int C, const double* data_range_f64,
+                double* map_f64, double* mean_f64, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!a || !b || !data_range_f64 || !map_f64 || !mean_f64) return ctx->fail(SR_ERR_INVALID, "ssim_map: null tensor");
+    if ((a_dtype != SR_DTYPE_U8 && a_dtype != SR_DTYPE_F32) || (b_dtype != SR_DTYPE_U8 && b_dtype != SR_DTYPE_F32))
+        return ctx->fail(SR_ERR_INVALID, "ssim_map: images must be uint8 or float32");
+    if (C != 1 && C != 3) return ctx->fail(SR_ERR_INVALID, "ssim_map: C must be 1 (gray) or 3 (RGB)");
+    if (B < 1 || B > 65535 || (int64_t)B * H * W * C >= ((int64_t)1 << 40)) return ctx->fail(SR_ERR_INVALID, "ssim_map: empty or oversized batch (1 <= B <= 65535)");
+    if (H < 7 || W < 7) return ctx->fail(SR_ERR_INVALID, "ssim_map: H and W must be at least 7 (the SSIM window)");
+    if ((int64_t)H * W > (int64_t)65535 * 4096) return ctx->fail(SR_ERR_INVALID, "ssim_map: images above 2^28 pixels are not supported");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 tgrid((W + MT - 1) / MT, (H + MT - 1) / MT, B);
+    const int ntiles = (int)(tgrid.x * tgrid.y);
+    double* part = static_cast<double*>(ctx->arena(ctx->met_work, sizeof(double) * (size_t)B * ntiles * SPART, st));
+    if (!part) return SR_ERR_OOM;
+    const int rec = ctx->prof_open("ssim_map", 0.0, (double)B * H * W * C * ((a_dtype == SR_DTYPE_U8 ? 1 : 4) + (b_dtype == SR_DTYPE_U8 ? 1 : 4) + 8.0), st);
+    if (a_dtype == SR_DTYPE_U8 && b_dtype == SR_DTYPE_U8)
+        hipLaunchKernelGGL(ssim_map_kernel<true>, tgrid, dim3(256), 0, st, a, a_dtype, b, b_dtype, H, W, C, data_range_f64, map_f64, part);
+    else
+        hipLaunchKernelGGL(ssim_map_kernel<false>, tgrid, dim3(256), 0, st, a, a_dtype, b, b_dtype, H, W, C, data_range_f64, map_f64, part);
+    hipLaunchKernelGGL(ssim_mean_kernel, dim3(B), dim3(256), 0, st, part, ntiles, H, W, C, mean_f64);
+    ctx->prof_close(rec, st);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
 
 int sr_classic_scores(sr_ctx* ctx, const void* hr, int hr_dtype, const void* sr, int sr_dtype, int B, int H, int W, int C, const double* data_range_f64,
                       double hf_radius_frac, double* scores_f64, float* gray_f32, float* sobel_f32, int* hist_luma_i32, int* hist_color_i32, void* stream) {

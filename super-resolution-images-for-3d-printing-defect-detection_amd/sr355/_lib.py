@@ -119,6 +119,9 @@ SIGNATURES = {
     "sr_edge_guided": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
     "sr_freq_extrapolate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "sr_classic_scores": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_rgb2gray_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sr_freq_to_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_ssim_map": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sr_eda_pair_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_eda_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_degrade_gauss": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -295,21 +295,31 @@ class Context:
         self.check(self.lib.sr_noise_sigma(self.h, x.data_ptr(), B, h, w, sigma.data_ptr(), self.stream()))
         return sigma
 
-    def non_local_means(self, lr, H, W, patch_size=5, patch_distance=6, h_scale=1.15, raw=False):
+    @staticmethod
+    def nlm_sigma_error(indices):
+        """The ValueError non_local_means raises for the images whose noise estimate is zero or not finite."""
+        return ValueError(f"non_local_means: the noise estimate of image(s) {[int(i) for i in indices]} is zero or not finite "
+                          "(an image without detail); the reference would divide by zero")
+
+    def non_local_means(self, lr, H, W, patch_size=5, patch_distance=6, h_scale=1.15, raw=False, check=True):
         """non_local_means (classic_algorithms.py:45-62) on lr [B,h,w] uint8: sigma, fast NL-means with h = h_scale * sigma, then
         INTER_LANCZOS4 to (H, W) -> float32 [B,H,W]; raw=True -> (that, the denoised [B,h,w], sigma [B]).  A sigma that is zero or not
-        finite (an image without detail: the reference divides by zero there) raises ValueError -- checking it waits for the device."""
+        finite (an image without detail: the reference divides by zero there) raises ValueError -- checking it waits for the device.
+        check=False does not wait: the result is followed by the device flag tensor, bool [B], true for such an image (its output is
+        then not a number), and the caller raises nlm_sigma_error once it has read the flags."""
         B, h, w = self._gray_batch(lr, "non_local_means input")
         sigma = self.noise_sigma(lr)
         bad = ~torch.isfinite(sigma) | (sigma <= 0)
-        if bool(bad.any()):
-            raise ValueError(f"non_local_means: the noise estimate of image(s) {torch.nonzero(bad).flatten().tolist()} is zero or not finite "
-                             "(an image without detail); the reference would divide by zero")
+        if check and bool(bad.any()):
+            raise self.nlm_sigma_error(torch.nonzero(bad).flatten().tolist())
         den = self.empty((B, h, w), torch.float32)
         self.check(self.lib.sr_nl_means(self.h, lr.data_ptr(), B, h, w, int(patch_size), int(patch_distance), sigma.data_ptr(), float(h_scale),
                                         den.data_ptr(), self.stream()))
         up = self.resize(den.unsqueeze(-1), int(H), int(W), "INTER_LANCZOS4").squeeze(-1)
-        return (up, den, sigma) if raw else up
+        out = (up, den, sigma) if raw else (up,)
+        if not check:
+            return out + (bad,)
+        return out if raw else up
 
     def edge_guided(self, x, H, W, weight=0.3, raw=False):
         """edge_guided_interpolation (sr_edge_guided) on x [B,h,w] uint8 -> uint8 [B,H,W]; raw=True -> (that, the float32 up-sized edges)."""
@@ -376,6 +386,48 @@ class Context:
                                               dr.data_ptr(), float(hf_radius_frac), out.data_ptr(), ptr("gray"), ptr("sobel"),
                                               ptr("hist_luma"), ptr("hist_color"), self.stream()))
         return (out, inter) if raw else out
+
+    # ------------------------------------------------------------------ the classical study's loop glue and SSIM maps (notebook cell 8; visualization_methods.py:553-591)
+    def rgb2gray(self, x):
+        """cv2.cvtColor(x, COLOR_RGB2GRAY) on a uint8 [B,H,W,3] device batch -> uint8 [B,H,W] on the device (sr_rgb2gray_u8)."""
+        _check_tensor(self, x, "rgb2gray input", (torch.uint8,))
+        if x.dim() != 4 or x.shape[3] != 3 or x.numel() == 0:
+            raise ValueError(f"rgb2gray: expected a non-empty [B,H,W,3] uint8 batch, got shape {tuple(x.shape)}")
+        B, H, W, _ = x.shape
+        y = self.empty((B, H, W), torch.uint8)
+        self.check(self.lib.sr_rgb2gray_u8(self.h, x.data_ptr(), B, H, W, y.data_ptr(), self.stream()))
+        return y
+
+    def freq_to_u8(self, f):
+        """The notebook's normalisation of frequency_extrapolation's output, (f / max(f) * 255.0) truncated to uint8 where max(f) > 0 and
+        f truncated otherwise, per image: f float64 [B,H,W] on the device -> (uint8 [B,H,W], the maxima float64 [B]) (sr_freq_to_u8)."""
+        _check_tensor(self, f, "freq_to_u8 input", (torch.float64,))
+        if f.dim() != 3 or f.numel() == 0:
+            raise ValueError(f"freq_to_u8: expected a non-empty [B,H,W] float64 batch, got shape {tuple(f.shape)}")
+        B, H, W = f.shape
+        y = self.empty((B, H, W), torch.uint8)
+        mx = self.empty((B,), torch.float64)
+        self.check(self.lib.sr_freq_to_u8(self.h, f.data_ptr(), B, H, W, y.data_ptr(), mx.data_ptr(), self.stream()))
+        return y, mx
+
+    def ssim_map(self, a, b, data_range=255.0):
+        """skimage's structural_similarity(a, b, data_range=..., full=True) for each pair (sr_ssim_map): a, b [B,H,W] or [B,H,W,C] (C 1 or 3)
+        device tensors, each uint8 or float32; data_range as classic_scores takes it -> (S float64 of a's shape, over the whole image with
+        scipy's 'reflect' border, and mssim float64 [B]), both on the device."""
+        _check_tensor(self, a, "ssim_map a", (torch.uint8, torch.float32))
+        _check_tensor(self, b, "ssim_map b", (torch.uint8, torch.float32))
+        if a.shape != b.shape or a.dim() not in (3, 4) or (a.dim() == 4 and a.shape[3] not in (1, 3)) or a.shape[0] < 1:
+            raise ValueError(f"ssim_map: expected two [B,H,W] or [B,H,W,C] (C 1 or 3) batches of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        B, H, W = a.shape[:3]
+        Cx = a.shape[3] if a.dim() == 4 else 1
+        if H < 7 or W < 7:
+            raise ValueError(f"ssim_map: images of {H} x {W} are smaller than the 7 x 7 SSIM window")
+        dr = self._score_data_range(a, data_range)
+        smap = self.empty(tuple(a.shape), torch.float64)
+        mean = self.empty((B,), torch.float64)
+        self.check(self.lib.sr_ssim_map(self.h, a.data_ptr(), dtype_code(a.dtype), b.data_ptr(), dtype_code(b.dtype), B, H, W, Cx, dr.data_ptr(),
+                                        smap.data_ptr(), mean.data_ptr(), self.stream()))
+        return smap, mean
 
     EDA_STAT_NAMES = L.EDA_STAT_NAMES
 
