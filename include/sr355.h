@@ -423,6 +423,26 @@ int  sr_eda_pair_stats(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, 
                        uint8_t* edges_u8, int* glcm_i32, double* dct_f64, void* stream);
 int  sr_eda_accumulate(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, double* fft_lr_sum_f64,
                        double* fft_hr_sum_f64, double* grad_hr_sum_f64, double* glcm_sum_f64, int64_t* sat_counts_i64, void* stream);
+/* sr_eda_pair_panels: the maps of the EDA's per-pair panels (cell 769cc582: create_advanced_visualizations, save_visual_example), one pair
+ *   after the other and unsummed; same pairs, limits and 8-bit contract as above.  Every output is optional (NULL: not computed; the two DFT
+ *   products are skipped when both spectra are NULL):
+ *   spec_lr_f64, spec_hr_f64 [B,H,W]   |fftshift(fft2(gray))| of lr / hr: the magnitude, not its log -- the panel's np.log(mag + 1e-8) is
+ *                                      the host's to take, on these bits;
+ *   grad_hr_f64 [B,H,W]                hypot of hr gray's ksize-5 Sobel pair;
+ *   glcm_lr_f64 [B,256,256]            lr gray's 256-level, angle-0, symmetric normed matrix (C + C^T) / T, T = 2 H (W - 1);
+ *   noise_lr_f64 [B,H,W]               np.mean(|lr - blur5(lr)|, axis=2): the exact integer sum of the three channels divided by 3.0 once;
+ *   diff_u8 [B,H,W]                    cvtColor(absdiff(lr, hr), BGR2GRAY), the 14-bit gray above of the per-channel |lr - hr|
+ *                                      (convertScaleAbs of a uint8 image and cv2.resize to the same size are the identity);
+ *   sat_hist_i64 [B,2,256]             counts of S per value, lr then hr;
+ *   scalars_f64 [B,SR_NUM_EDA_PANEL_SCALARS]   graycoprops(glcm_lr, contrast)[0,0] and mean(noise_lr).
+ *   For one pair spec_*, grad_hr and glcm_lr are the bits sr_eda_accumulate adds into zeroed buffers (the same kernels, storing), sat_hist
+ *   folded by s * 25 / 128 is its sat_counts, and the scalars are the bits of sr_eda_pair_stats(256 levels, angle_mask 1)'s glcm_contrast and
+ *   color_noise_lr.  Integer sums and fixed orders only: a pair's outputs are bitwise the same on every run, for any B and at any
+ *   position in the batch. */
+enum { SR_EDA_PANEL_GLCM_CONTRAST = 0, SR_EDA_PANEL_NOISE_MEAN, SR_NUM_EDA_PANEL_SCALARS };
+int  sr_eda_pair_panels(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, double* spec_lr_f64, double* spec_hr_f64,
+                        double* grad_hr_f64, double* glcm_lr_f64, double* noise_lr_f64, uint8_t* diff_u8, int64_t* sat_hist_i64,
+                        double* scalars_f64, void* stream);
 
 /* ---- dataset synthesis: the per-pixel stages of degrade_image (reference data/common_methods.py:52-107), csrc/degrade.hip ----
  * B images of one shape, x_u8 and y_u8 DEVICE uint8 [B,H,W,3] in BGR order; 16 <= H, W <= 4096, B <= 32767 (anything else: SR_ERR_INVALID).

@@ -23,6 +23,8 @@
 //      fp64 (correlation as an exact integer ratio).
 //   5. DCT: D = C_H X C_W^T by cgemm_f64.h's real fp64 GEMM, operators built on the device once per size; blocking sums in a fixed order.
 //   6. finalize: one workgroup per pair; central moments and variances from the integer power sums in 128-bit integers, one division.
+// The panel entry (sr_eda_pair_panels: create_advanced_visualizations and save_visual_example of cell 769cc582, per pair and unsummed) runs the
+// accumulate entry's kernels with a store in place of the sum, plus one pixel kernel for the colour-noise map and the difference map.
 // The accumulate entry adds |fftshift(fft2(gray))| (the DFT operators of metrics.hip), the 5-tap Sobel magnitude of hr, the normed
 // 256-level co-occurrence matrix of lr and the saturation histograms into caller-owned buffers, pair after pair in batch order.
 // No float atomics anywhere: a pair's row is the same bits on every run and for any B.
@@ -104,6 +106,28 @@ __device__ inline double block_sum_f64(double v, double* red) {
     return s;
 }
 
+// one channel's BGR tile [ER][ER] origin (y0 - EHALO, x0 - EHALO) with its BORDER_REFLECT_101 halo -> raw[c][ER * ER], all 256 threads
+__device__ inline void load_bgr_tile(const uint8_t* img, int H, int W, int y0, int x0, uint8_t (*raw)[ER * ER]) {
+    for (int i = (int)threadIdx.x; i < ER * ER * 3; i += 256) {                     // channel fastest: coalesced on interleaved BGR
+        const int p = i / 3, c = i - p * 3;
+        const int r = p / ER, cc = p - r * ER;
+        // beyond one tile's reach past the last row / column nothing is used: keep the reflected index inside the image
+        const int y = r101(min(y0 - EHALO + r, H + 1), H), x = r101(min(x0 - EHALO + cc, W + 1), W);
+        raw[c][p] = img[((int64_t)y * W + x) * 3 + c];
+    }
+}
+
+// the 5 x 5 binomial blur at the tile position rp5 points to (row pitch ER): the exact integer sum rounded half up once
+__device__ inline int blur5_at(const uint8_t* rp5) {
+    int t = 0;
+    for (int dy = -2; dy <= 2; ++dy) {
+        const uint8_t* row = rp5 + dy * ER;
+        const int h = row[-2] + 4 * row[-1] + 6 * row[0] + 4 * row[1] + row[2];
+        t += h * (dy == 0 ? 6 : (dy == -1 || dy == 1 ? 4 : 1));
+    }
+    return (t + 128) >> 8;
+}
+
 __device__ inline double i128_to_double(i128 v) {
     const bool neg = v < 0;
     const unsigned __int128 u = neg ? (unsigned __int128)(-v) : (unsigned __int128)v;
@@ -126,13 +150,7 @@ __global__ void __launch_bounds__(256) eda_planes_kernel(const uint8_t* lr, cons
     const int64_t HW = (int64_t)H * W;
     const uint8_t* img = ((g & 1) ? hr : lr) + (int64_t)(g >> 1) * HW * 3;
 
-    for (int i = tid; i < ER * ER * 3; i += 256) {                     // channel fastest: coalesced on interleaved BGR
-        const int p = i / 3, c = i - p * 3;
-        const int r = p / ER, cc = p - r * ER;
-        // beyond one tile's reach past the last row / column nothing is used: keep the reflected index inside the image
-        const int y = r101(min(y0 - EHALO + r, H + 1), H), x = r101(min(x0 - EHALO + cc, W + 1), W);
-        raw[c][p] = img[((int64_t)y * W + x) * 3 + c];
-    }
+    load_bgr_tile(img, H, W, y0, x0, raw);
     __syncthreads();
     for (int i = tid; i < ER * ER; i += 256) gry[i] = (uint8_t)gray_bgr(raw[0][i], raw[1][i], raw[2][i]);
     __syncthreads();
@@ -188,13 +206,7 @@ __global__ void __launch_bounds__(256) eda_planes_kernel(const uint8_t* lr, cons
         // 5 x 5 binomial blur per channel, power sums
         for (int c = 0; c < 3; ++c) {
             const uint8_t* rp5 = &raw[c][rp];
-            int t = 0;
-            for (int dy = -2; dy <= 2; ++dy) {
-                const uint8_t* row = rp5 + dy * ER;
-                const int h = row[-2] + 4 * row[-1] + 6 * row[0] + 4 * row[1] + row[2];
-                t += h * (dy == 0 ? 6 : (dy == -1 || dy == 1 ? 4 : 1));
-            }
-            const int b5 = (t + 128) >> 8;
+            const int b5 = blur5_at(rp5);
             const i64 xv = rp5[0];
             v[A_CN] += abs((int)xv - b5);
             if (blur5_out) blur5_out[o * 3 + c] = (uint8_t)b5;
@@ -500,26 +512,34 @@ __global__ void fill_f64_kernel(double* p, int n, double v) {
 // ------------------------------------------------------------------------------------------------
 // the accumulate entry's kernels
 // ------------------------------------------------------------------------------------------------
-// gray planes [2B][H W] and the saturation histograms np.histogram(S, linspace(0, 256, 51)): bin = S * 25 / 128 (edges i * 5.12).  grid (chunks, 2 B)
+// gray planes [2B][H W] and the saturation histograms.  NB 50: np.histogram(S, linspace(0, 256, 51)), bin = S * 25 / 128 (edges i * 5.12), all pairs
+// into one sat_counts [2][50] (the accumulate entry); NB 256: the counts per value of S, pair b into sat_counts [b][2][256] (the panel entry; NULL:
+// gray alone).  grid (chunks, 2 B)
+template <int NB>
 __global__ void __launch_bounds__(256) gray_sat_hist_kernel(const uint8_t* lr, const uint8_t* hr, int64_t HW, uint8_t* gray, u64* sat_counts) {
-    __shared__ int h[50];
+    __shared__ int h[NB];
     const int g = blockIdx.y, tid = threadIdx.x;
     const uint8_t* img = ((g & 1) ? hr : lr) + (int64_t)(g >> 1) * HW * 3;
-    if (tid < 50) h[tid] = 0;
+    if (tid < NB) h[tid] = 0;
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 4096 + tid, e = min((int64_t)(blockIdx.x + 1) * 4096, HW); i < e; i += 256) {
         const int b = img[3 * i], gg = img[3 * i + 1], r = img[3 * i + 2];
         gray[(int64_t)g * HW + i] = (uint8_t)gray_bgr(b, gg, r);
         int s, v;
         hsv_sv(b, gg, r, &s, &v);
-        atomicAdd(&h[s * 25 / 128], 1);
+        atomicAdd(&h[NB == 256 ? s : s * 25 / 128], 1);
     }
     __syncthreads();
-    if (tid < 50 && h[tid]) atomicAdd(&sat_counts[(g & 1) * 50 + tid], (u64)h[tid]);
+    if (!sat_counts) return;
+    u64* dst = sat_counts + (NB == 256 ? (int64_t)(g >> 1) * 2 * NB : 0) + (g & 1) * NB;
+    if (tid < NB && h[tid]) atomicAdd(&dst[tid], (u64)h[tid]);
 }
 
-// grad_sum [H][W] += hypot of the ksize-5 Sobel pair (1 4 6 4 1 x -1 -2 0 2 1, BORDER_REFLECT_101) of each hr gray image, in batch order
-__global__ void __launch_bounds__(256) grad5_accumulate_kernel(const uint8_t* gray, int B, int H, int W, double* grad_sum) {
+// hypot of the ksize-5 Sobel pair (1 4 6 4 1 x -1 -2 0 2 1, BORDER_REFLECT_101) of each hr gray image.  STORE false: grad [H][W] += it, in batch
+// order; STORE true: grad [B][H][W] = it, pair by pair (the panel entry).  The same expression either way, and 0.0 + v is v: a zeroed sum of one
+// pair holds the stored bits.
+template <bool STORE>
+__global__ void __launch_bounds__(256) grad5_kernel(const uint8_t* gray, int B, int H, int W, double* grad) {
     const int64_t HW = (int64_t)H * W;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
@@ -527,7 +547,7 @@ __global__ void __launch_bounds__(256) grad5_accumulate_kernel(const uint8_t* gr
     int ys[5], xs[5];
     for (int t = 0; t < 5; ++t) { ys[t] = r101(y + t - 2, H); xs[t] = r101(x + t - 2, W); }
     const int sm[5] = {1, 4, 6, 4, 1}, df[5] = {-1, -2, 0, 2, 1};
-    double s = grad_sum[p];
+    double s = STORE ? 0.0 : grad[p];
     for (int b = 0; b < B; ++b) {
         const uint8_t* G = gray + (int64_t)(2 * b + 1) * HW;
         int gx = 0, gy = 0;
@@ -537,33 +557,118 @@ __global__ void __launch_bounds__(256) grad5_accumulate_kernel(const uint8_t* gr
                 gx += sm[i] * df[j] * v;
                 gy += df[i] * sm[j] * v;
             }
-        s += sqrt((double)((i64)gx * gx + (i64)gy * gy));
+        const double m = sqrt((double)((i64)gx * gx + (i64)gy * gy));
+        if (STORE) grad[(int64_t)b * HW + p] = m;
+        else s += m;
     }
-    grad_sum[p] = s;
+    if (!STORE) grad[p] = s;
 }
 
-// glcm_sum [256][256] += (C_b + C_b^T) / T, T = 2 H (W - 1), pair after pair
-__global__ void __launch_bounds__(256) glcm_accumulate_kernel(const int* counts, int B, double T, double* glcm_sum) {
+// (C_b + C_b^T) / T, T = 2 H (W - 1).  STORE false: glcm [256][256] += it, pair after pair; STORE true: glcm [B][256][256] = it (the panel entry)
+template <bool STORE>
+__global__ void __launch_bounds__(256) glcm_normed_kernel(const int* counts, int B, double T, double* glcm) {
     const int i = blockIdx.x, j = threadIdx.x;
-    double s = glcm_sum[i * 256 + j];
+    double s = STORE ? 0.0 : glcm[i * 256 + j];
     for (int b = 0; b < B; ++b) {
         const int* C = counts + (int64_t)b * 65536;
-        s += (double)(C[i * 256 + j] + C[j * 256 + i]) / T;
+        const double v = (double)(C[i * 256 + j] + C[j * 256 + i]) / T;
+        if (STORE) glcm[(int64_t)b * 65536 + i * 256 + j] = v;
+        else s += v;
     }
-    glcm_sum[i * 256 + j] = s;
+    if (!STORE) glcm[i * 256 + j] = s;
 }
 
-// sum_{lr,hr} [H][W] += fftshift(|F|) of images g0 .. g0 + n - 1 (absf [n][H][W]), in image order
-__global__ void __launch_bounds__(256) fft_accumulate_kernel(const double* absf, int g0, int n, int H, int W, double* sum_lr, double* sum_hr) {
+// fftshift(|F|) of images g0 .. g0 + n - 1 (absf [n][H][W]); image g0 + i is pair (g0 + i) >> 1's lr (even) or hr (odd), and a chunk may begin or
+// end between the two.  STORE false: out_{lr,hr} [H][W] += it, in image order; STORE true: out_{lr,hr} [B][H][W] = it, a NULL side skipped (the
+// panel entry).
+template <bool STORE>
+__global__ void __launch_bounds__(256) fft_shift_kernel(const double* absf, int g0, int n, int H, int W, double* out_lr, double* out_hr) {
     const int64_t HW = (int64_t)H * W;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= HW) return;
     const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
     const int64_t src = (int64_t)((y + (H + 1) / 2) % H) * W + (x + (W + 1) / 2) % W;
-    double s[2] = {sum_lr[p], sum_hr[p]};
+    if (STORE) {
+        for (int i = 0; i < n; ++i) {
+            double* o = ((g0 + i) & 1) ? out_hr : out_lr;
+            if (o) o[(int64_t)((g0 + i) >> 1) * HW + p] = absf[(int64_t)i * HW + src];
+        }
+        return;
+    }
+    double s[2] = {out_lr[p], out_hr[p]};
     for (int i = 0; i < n; ++i) s[(g0 + i) & 1] += absf[(int64_t)i * HW + src];
-    sum_lr[p] = s[0];
-    sum_hr[p] = s[1];
+    out_lr[p] = s[0];
+    out_hr[p] = s[1];
+}
+
+// ------------------------------------------------------------------------------------------------
+// the panel entry's own kernels
+// ------------------------------------------------------------------------------------------------
+// per pixel of pair b: noise [B][H][W] = (sum over B, G, R of |lr - blur5(lr)|) / 3.0 (the planes pass's blur; NULL: not stored), its integer sum
+// over the image into cn_acc [B] (one integer atomic per workgroup: exact, order-independent), diff [B][H][W] = the 14-bit gray of |lr - hr| per
+// channel (NULL: not computed).  grid (tiles x, tiles y, B)
+__global__ void __launch_bounds__(256) eda_panel_pixel_kernel(const uint8_t* lr, const uint8_t* hr, int H, int W, double* noise, u64* cn_acc, uint8_t* diff) {
+    __shared__ uint8_t raw[3][ER * ER];
+    __shared__ u64 lacc[1];
+    const int b = blockIdx.z, tid = threadIdx.x;
+    const int y0 = blockIdx.y * ET, x0 = blockIdx.x * ET;
+    const int64_t HW = (int64_t)H * W;
+    load_bgr_tile(lr + (int64_t)b * HW * 3, H, W, y0, x0, raw);
+    __syncthreads();
+    i64 v[1] = {0};
+    for (int q = 0; q < 4; ++q) {
+        const int p = tid + 256 * q, r = p >> 5, cc = p & 31;
+        const int y = y0 + r, x = x0 + cc;
+        if (y >= H || x >= W) continue;
+        const int rp = (r + EHALO) * ER + cc + EHALO;
+        const int64_t o = (int64_t)b * HW + (int64_t)y * W + x;
+        int cn = 0, ad[3];
+        for (int c = 0; c < 3; ++c) {
+            const uint8_t* rp5 = &raw[c][rp];
+            cn += abs((int)rp5[0] - blur5_at(rp5));
+            if (diff) ad[c] = abs((int)rp5[0] - (int)hr[o * 3 + c]);
+        }
+        v[0] += cn;
+        if (noise) noise[o] = (double)cn / 3.0;
+        if (diff) diff[o] = (uint8_t)gray_bgr(ad[0], ad[1], ad[2]);
+    }
+    block_accumulate(v, lacc, cn_acc + b);
+}
+
+// scalars [B][SR_NUM_EDA_PANEL_SCALARS]: the expressions eda_finalize_kernel forms for glcm_contrast (one angle: (0.0 + c) / 1.0 is c) and color_noise_lr
+__global__ void eda_panel_scalars_kernel(const double* props, const u64* cn_acc, int B, int H, int W, double* scalars) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double dn = (double)((i64)H * W);
+    scalars[(int64_t)b * SR_NUM_EDA_PANEL_SCALARS + SR_EDA_PANEL_GLCM_CONTRAST] = props[(int64_t)b * 3];
+    scalars[(int64_t)b * SR_NUM_EDA_PANEL_SCALARS + SR_EDA_PANEL_NOISE_MEAN] = (double)(i64)cn_acc[b] / (3.0 * dn);
+}
+
+// |fftshift(fft2(gray))| of images 0 .. nimg - 1 of gray [nimg][H W] (lr and hr interleaved) by the DFT operators of metrics.hip, in chunks of
+// images: summed into out_{lr,hr} [H][W] (STORE false) or stored per pair (STORE true).  A chunk counts images, so it may end inside a pair.
+template <bool STORE>
+int dft_magnitudes(sr_ctx* ctx, const uint8_t* gray, int nimg, int H, int W, double* out_lr, double* out_hr, hipStream_t st) {
+    const int64_t HW = (int64_t)H * W;
+    const double *ahr, *ahi, *awr, *awi;
+    if (int rc = dft_full_operator(ctx, H, st, &ahr, &ahi)) return rc;
+    if (int rc = dft_full_operator(ctx, W, st, &awr, &awi)) return rc;
+    const size_t per_img = sizeof(double) * (size_t)HW * 4;          // X, T's real and imaginary parts, |F|
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nimg, EDA_CHUNK_BYTES / per_img));
+    double* xb = static_cast<double*>(ctx->arena(ctx->eda_dct, per_img * (size_t)chunk, st));
+    if (!xb) return SR_ERR_OOM;
+    double* tr = xb + (int64_t)chunk * HW;
+    double* ti = tr + (int64_t)chunk * HW;
+    double* fa = ti + (int64_t)chunk * HW;
+    const dim3 fgrid((W + GT - 1) / GT, (H + GT - 1) / GT, 1);
+    for (int g0 = 0; g0 < nimg; g0 += chunk) {
+        const int n = std::min(chunk, nimg - g0);
+        hipLaunchKernelGGL(gray_to_f64_kernel, dim3(grid1d((int64_t)n * HW)), dim3(256), 0, st, gray, (int64_t)g0 * HW, (int64_t)n * HW, xb);
+        cgemm_dispatch<CG_STORE>(false, true, dim3(fgrid.x, fgrid.y, n), st, H, W, W, xb, nullptr, W, 1, HW, awr, awi, 1, W, 0, tr, ti, HW);
+        cgemm_dispatch<CG_ABS>(true, true, dim3(fgrid.x, fgrid.y, n), st, H, W, H, ahr, ahi, H, 1, 0, tr, ti, W, 1, HW, fa, nullptr, HW);
+        hipLaunchKernelGGL(fft_shift_kernel<STORE>, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, fa, g0, n, H, W, out_lr, out_hr);
+    }
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
 }
 
 int check_shape(sr_ctx* ctx, const char* who, int B, int H, int W) {
@@ -675,34 +780,69 @@ int sr_eda_accumulate(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, i
     uint8_t* gray = reinterpret_cast<uint8_t*>(wk);
     int* glcm = reinterpret_cast<int*>(wk + b_gray);
 
-    hipLaunchKernelGGL(gray_sat_hist_kernel, dim3((unsigned)((HW + 4095) / 4096), nimg), dim3(256), 0, st, lr_u8, hr_u8, HW, gray,
+    hipLaunchKernelGGL(gray_sat_hist_kernel<50>, dim3((unsigned)((HW + 4095) / 4096), nimg), dim3(256), 0, st, lr_u8, hr_u8, HW, gray,
                        reinterpret_cast<u64*>(sat_counts_i64));
-    hipLaunchKernelGGL(grad5_accumulate_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, gray, B, H, W, grad_hr_sum_f64);
+    hipLaunchKernelGGL(grad5_kernel<false>, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, gray, B, H, W, grad_hr_sum_f64);
     SR_HIP(ctx, hipMemsetAsync(glcm, 0, sizeof(int) * (size_t)B * 65536, st));
     hipLaunchKernelGGL(glcm_count_kernel<false>, dim3((unsigned)std::min(16, (H + 31) / 32), B), dim3(256), 0, st, gray, 2, H, W, 0, 1, glcm);
-    hipLaunchKernelGGL(glcm_accumulate_kernel, dim3(256), dim3(256), 0, st, glcm, B, 2.0 * (double)H * (double)(W - 1), glcm_sum_f64);
+    hipLaunchKernelGGL(glcm_normed_kernel<false>, dim3(256), dim3(256), 0, st, glcm, B, 2.0 * (double)H * (double)(W - 1), glcm_sum_f64);
     SR_HIP(ctx, hipGetLastError());
 
-    const double *ahr, *ahi, *awr, *awi;
-    if (int rc = dft_full_operator(ctx, H, st, &ahr, &ahi)) return rc;
-    if (int rc = dft_full_operator(ctx, W, st, &awr, &awi)) return rc;
-    const size_t per_img = sizeof(double) * (size_t)HW * 4;          // X, T's real and imaginary parts, |F|
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nimg, EDA_CHUNK_BYTES / per_img));
-    double* xb = static_cast<double*>(ctx->arena(ctx->eda_dct, per_img * (size_t)chunk, st));
-    if (!xb) return SR_ERR_OOM;
-    double* tr = xb + (int64_t)chunk * HW;
-    double* ti = tr + (int64_t)chunk * HW;
-    double* fa = ti + (int64_t)chunk * HW;
-    const dim3 fgrid((W + GT - 1) / GT, (H + GT - 1) / GT, 1);
-    for (int g0 = 0; g0 < nimg; g0 += chunk) {
-        const int n = std::min(chunk, nimg - g0);
-        hipLaunchKernelGGL(gray_to_f64_kernel, dim3(grid1d((int64_t)n * HW)), dim3(256), 0, st, gray, (int64_t)g0 * HW, (int64_t)n * HW, xb);
-        cgemm_dispatch<CG_STORE>(false, true, dim3(fgrid.x, fgrid.y, n), st, H, W, W, xb, nullptr, W, 1, HW, awr, awi, 1, W, 0, tr, ti, HW);
-        cgemm_dispatch<CG_ABS>(true, true, dim3(fgrid.x, fgrid.y, n), st, H, W, H, ahr, ahi, H, 1, 0, tr, ti, W, 1, HW, fa, nullptr, HW);
-        hipLaunchKernelGGL(fft_accumulate_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, fa, g0, n, H, W, fft_lr_sum_f64, fft_hr_sum_f64);
+    return dft_magnitudes<false>(ctx, gray, nimg, H, W, fft_lr_sum_f64, fft_hr_sum_f64, st);
+}
+
+int sr_eda_pair_panels(sr_ctx* ctx, const uint8_t* lr_u8, const uint8_t* hr_u8, int B, int H, int W, double* spec_lr_f64, double* spec_hr_f64,
+                       double* grad_hr_f64, double* glcm_lr_f64, double* noise_lr_f64, uint8_t* diff_u8, int64_t* sat_hist_i64, double* scalars_f64,
+                       void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!lr_u8 || !hr_u8) return ctx->fail(SR_ERR_INVALID, "eda_pair_panels: null tensor");
+    if (int rc = check_shape(ctx, "eda_pair_panels", B, H, W)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t HW = (int64_t)H * W;
+    const int nimg = 2 * B;
+    const bool want_spec = spec_lr_f64 || spec_hr_f64, want_glcm = glcm_lr_f64 || scalars_f64;
+    const bool want_gray = want_spec || grad_hr_f64 || want_glcm || sat_hist_i64;
+    const size_t b_gray = want_gray ? al256((size_t)nimg * HW) : 0, b_glcm = want_glcm ? al256(sizeof(int) * (size_t)B * 65536) : 0;
+    const size_t b_props = al256(sizeof(double) * (size_t)B * 3), b_cn = al256(sizeof(u64) * (size_t)B);
+    char* wk = static_cast<char*>(ctx->arena(ctx->eda_work, b_gray + b_glcm + b_props + b_cn, st));
+    if (!wk) return SR_ERR_OOM;
+    uint8_t* gray = reinterpret_cast<uint8_t*>(wk); wk += b_gray;
+    int* glcm = reinterpret_cast<int*>(wk); wk += b_glcm;
+    double* props = reinterpret_cast<double*>(wk); wk += b_props;
+    u64* cn = reinterpret_cast<u64*>(wk);
+
+    int rec = ctx->prof_open("eda_panel_planes", 0.0, (double)nimg * HW * 3.0, st);
+    if (want_gray) {
+        if (sat_hist_i64) SR_HIP(ctx, hipMemsetAsync(sat_hist_i64, 0, sizeof(int64_t) * (size_t)B * 512, st));
+        hipLaunchKernelGGL(gray_sat_hist_kernel<256>, dim3((unsigned)((HW + 4095) / 4096), nimg), dim3(256), 0, st, lr_u8, hr_u8, HW, gray,
+                           reinterpret_cast<u64*>(sat_hist_i64));
+    }
+    if (noise_lr_f64 || diff_u8 || scalars_f64) {
+        SR_HIP(ctx, hipMemsetAsync(cn, 0, sizeof(u64) * (size_t)B, st));
+        hipLaunchKernelGGL(eda_panel_pixel_kernel, dim3((W + ET - 1) / ET, (H + ET - 1) / ET, B), dim3(256), 0, st, lr_u8, hr_u8, H, W, noise_lr_f64, cn, diff_u8);
+    }
+    if (grad_hr_f64) hipLaunchKernelGGL(grad5_kernel<true>, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, gray, B, H, W, grad_hr_f64);
+    ctx->prof_close(rec, st);
+    if (want_glcm) {
+        rec = ctx->prof_open("eda_panel_glcm", 0.0, 0.0, st);
+        SR_HIP(ctx, hipMemsetAsync(glcm, 0, sizeof(int) * (size_t)B * 65536, st));
+        hipLaunchKernelGGL(glcm_count_kernel<false>, dim3((unsigned)std::min(16, (H + 31) / 32), B), dim3(256), 0, st, gray, 2, H, W, 0, 1, glcm);
+        if (glcm_lr_f64) hipLaunchKernelGGL(glcm_normed_kernel<true>, dim3(256), dim3(256), 0, st, glcm, B, 2.0 * (double)H * (double)(W - 1), glcm_lr_f64);
+        if (scalars_f64) {
+            // 256 levels quantise to themselves ((uint8)(float32(g) / 255 * 255) is g for every g), so these are sr_eda_pair_stats' counts
+            hipLaunchKernelGGL(glcm_props_kernel, dim3(1, B), dim3(256), 0, st, glcm, 256, props);
+            hipLaunchKernelGGL(eda_panel_scalars_kernel, dim3((B + 255) / 256), dim3(256), 0, st, props, cn, B, H, W, scalars_f64);
+        }
+        ctx->prof_close(rec, st);
     }
     SR_HIP(ctx, hipGetLastError());
-    return SR_OK;
+    if (!want_spec) return SR_OK;
+
+    rec = ctx->prof_open("eda_panel_dft", (double)nimg * 8.0 * (H * (double)W * W + (double)H * H * W), (double)nimg * HW * 8.0 * 7.0, st);
+    const int rc = dft_magnitudes<true>(ctx, gray, nimg, H, W, spec_lr_f64, spec_hr_f64, st);
+    ctx->prof_close(rec, st);
+    return rc;
 }
 
 }  // extern "C"

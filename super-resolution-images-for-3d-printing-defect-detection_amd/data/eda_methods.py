@@ -1,6 +1,6 @@
-"""The dataset EDA's metrics (reference: data/EDA.ipynb -- ImagePairLoader, ImageDatasetAnalyzer, ImagePairMetrics, MetricsAggregator,
-StatsReporter), with every per-pair statistic and global accumulator on the MI355X (csrc/eda.hip: sr_eda_pair_stats, sr_eda_accumulate)
-and the bookkeeping on the host in NumPy.  A notebook imports these names instead of defining the cells; cv2, scikit-image, scipy and
+"""The dataset EDA (reference: data/EDA.ipynb -- ImagePairLoader, ImageDatasetAnalyzer, ImagePairMetrics, MetricsAggregator,
+StatsReporter, ImageDataVisualization, run_eda_pipeline), with every per-pair statistic, global accumulator and per-pair panel map on
+the MI355X (csrc/eda.hip: sr_eda_pair_stats, sr_eda_accumulate, sr_eda_pair_panels) and the bookkeeping on the host in NumPy.  A notebook imports these names instead of defining the cells; cv2, scikit-image, scipy and
 pandas are not needed.
 
 Images are uint8 BGR [H, W, 3] as cv2.imread returns them (files are decoded through PIL and the channel order restored), gray images
@@ -18,8 +18,17 @@ VGG16's and VGG19's do not): after ImageDatasetAnalyzer.load_lpips(alexnet_path,
 Context.lpips) -- lpips_score returns the float, collect / collect_arrays fill the rows' lpips column in the same batch pass, loss_fn()
 returns the scoring callable and StatsReporter.lpips_scenarios gives the pipeline's best / worst file names.  The loaded state is
 process-wide and nothing loads it implicitly; until then, and after unload_lpips(), the lpips column is NaN and lpips_score and loss_fn
-raise NotImplementedError.  Out of scope: every matplotlib / seaborn panel.  Importing this module and its host helpers
-(ImagePairLoader.iter_pairs, ImagePairMetrics, StatsReporter) needs no GPU."""
+raise NotImplementedError.
+
+ImageDataVisualization is the numeric half of the notebook's plots: visual_example / advanced_panel / advanced_panels return the maps
+of one pair or a stack from the device (the spectra as np.log(mag + 1e-8) of the device's magnitudes, taken here), global_advanced_panel
+and the *_data methods return the numbers under the global panel and the seven table plots in host NumPy on collect's global_data and
+StatsReporter.dataframe's columns (no pandas, scipy, seaborn or matplotlib).  run_eda_panels returns (df, panels); run_eda_pipeline has
+the reference's signature, returns df and writes each panel as an .npz where the reference writes the .png of the same stem.  Ranking
+the examples by lpips needs load_lpips; rank_by names another column.  Out of scope: the drawing itself -- the plotting names
+(save_visual_example, create_advanced_visualizations, basic_distributions, ...) raise NotImplementedError naming the numeric method --
+PNG writing and OpenCV's JET colour map.  Importing this module and its host helpers (ImagePairLoader.iter_pairs, ImagePairMetrics,
+StatsReporter, ImageDataVisualization's *_data methods and global_advanced_panel) needs no GPU."""
 import math
 import os
 
@@ -387,3 +396,331 @@ class StatsReporter:
             std = math.sqrt(float(((a - mean) ** 2).sum()) / (n - 1)) if n > 1 else math.nan
             out[k] = {"mean": mean, "std": std, "25%": quantile(0.25), "50%": quantile(0.5), "75%": quantile(0.75)}
         return out
+
+
+def _finite(col):
+    a = np.asarray(col, dtype=np.float64).ravel()
+    return a[np.isfinite(a)]
+
+
+def _hist30(col):
+    """(counts, edges) of plt.hist(col, bins=30): np.histogram over the finite values' own range (matplotlib takes the range with
+    nanmin / nanmax and np.histogram then drops the NaNs); None for a column without a finite value, where the plot fails."""
+    a = _finite(col)
+    return np.histogram(a, bins=30) if a.size else None
+
+
+def _sat_density(counts):
+    """(density, edges) of plt.hist(S.ravel(), bins=50, density=True) from the 256 counts of S: np.histogram over the image's own
+    [min, max]; integer weights give the bits of the unweighted call on the pixels."""
+    counts = np.asarray(counts, dtype=np.int64)
+    nz = np.nonzero(counts)[0]
+    return np.histogram(np.arange(256), 50, range=(int(nz[0]), int(nz[-1])), weights=counts, density=True)
+
+
+def _contrast(P):
+    """graycoprops(P, 'contrast')[0, 0] of a normed [L, L] matrix."""
+    L = P.shape[0]
+    I, J = np.ogrid[0:L, 0:L]
+    return float(np.sum(P * (I - J) ** 2))
+
+
+class ImageDataVisualization:
+    """The numeric half of the reference's plots (cell 769cc582): every array and number a panel draws, no drawing.  The plotting names
+    raise NotImplementedError naming the method that returns their numbers."""
+    OVERLAY_PAIRS = (("blocking_lr", "blocking_hr", "Blocking Score"), ("ringing_lr", "ringing_hr", "Ringing Artifact"),
+                     ("saturation_mean_lr", "saturation_mean_hr", "Saturation Mean"), ("brightness_mean_lr", "brightness_mean_hr", "Brightness Mean"),
+                     ("color_noise_lr", "color_noise_hr", "Color Noise"))
+    BOX_GROUPS = (("blocking_lr", "blocking_hr", "Blocking"), ("ringing_lr", "ringing_hr", "Ringing"), ("saturation_mean_lr", "saturation_mean_hr", "Saturation"),
+                  ("brightness_mean_lr", "brightness_mean_hr", "Brightness"), ("color_noise_lr", "color_noise_hr", "ColorNoise"))
+    DISTRIBUTION_COLUMNS = ("lpips", "psnr", "ssim", "lap_var_hr", "rms_noise_hr", "blocking_hr", "glcm_contrast", "glcm_homogeneity", "glcm_correlation")
+    CORRELATION_COLUMNS = ("lpips", "psnr", "ssim", "lap_var_hr", "rms_noise_hr", "blocking_hr", "ringing_hr", "saturation_mean_hr", "brightness_mean_hr",
+                           "edge_diff")
+    SCATTER_PAIRS = (("lpips", "psnr", "LPIPS vs PSNR"), ("lpips", "ssim", "LPIPS vs SSIM"), ("lap_var_hr", "psnr", "LaplacianVar HR vs PSNR"),
+                     ("rms_noise_hr", "psnr", "Noise HR vs PSNR"), ("blocking_hr", "ringing_hr", "Blocking vs Ringing"),
+                     ("saturation_mean_hr", "brightness_mean_hr", "Saturation vs Brightness"), ("edge_diff", "psnr", "Edge Diff vs PSNR"),
+                     ("edge_diff", "ssim", "Edge Diff vs SSIM"))
+    _PLOTS = {"save_visual_example": "visual_example", "create_advanced_visualizations": "advanced_panel",
+              "create_global_advanced_visualizations": "global_advanced_panel", "basic_distributions": "basic_distributions_data",
+              "artifact_color_histograms": "artifact_color_histograms_data", "artifact_boxplots": "artifact_boxplots_data",
+              "channel_shape_bars": "channel_shape_bars_data", "correlation_matrix": "correlation_matrix_data", "scatter_relations": "scatter_relations_data"}
+
+    # ---------------------------------------------------------------- per pair, on the device
+    @staticmethod
+    def _aligned(lr_img, hr_img, who):
+        lr, hr = _bgr(lr_img, who), _bgr(hr_img, who)
+        if lr.shape != hr.shape:                      # save_visual_example's cv2.resize(lr, hr's size, INTER_CUBIC); the identity on an aligned pair
+            ctx = _context()
+            lr = ctx.resize(ctx.to_device(lr[None]), hr.shape[0], hr.shape[1], "INTER_CUBIC")[0].cpu().numpy()
+        return lr, hr
+
+    @staticmethod
+    def visual_example(lr_img, hr_img):
+        """save_visual_example's three images -> {'lr_rgb', 'hr_rgb', 'diff_gray'} uint8: the two RGB views and the gray difference map
+        cvtColor(absdiff(lr, hr), BGR2GRAY) from the device.  The JET colour map on top of it is the plot's half: OpenCV's table is not
+        restated here."""
+        lr, hr = ImageDataVisualization._aligned(lr_img, hr_img, "visual_example")
+        ctx = _context()
+        d = ctx.eda_pair_panels(ctx.to_device(lr[None]), ctx.to_device(hr[None]), which=("diff",))["diff"][0].cpu().numpy()
+        return {"lr_rgb": np.ascontiguousarray(lr[..., ::-1]), "hr_rgb": np.ascontiguousarray(hr[..., ::-1]), "diff_gray": d}
+
+    @staticmethod
+    def _panel_of(host, i):
+        return {"lr_log_spectrum": np.log(host["spec_lr"][i] + 1e-8), "hr_log_spectrum": np.log(host["spec_hr"][i] + 1e-8),
+                "gradient_magnitude": host["grad_hr"][i], "lr_glcm": host["glcm_lr"][i], "lr_glcm_contrast": float(host["glcm_contrast"][i]),
+                "noise_map": host["noise_lr"][i], "color_noise_mean": float(host["noise_mean"][i]),
+                "sat_lr": _sat_density(host["sat_hist"][i, 0]), "sat_hr": _sat_density(host["sat_hist"][i, 1]), "diff_gray": host["diff"][i]}
+
+    @staticmethod
+    def advanced_panels(lr_imgs, hr_imgs):
+        """advanced_panel for aligned stacks [B, H, W, 3] uint8 BGR (NumPy arrays or device tensors) -> list of B dicts (each also carries
+        visual_example's 'diff_gray').  One device call and one read per chunk of MetricsAggregator.BATCH pairs."""
+        import torch
+        ctx = _context()
+        to_dev = lambda a: a.contiguous() if isinstance(a, torch.Tensor) else ctx.to_device(np.ascontiguousarray(np.asarray(a)))
+        out = []
+        for s in range(0, int(lr_imgs.shape[0]), MetricsAggregator.BATCH):
+            dev = ctx.eda_pair_panels(to_dev(lr_imgs[s:s + MetricsAggregator.BATCH]), to_dev(hr_imgs[s:s + MetricsAggregator.BATCH]))
+            host = {k: v.cpu().numpy() for k, v in dev.items()}
+            out.extend(ImageDataVisualization._panel_of(host, i) for i in range(host["diff"].shape[0]))
+        return out
+
+    @staticmethod
+    def advanced_panel(lr_img, hr_img):
+        """create_advanced_visualizations' numbers for one aligned BGR pair: 'lr_log_spectrum', 'hr_log_spectrum' (np.log(mag + 1e-8) of the
+        device's magnitudes, taken here), 'gradient_magnitude', 'lr_glcm' [256, 256], 'lr_glcm_contrast', 'noise_map', 'color_noise_mean',
+        'sat_lr', 'sat_hr' ((density, edges) of plt.hist(S.ravel(), bins=50, density=True))."""
+        lr, hr = _bgr(lr_img, "advanced_panel"), _bgr(hr_img, "advanced_panel")
+        if lr.shape != hr.shape:
+            raise ValueError(f"advanced_panel: the pair is not aligned ({lr.shape} and {hr.shape}); ImagePairLoader.load_and_align does that")
+        p = ImageDataVisualization.advanced_panels(lr[None], hr[None])[0]
+        p.pop("diff_gray")
+        return p
+
+    # ---------------------------------------------------------------- host NumPy on collect's global_data and on the frame
+    @staticmethod
+    def global_advanced_panel(global_data):
+        """create_global_advanced_visualizations' numbers from collect's global_data; None when it holds no pair (the reference prints and returns)."""
+        if global_data is None or global_data.get("count", 0) == 0:
+            return None
+        n, eps = global_data["count"], 1e-8
+        out = {k + "_avg": np.asarray(global_data[k + "_sum"]) / n for k in ("lr_fft", "hr_fft", "grad_hr")}
+        out["lr_log_spectrum"], out["hr_log_spectrum"] = np.log(out["lr_fft_avg"] + eps), np.log(out["hr_fft_avg"] + eps)
+        glcm_sum = np.asarray(global_data["glcm_sum"])
+        glcm_avg = (glcm_sum / glcm_sum.sum()).reshape(glcm_sum.shape[0], glcm_sum.shape[1])
+        out["glcm_avg"], out["glcm_contrast"] = glcm_avg, _contrast(glcm_avg)
+        bins = np.asarray(global_data["sat_bins"])
+        width = bins[1] - bins[0]
+        for s in ("lr", "hr"):
+            c = np.asarray(global_data[f"sat_{s}_counts"])
+            out[f"sat_{s}_density"] = c / (c.sum() * width + eps)
+        out["sat_centers"] = 0.5 * (bins[:-1] + bins[1:])
+        noise = np.array(global_data["noise_means_lr"], dtype=np.float64)
+        out["noise_means"], out["noise_mean"], out["noise_std"] = noise, float(noise.mean()), float(noise.std())
+        out["noise_hist"] = np.histogram(noise, bins=30)
+        return out
+
+    @staticmethod
+    def basic_distributions_data(df):
+        """{column: (counts, edges)}: plt.hist(df[column], bins=30) of the nine columns of distributions.png."""
+        return {m: _hist30(df[m]) for m in ImageDataVisualization.DISTRIBUTION_COLUMNS}
+
+    @staticmethod
+    def kde(values, gridsize=200, cut=3):
+        """The curve seaborn.kdeplot draws by default, restated from seaborn's documented defaults (seaborn is not installed where this
+        project runs, so it is not pinned against seaborn itself): a Gaussian kernel with Scott's factor n^(-1/5) on the sample standard
+        deviation (ddof 1), evaluated at `gridsize` points from min - cut bw to max + cut bw -> (grid, density, bw)."""
+        x = _finite(values)
+        n = x.size
+        if n < 2:
+            return None
+        bw = float(np.std(x, ddof=1)) * n ** (-0.2)
+        if not bw > 0.0:
+            return None
+        grid = np.linspace(x.min() - cut * bw, x.max() + cut * bw, gridsize)
+        z = (grid[:, None] - x[None, :]) / bw
+        return grid, np.exp(-0.5 * z * z).sum(1) / (n * bw * math.sqrt(2.0 * math.pi)), bw
+
+    @staticmethod
+    def artifact_color_histograms_data(df):
+        """artifact_color_histograms.png: per overlay title {'lr', 'hr'} each its own 30-bin histogram (two plt.hist calls), then
+        'edge_diff' (histogram) and 'edge_diff_kde' (kde above)."""
+        out = {title: {"lr": _hist30(df[l]), "hr": _hist30(df[h])} for l, h, title in ImageDataVisualization.OVERLAY_PAIRS}
+        out["edge_diff"] = _hist30(df["edge_diff"])
+        k = ImageDataVisualization.kde(df["edge_diff"])
+        out["edge_diff_kde"] = None if k is None else {"grid": k[0], "density": k[1], "bw": k[2]}
+        return out
+
+    @staticmethod
+    def boxplot_stats(values, whis=1.5):
+        """matplotlib.cbook.boxplot_stats(x, whis) of the finite values: q1 / med / q3 by linear percentiles, the whiskers at the furthest
+        data within whis IQR of the box (the quartile itself when there is none), fliers beyond them (low ones first), mean, iqr."""
+        x = _finite(values)
+        if not x.size:
+            return None
+        q1, med, q3 = (float(v) for v in np.percentile(x, [25, 50, 75]))
+        iqr = q3 - q1
+        hi, lo = x[x <= q3 + whis * iqr], x[x >= q1 - whis * iqr]
+        whishi = q3 if hi.size == 0 or hi.max() < q3 else float(hi.max())
+        whislo = q1 if lo.size == 0 or lo.min() > q1 else float(lo.min())
+        return {"mean": float(np.mean(x)), "med": med, "q1": q1, "q3": q3, "iqr": iqr, "whislo": whislo, "whishi": whishi,
+                "fliers": np.concatenate([x[x < whislo], x[x > whishi]])}
+
+    @staticmethod
+    def artifact_boxplots_data(df):
+        """{label: boxplot_stats} under the reference's ten labels ('Blocking LR', 'Blocking HR', ...), in its order."""
+        out = {}
+        for l, h, name in ImageDataVisualization.BOX_GROUPS:
+            out[f"{name} LR"] = ImageDataVisualization.boxplot_stats(df[l])
+            out[f"{name} HR"] = ImageDataVisualization.boxplot_stats(df[h])
+        return out
+
+    @staticmethod
+    def channel_shape_bars_data(df):
+        """The four bar groups' heights, each [B, G, R]: the columns' means, NaN skipped as Series.mean does; None when a column is missing."""
+        need = [f"ch{c}_{k}_{s}" for k in ("skew", "kurt") for c in range(3) for s in ("lr", "hr")]
+        if not all(r in df for r in need):
+            return None
+        mean = lambda k: float(_finite(df[k]).mean()) if _finite(df[k]).size else math.nan
+        return {f"{k}_means_{s}": [mean(f"ch{c}_{k}_{s}") for c in range(3)] for k in ("skew", "kurt") for s in ("lr", "hr")}
+
+    @staticmethod
+    def correlation_matrix_data(df):
+        """{'columns', 'corr'}: Pearson's r between the available ones of the ten columns, each pair over the rows where both are finite,
+        as DataFrame.corr does (NaN where fewer than two such rows or a constant column); None below three columns."""
+        cols = [m for m in ImageDataVisualization.CORRELATION_COLUMNS if m in df]
+        if len(cols) < 3:
+            return None
+        data = [np.asarray(df[m], dtype=np.float64) for m in cols]
+        corr = np.full((len(cols), len(cols)), math.nan)
+        for i, a in enumerate(data):
+            for j, b in enumerate(data[:i + 1]):
+                m = np.isfinite(a) & np.isfinite(b)
+                if m.sum() < 2:
+                    continue
+                x, y = a[m] - a[m].mean(), b[m] - b[m].mean()
+                den = math.sqrt(float((x * x).sum()) * float((y * y).sum()))
+                if den > 0.0:
+                    corr[i, j] = corr[j, i] = 1.0 if i == j else float((x * y).sum()) / den
+        return {"columns": cols, "corr": corr}
+
+    @staticmethod
+    def scatter_relations_data(df):
+        """The scatter panels present in the frame: list of {'x', 'y', 'title', 'x_values', 'y_values'}."""
+        return [{"x": x, "y": y, "title": t, "x_values": np.asarray(df[x], dtype=np.float64), "y_values": np.asarray(df[y], dtype=np.float64)}
+                for x, y, t in ImageDataVisualization.SCATTER_PAIRS if x in df and y in df]
+
+    @staticmethod
+    def flatten_panel(panel, prefix=""):
+        """A panel as the flat {name: array} that its .npz holds: nested names joined with '.', tuples and lists of arrays by index,
+        None left out."""
+        out = {}
+        if panel is None:
+            return out
+        if isinstance(panel, dict):
+            items = panel.items()
+        elif isinstance(panel, (tuple, list)) and any(isinstance(v, (dict, tuple, list, np.ndarray)) or v is None for v in panel):
+            items = enumerate(panel)
+        else:
+            out[prefix or "value"] = np.asarray(panel)
+            return out
+        for k, v in items:
+            out.update(ImageDataVisualization.flatten_panel(v, f"{prefix}.{k}" if prefix else str(k)))
+        return out
+
+
+def _plot_stub(name, numeric):
+    def stub(*args, **kwargs):
+        raise NotImplementedError(f"{name}: drawing is not offered (no matplotlib / seaborn here); ImageDataVisualization.{numeric} returns the numbers "
+                                  f"this plot shows")
+    stub.__name__ = name
+    return staticmethod(stub)
+
+
+for _name, _numeric in ImageDataVisualization._PLOTS.items():
+    setattr(ImageDataVisualization, _name, _plot_stub(_name, _numeric))
+
+
+def _load_interp_map(interp_map_path):
+    """run_eda_pipeline's loading of the pickled {file name: interpolation name} map, with its two messages."""
+    if interp_map_path and os.path.exists(interp_map_path):
+        try:
+            import pickle
+            with open(interp_map_path, "rb") as f:
+                return pickle.load(f)
+        except Exception as e:
+            print(f"Warning: could not load interpolation map: {e}")
+            return None
+    print("Interpolation map not found; default interpolation will be used.")
+    return None
+
+
+def run_eda_panels(lr_dir, hr_dir, top_k_examples=1, glcm_multi_angle=False, glcm_levels=64, interp_map_path="", rank_by="lpips"):
+    """run_eda_pipeline without the files -> (df, panels).  panels: 'advanced_global_panel', 'distributions',
+    'artifact_color_histograms', 'artifact_boxplots', 'channel_shape_bars', 'correlation_matrix', 'scatter_relations' (the numeric
+    methods above on collect's rows) and 'examples': {'{label}_scenarios/{parent}/{label}_{rank}_{stem}': visual_example,
+    '.../{label}_{rank}_advanced_{stem}': advanced_panel} for the best and worst top_k_examples rows by `rank_by` (ascending, stable,
+    NaN last; the reference ranks by lpips).  Example pairs of one size go through the device as one batch."""
+    if rank_by == "lpips" and ImageDatasetAnalyzer._lpips_ctx is None:
+        raise NotImplementedError("run_eda_panels: ranking by lpips needs the LPIPS weights: call ImageDatasetAnalyzer.load_lpips(alexnet_path, "
+                                  "lpips_path) first, or rank by another column (rank_by='psnr')")
+    interp_map = _load_interp_map(interp_map_path)
+    rows, global_data = MetricsAggregator.collect(lr_dir, hr_dir, glcm_multi_angle=glcm_multi_angle, glcm_levels=glcm_levels, interp_map=interp_map)
+    df = StatsReporter.dataframe(rows)
+    V = ImageDataVisualization
+    panels = {"advanced_global_panel": V.global_advanced_panel(global_data), "distributions": V.basic_distributions_data(df),
+              "artifact_color_histograms": V.artifact_color_histograms_data(df), "artifact_boxplots": V.artifact_boxplots_data(df),
+              "channel_shape_bars": V.channel_shape_bars_data(df), "correlation_matrix": V.correlation_matrix_data(df),
+              "scatter_relations": V.scatter_relations_data(df), "examples": {}}
+    if rank_by not in df or np.asarray(df[rank_by]).dtype.kind != "f":
+        raise ValueError(f"run_eda_panels: rank_by {rank_by!r} is not a numeric column of the frame")
+    vals = np.asarray(df[rank_by], dtype=np.float64)
+    order = np.argsort(vals, kind="stable")
+    k = min(max(int(top_k_examples), 0), vals.size)
+    names = [str(f) for f in df["filename"]]
+    picked = []                                      # (visual key, advanced key, lr, hr)
+    for label, idx in (("best", order[:k]), ("worst", order[vals.size - k:])):
+        for rank, i in enumerate(idx, 1):
+            rel = names[i]
+            lr, hr = ImagePairLoader.load_and_align(os.path.join(lr_dir, rel), os.path.join(hr_dir, rel), interp_map=interp_map)
+            rel_no_ext = os.path.splitext(rel.replace("\\", "/"))[0]
+            parent, stem = os.path.dirname(rel_no_ext), os.path.basename(rel_no_ext)
+            base = f"{label}_scenarios/{parent}/" if parent else f"{label}_scenarios/"
+            picked.append((f"{base}{label}_{rank}_{stem}", f"{base}{label}_{rank}_advanced_{stem}", lr, hr))
+    by_shape = {}
+    for n, p in enumerate(picked):
+        by_shape.setdefault(p[3].shape, []).append(n)
+    adv = [None] * len(picked)
+    for members in by_shape.values():
+        res = V.advanced_panels(np.stack([picked[n][2] for n in members]), np.stack([picked[n][3] for n in members]))
+        for n, r in zip(members, res):
+            adv[n] = r
+    for (vis_key, adv_key, lr, hr), a in zip(picked, adv):
+        panels["examples"][vis_key] = {"lr_rgb": np.ascontiguousarray(lr[..., ::-1]), "hr_rgb": np.ascontiguousarray(hr[..., ::-1]), "diff_gray": a.pop("diff_gray")}
+        panels["examples"][adv_key] = a
+    return df, panels
+
+
+PANEL_NAMES = ("advanced_global_panel", "distributions", "artifact_color_histograms", "artifact_boxplots", "channel_shape_bars", "correlation_matrix",
+               "scatter_relations")
+
+
+def run_eda_pipeline(lr_dir, hr_dir, output_dir="eda_results", top_k_examples=1, glcm_multi_angle=False, glcm_levels=64, interp_map_path="", rank_by="lpips"):
+    """The notebook's last cell: the reference's signature (rank_by is this port's addition, for a run without the LPIPS weights) and its
+    return value, df.  Where the reference saves a .png, the panel's numbers are written as an .npz of the same stem (flatten_panel's
+    names): advanced_global_panel.npz, distributions.npz, artifact_color_histograms.npz, artifact_boxplots.npz, channel_shape_bars.npz,
+    correlation_matrix.npz, scatter_relations.npz, LPIPS_Scenarios/{best,worst}_scenarios/<parent>/{label}_{rank}[_advanced]_{stem}.npz.
+    A panel the reference skips (None) writes no file."""
+    df, panels = run_eda_panels(lr_dir, hr_dir, top_k_examples, glcm_multi_angle, glcm_levels, interp_map_path, rank_by)
+    examples_dir = os.path.join(output_dir, "LPIPS_Scenarios")
+    for d in (output_dir, os.path.join(examples_dir, "best_scenarios"), os.path.join(examples_dir, "worst_scenarios")):
+        os.makedirs(d, exist_ok=True)
+    files = [(os.path.join(output_dir, key), panels[key]) for key in PANEL_NAMES]
+    files += [(os.path.join(examples_dir, *key.split("/")), p) for key, p in panels["examples"].items()]
+    for path, panel in files:
+        flat = ImageDataVisualization.flatten_panel(panel)
+        if not flat:
+            continue
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        np.savez(path + ".npz", **flat)
+    return df

@@ -124,6 +124,7 @@ SIGNATURES = {
     "sr_ssim_map": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "sr_eda_pair_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_eda_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sr_eda_pair_panels": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sr_degrade_gauss": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sr_degrade_motion": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "sr_degrade_noise": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),

@@ -476,6 +476,32 @@ class Context:
                                               acc["grad_hr_sum"].data_ptr(), acc["glcm_sum"].data_ptr(), acc["sat_counts"].data_ptr(), self.stream()))
         return acc
 
+    EDA_PANEL_OUTPUTS = ("spec_lr", "spec_hr", "grad_hr", "glcm_lr", "noise_lr", "diff", "sat_hist", "glcm_contrast", "noise_mean")
+
+    def eda_pair_panels(self, lr, hr, which=None):
+        """The maps of the EDA's per-pair panels (sr_eda_pair_panels), unsummed -> dict of device tensors: 'spec_lr', 'spec_hr' float64
+        [B,H,W] (|fftshift(fft2(gray))|, the magnitude: the panel's log is the caller's), 'grad_hr', 'noise_lr' float64 [B,H,W], 'glcm_lr'
+        float64 [B,256,256], 'diff' uint8 [B,H,W], 'sat_hist' int64 [B,2,256] (lr, hr), 'glcm_contrast', 'noise_mean' float64 [B].
+        which: the names wanted (None: all); the others are neither computed nor returned."""
+        B, H, W = self._eda_pair(lr, hr, "eda_pair_panels")
+        names = self.EDA_PANEL_OUTPUTS if which is None else tuple(which)
+        unknown = [k for k in names if k not in self.EDA_PANEL_OUTPUTS]
+        if unknown or not names:
+            raise ValueError(f"eda_pair_panels: which names outputs among {self.EDA_PANEL_OUTPUTS}, got {list(names)}")
+        shapes = {"spec_lr": ((B, H, W), torch.float64), "spec_hr": ((B, H, W), torch.float64), "grad_hr": ((B, H, W), torch.float64),
+                  "glcm_lr": ((B, 256, 256), torch.float64), "noise_lr": ((B, H, W), torch.float64), "diff": ((B, H, W), torch.uint8),
+                  "sat_hist": ((B, 2, 256), torch.int64)}
+        out = {k: self.empty(*shapes[k]) for k in shapes if k in names}
+        scalars = self.empty((B, 2), torch.float64) if ("glcm_contrast" in names or "noise_mean" in names) else None
+        ptr = (lambda k: out[k].data_ptr() if k in out else None)
+        self.check(self.lib.sr_eda_pair_panels(self.h, lr.data_ptr(), hr.data_ptr(), B, H, W, ptr("spec_lr"), ptr("spec_hr"), ptr("grad_hr"), ptr("glcm_lr"),
+                                               ptr("noise_lr"), ptr("diff"), ptr("sat_hist"), None if scalars is None else scalars.data_ptr(),
+                                               self.stream()))
+        for j, k in enumerate(("glcm_contrast", "noise_mean")):           # SR_EDA_PANEL_* order
+            if k in names:
+                out[k] = scalars[:, j].contiguous()
+        return out
+
     # ------------------------------------------------------------------ LPIPS (data/EDA.ipynb lpips_score; csrc/lpips.hip)
     def lpips_set_weights(self, weights):
         """Sets (a dict from sr355.lpips.load_weights / seeded_weights) or, with None, unloads the weights of lpips / sr_lpips on this context.
