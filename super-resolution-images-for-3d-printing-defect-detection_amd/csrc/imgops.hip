@@ -260,6 +260,22 @@ __global__ void __launch_bounds__(256) bicubic_f32_tile_kernel(const float* x, i
     }
 }
 
+// The uint8 path rounds each weight to an 11-bit integer, so a weight one ulp off flips that integer where w * 2048 lies next to a half:
+// the weights must be the bits cv2 computes, every operation of interpolateCubic rounded on its own.  Left to the compiler, cubic_w's
+// polynomials are contracted into fmas -- harmless to the float kernels (2e-6), but one output position in 837 then took another integer tap.
+__device__ __forceinline__ void cubic_axis_rounded(int d, double scale, int n, int idx[4], float w[4]) {
+#pragma clang fp contract(off)
+    const float f = (float)(((double)d + 0.5) * scale - 0.5);
+    const int s = (int)floorf(f);
+    const float x = f - (float)s, A = -0.75f;
+    w[0] = ((A * (x + 1.f) - 5.f * A) * (x + 1.f) + 8.f * A) * (x + 1.f) - 4.f * A;
+    w[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+    w[2] = ((A + 2.f) * (1.f - x) - (A + 3.f)) * (1.f - x) * (1.f - x) + 1.f;
+    w[3] = 1.f - w[0] - w[1] - w[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) idx[k] = min(max(s - 1 + k, 0), n - 1);
+}
+
 __global__ void bicubic_u8_kernel(const uint8_t* x, int B, int H, int W, int C, int oH, int oW, double sy, double sx, uint8_t* y) {
     const int64_t n = (int64_t)B * oH * oW;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -268,8 +284,8 @@ __global__ void bicubic_u8_kernel(const uint8_t* x, int B, int H, int W, int C, 
         const int b = (int)(i / ((int64_t)oW * oH));
         int ix[4], iy[4], iwx[4], iwy[4];
         float wx[4], wy[4];
-        cubic_axis(ox, sx, W, ix, wx);
-        cubic_axis(oy, sy, H, iy, wy);
+        cubic_axis_rounded(ox, sx, W, ix, wx);
+        cubic_axis_rounded(oy, sy, H, iy, wy);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             iwx[k] = min(max((int)rintf(wx[k] * 2048.f), -32768), 32767);

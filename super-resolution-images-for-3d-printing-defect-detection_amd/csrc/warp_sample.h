@@ -8,25 +8,30 @@
 
 constexpr int WARP_PRM = 16;          // per image: hi(a00 a01 a10 a11 o0 o1), lo(same), flip, 3 unused
 
+// The error-free transformations below hold only if every operation is rounded on its own.  __fmul_rn / __fadd_rn are plain operators to the
+// compiler, which had fused the products into the sums that follow them (s - h * u as one fma): the sum's error term then no longer belongs to
+// the rounded product, and the coordinate was off by half an ulp of its magnitude -- 3e-5 of a pixel at 592 pixels, within the tests' bound
+// at 128.  Contraction is therefore switched off for the operators written here; the two fmas that are meant are spelled out.
 __device__ __forceinline__ void two_sum(float a, float b, float& s, float& e) {
-    s = __fadd_rn(a, b);
-    const float bb = __fsub_rn(s, a);
-    e = __fadd_rn(__fsub_rn(a, __fsub_rn(s, bb)), __fsub_rn(b, bb));
+#pragma clang fp contract(off)
+    s = a + b;
+    const float bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
 }
 
 // ah * u + bh * v + oh (+ the lo halves) for integer u, v -> floor and fraction in [0, 1)
 __device__ __forceinline__ void coord(const float* h, const float* l, int k, float u, float v, int lim, int& i0, float& t) {
-    const float p1 = __fmul_rn(h[2 * k], u), e1 = __fmaf_rn(h[2 * k], u, -p1);
-    const float p2 = __fmul_rn(h[2 * k + 1], v), e2 = __fmaf_rn(h[2 * k + 1], v, -p2);
+#pragma clang fp contract(off)
+    const float p1 = h[2 * k] * u, e1 = __fmaf_rn(h[2 * k], u, -p1);
+    const float p2 = h[2 * k + 1] * v, e2 = __fmaf_rn(h[2 * k + 1], v, -p2);
     float s, t1, s2, t2;
     two_sum(p1, p2, s, t1);
     two_sum(s, h[4 + k], s2, t2);
-    const float lo = __fadd_rn(__fadd_rn(__fadd_rn(t1, t2), __fadd_rn(e1, e2)),
-                               __fadd_rn(__fadd_rn(__fmul_rn(l[2 * k], u), __fmul_rn(l[2 * k + 1], v)), l[4 + k]));
+    const float lo = ((t1 + t2) + (e1 + e2)) + ((l[2 * k] * u + l[2 * k + 1] * v) + l[4 + k]);
     float f = floorf(s2);
-    float fr = __fadd_rn(__fsub_rn(s2, f), lo);
-    if (fr < 0.f) { f = __fsub_rn(f, 1.f); fr = __fadd_rn(fr, 1.f); }
-    if (fr >= 1.f) { f = __fadd_rn(f, 1.f); fr = __fsub_rn(fr, 1.f); }
+    float fr = (s2 - f) + lo;
+    if (fr < 0.f) { f = f - 1.f; fr = fr + 1.f; }
+    if (fr >= 1.f) { f = f + 1.f; fr = fr - 1.f; }
     f = fminf(fmaxf(f, -1.f), (float)lim);          // beyond the border both taps clamp to the edge; keeps the int conversion in range
     i0 = (int)f;
     t = fr;
