@@ -108,8 +108,15 @@ int64_t sr_debug_stamp_bytes_needed(int which, int64_t workgroups);
  * up-sampling convs, EDSR's body) on a persistent kernel that keeps a 64-cout tile's weights in LDS; bit 8 = SRCNN's 1x1 conv (conv2d_1, 96 -> 32, ReLU:
  * SRCNN_model.py:51) computed from the accumulators in the epilogue of the 9x9 head, whose 96-channel fp32 output is then never stored; default 511.
  * mask 0 = layer by layer (the A/B switch of the parity tests and of tools/ benchmarks).  max_workgroups > 0 caps the persistent grid (tests: several images per workgroup
- * at small batches); 0 = one workgroup per CU. */
+ * at small batches); 0 = one workgroup per CU.
+ * At 8 growth channels (bf16; the reference notebook's generator) bits 0, 1 and 5 together -- the bits that mean "the whole dense block on fused kernels" -- run every
+ * dense block as ONE kernel whose 96-channel concat tensor lives in LDS (dense_block_lds<bf16,g8>), for every image sr_dense_block_lds_bytes accepts (24 x 24 patches
+ * among them); without one of the three, or for a larger image, the block runs conv by conv as before.  max_workgroups caps that kernel's grid too. */
 int  sr_debug_set_fused(sr_ctx* ctx, int mask, int max_workgroups);
+/* Dynamic LDS bytes the LDS-resident dense-block kernel needs for one H x W image of a generator with `growth_channels` growth channels (the padded (H + 2) x (W + 2)
+ * image of 96 bf16 channels, in whole 256-byte bank rows per 8-channel plane), or -1 where that kernel does not apply: growth_channels != 8, H or W < 1, or more than
+ * the 160 KiB of a CU.  Every H, W with (H + 2)(W + 2) <= 676 fits.  Pure function, no context: sr_forward's router and the kernel's launcher both ask it. */
+int64_t sr_dense_block_lds_bytes(int growth_channels, int H, int W);
 /* The bits of sr_debug_set_fused's mask, as described above.  SR_FUSE_TWO_UP: the bits the two-up packing of 24-pixel-wide images needs. */
 enum { SR_FUSE_DENSE_TAIL = 1, SR_FUSE_DENSE_MID = 2, SR_FUSE_RGB_TAIL = 4, SR_FUSE_ATTN_PROJ = 8, SR_FUSE_CELLS = 16, SR_FUSE_CONV1_STREAM = 32,
        SR_FUSE_POOL = 64, SR_FUSE_CONV_STREAM = 128, SR_FUSE_SRCNN_1X1 = 256, SR_FUSE_ALL = 511,

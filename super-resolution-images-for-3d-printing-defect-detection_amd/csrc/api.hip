@@ -122,6 +122,7 @@ struct Op {
     int pack_alt = -1;                              // conv (ESRGAN trunk_conv): a free row-blocked buffer the two-up packed trunk output is unpacked into (sr_forward, 24-pixel-wide patches)
     int pw2 = -1;                                   // conv: the next op is the 1x1 conv m->pw2s[pw2], which this fp32 thin conv's epilogue can compute from its accumulators
     int proj = -1;                                  // conv: the next op is the 1x1 projection m->projs[proj], which this conv's epilogue can compute
+    int block = -1, block_pos = 0;                  // conv: conv block_pos + 1 of the dense block m->blocks[block], which can run as one LDS-resident kernel
 };
 struct BufSpec { int C = 0; int mul = 1; int shift = 0; bool vec = false; int Cbuf = 0; int blk = 0; int cshift = 0; int cells = 0; int cat = 0; };   // vec: fp32 [B,C]; blk: row-blocked (conv_common.h); shift: floor halvings (pooling), cshift: ceil halvings (stride-2 SAME convs); cells: small images may be packed in a CellGrid (common.h)
 struct ConvPart { std::string name; int cout; float scale = 1.f; };   // scale: applied to kernel and bias when the conv is packed
@@ -130,6 +131,8 @@ struct ConvSpec { std::vector<ConvPart> parts; int KS = 3, Cin = 0, Cout = 0; Co
 struct ChainSpec { int conv_a = -1, conv_b = -1; int tail = 0; ChainWeights w; };
 // a 64-cout 3x3 conv followed by the 3x3 conv to the image's <= 3 channels: one kernel + a finishing pass when the shape allows (conv_rows.hip)
 struct RgbTailSpec { int conv_b = -1; RgbTailWeights w; };
+// the five convs of a dense block at 8 growth channels: one LDS-resident kernel when the image fits (dense_block.hip): ops[first .. first + 4]
+struct BlockSpec { int conv[5] = {-1, -1, -1, -1, -1}; BlockWeights w; };
 // the f / g / h projections of a SelfAttention layer, computed in the epilogue of the conv that produces the layer's input (conv_rows.hip)
 struct ProjSpec { int conv = -1; ProjWeights w; };
 struct Pw2Spec { int conv = -1; int act = 0; Pw2Weights w; };
@@ -144,6 +147,7 @@ struct sr_model {
     std::vector<Param> params;
     std::vector<ConvSpec> convs;
     std::vector<ChainSpec> chains;
+    std::vector<BlockSpec> blocks;
     std::vector<RgbTailSpec> rgbtails;
     std::vector<ProjSpec> projs;
     std::vector<Pw2Spec> pw2s;
@@ -326,6 +330,16 @@ int build_esrgan(sr_model* m) {
                 };
                 link(first_op + 1, 0);
                 link(first_op + 3, 1);
+            }
+            if (m->bufs[I].blk && G == 8) {
+                // row-blocked buffers, 8 growth channels (the reference notebook's generator): the 96-channel concat tensor of a small image fits the LDS of a
+                // CU, and the whole block can run as one kernel (dense_block.hip); sr_forward decides per call and otherwise runs the ops one by one
+                BlockSpec bs;
+                for (int k = 0; k < 5; ++k) {
+                    bs.conv[k] = m->ops[first_op + k].conv;
+                    m->ops[first_op + k].block = (int)m->blocks.size(); m->ops[first_op + k].block_pos = k;
+                }
+                m->blocks.push_back(bs);
             }
         }
         const int nX = Y, nY = Z, nZ = X; X = nX; Y = nY; Z = nZ;
@@ -510,6 +524,13 @@ struct Layout {
     int B_ws = 0;            // the batch the workspace is sized for
 };
 
+// the dense blocks of this forward run as one LDS-resident kernel each (dense_block.hip): the model has them packed (bf16, 8 growth channels, row-blocked concat
+// buffers), the mask holds the three bits that mean "the whole dense block on fused kernels", and an image of the concat buffers fits the LDS
+bool block_here(const sr_model* m, int H, int W) {
+    return m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && !m->blocks.empty() && (m->ctx->chain_mask & SR_FUSE_TWO_UP) == SR_FUSE_TWO_UP &&
+           sr_dense_block_lds_bytes(m->cfg.growth_channels, H, W) > 0;
+}
+
 Layout choose_layout(const sr_model* m, int B, int H, int W) {
     const int mask = m->ctx->chain_mask;
     Layout L;
@@ -525,7 +546,7 @@ Layout choose_layout(const sr_model* m, int B, int H, int W) {
     bool cat_blk = false; int Cmax = 0;
     for (const BufSpec& bs : m->bufs) if (bs.cat) { cat_blk = cat_blk || bs.blk; Cmax = std::max(Cmax, bs.Cbuf); }
     const bool fused_here = !m->chains.empty() && W == 48 && (mask & (SR_FUSE_DENSE_TAIL | SR_FUSE_DENSE_MID));
-    if (m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && cat_blk && !L.pack2 && !fused_here && m->taps.empty()) L.cat = cat_grid_for(B, H, W, Cmax);
+    if (m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && cat_blk && !L.pack2 && !fused_here && !block_here(m, H, W) && m->taps.empty()) L.cat = cat_grid_for(B, H, W, Cmax);
     L.B_ws = L.pack2 ? (B + 1) & ~1 : L.cat.gx ? (int)std::max<int64_t>(B, ((int64_t)L.cat.Hv * L.cat.Wv + (int64_t)H * W - 1) / ((int64_t)H * W)) : B;
     return L;
 }
@@ -576,8 +597,9 @@ int ensure_workspace(sr_model* m, const Layout& L, int H, int W, hipStream_t st)
 }
 
 // ---- the route of every op in one forward: its own kind (OP_CONV: a conv, possibly with the next op in its epilogue), or a fused route --------
-// (CHAIN: a dense-block pair as one kernel, launched at its first conv; CHAIN_SECOND: that pair's second conv; IN_EPILOGUE: computed by the conv in front of it)
-enum Route { RT_CHAIN = OP_PREPROC + 1, RT_CHAIN_SECOND, RT_CONV1_STREAM, RT_RGB_TAIL, RT_PW2, RT_IN_EPILOGUE };
+// (CHAIN: a dense-block pair as one kernel, launched at its first conv; CHAIN_SECOND: that pair's second conv; BLOCK: a whole dense block as one kernel, launched
+//  at its conv1; BLOCK_REST: that block's conv2 .. conv5; IN_EPILOGUE: computed by the conv in front of it)
+enum Route { RT_CHAIN = OP_PREPROC + 1, RT_CHAIN_SECOND, RT_BLOCK, RT_BLOCK_REST, RT_CONV1_STREAM, RT_RGB_TAIL, RT_PW2, RT_IN_EPILOGUE };
 
 bool tapped(const sr_model* m, size_t oi) { return !m->taps.empty() && m->taps.count((int)oi) != 0; }
 // no skips, no clip, no depth_to_space
@@ -624,7 +646,7 @@ bool proj_fits(const sr_model* m, const Op& op) {
            op.out.buf >= 0 && !m->bufs[op.out.buf].blk && op.skip2.buf < 0 && !op.clip && op.act != SR_ACT_TANH && m->bufs[op.out.buf].Cbuf % 4 == 0;
 }
 
-// After ensure_workspace (the RGB tail's check reads bufcap, the pool's grid_now): m->routes.  Precedence: a fused pair, conv1's streaming kernel, (the
+// After ensure_workspace (the RGB tail's check reads bufcap, the pool's grid_now): m->routes.  Precedence: a whole dense block, a fused pair, conv1's streaming kernel, (the
 // input unpack of trunk_conv, at launch), the RGB tail, SRCNN's fused 1x1, else the conv -- with a max-pool or projection behind it in its epilogue where that fits.
 void plan_routes(sr_model* m, const Layout& L, int B, int H, int W) {
     std::vector<int>& rt = m->routes;
@@ -635,7 +657,8 @@ void plan_routes(sr_model* m, const Layout& L, int B, int H, int W) {
         if (rt[oi] != OP_CONV) continue;                                      // not a conv, or one the conv in front of it has taken
         int h, w;
         buf_hw(m->bufs[op.in.buf], H, W, &h, &w);
-        if (chain_fits(m, oi, w, L.pack2)) { rt[oi] = RT_CHAIN; rt[oi + 1] = RT_CHAIN_SECOND; }
+        if (op.block >= 0 && op.block_pos == 0 && block_here(m, h, w)) { rt[oi] = RT_BLOCK; for (int k = 1; k < 5; ++k) rt[oi + k] = RT_BLOCK_REST; }
+        else if (chain_fits(m, oi, w, L.pack2)) { rt[oi] = RT_CHAIN; rt[oi + 1] = RT_CHAIN_SECOND; }
         else if (conv1_stream_fits(m, op, w, L.pack2)) rt[oi] = RT_CONV1_STREAM;
         else if (rgb_tail_fits(m, op, oi, B, h, w)) { rt[oi] = RT_RGB_TAIL; rt[oi + 1] = RT_IN_EPILOGUE; }
         else if (pw2_fits(m, op, oi)) { rt[oi] = RT_PW2; rt[oi + 1] = RT_IN_EPILOGUE; }
@@ -824,6 +847,7 @@ void sr_model_destroy(sr_model* m) {
     m->free_bufs();
     for (auto& c : m->convs) conv_free_weights(m->ctx, &c.w);
     for (auto& ch : m->chains) chain_free_weights(m->ctx, &ch.w);
+    for (auto& bs : m->blocks) block_free_weights(m->ctx, &bs.w);
     for (auto& rt : m->rgbtails) rgbtail_free_weights(m->ctx, &rt.w);
     for (auto& pj : m->projs) proj_free_weights(m->ctx, &pj.w);
     for (auto& pw : m->pw2s) pw2_free_weights(m->ctx, &pw.w);
@@ -947,6 +971,14 @@ int sr_model_finalize(sr_model* m) {
         int rc = chain_pack_weights(ctx, ka.data(), ba.data(), kb.data(), bb.data(), a.Cin / 32, a.Cout / 16, bq.Cout / 16, &ch.w);
         if (rc) return rc;
     }
+    for (auto& bs : m->blocks) {
+        block_free_weights(ctx, &bs.w);
+        std::vector<float> k[5], bias[5];
+        const float* kp[5]; const float* bp[5];
+        for (int i = 0; i < 5; ++i) { gather(m->convs[bs.conv[i]], k[i], bias[i]); kp[i] = k[i].data(); bp[i] = bias[i].data(); }
+        int rc = block_pack_weights(ctx, kp, bp, &bs.w);
+        if (rc) return rc;
+    }
     for (auto& rt : m->rgbtails) {
         rgbtail_free_weights(ctx, &rt.w);
         const ConvSpec& c2 = m->convs[rt.conv_b];
@@ -1025,8 +1057,19 @@ int sr_forward(sr_model* m, const void* x, int io_dtype, int B, int H, int W, in
         const TensorView vi = m->view(op.in), vo = m->view(op.out);
         void* const po = op.out.buf >= 0 ? m->bufp[op.out.buf] : nullptr;
         switch (route) {
-            case RT_CHAIN_SECOND: case RT_IN_EPILOGUE:                        // launched with the op in front of it (a tap reads its output below)
+            case RT_CHAIN_SECOND: case RT_BLOCK_REST: case RT_IN_EPILOGUE:    // launched with the op in front of it (a tap reads its output below)
                 break;
+            case RT_BLOCK: {
+                const Op& o5 = m->ops[oi + 4];
+                // which skip of conv5 is the block's own input (in LDS), which the other tensor (the RRDB's input, from memory)
+                const bool x1 = o5.skip1.buf == op.in.buf && o5.skip1.coff == 0;
+                const Ref& other = x1 ? o5.skip2 : o5.skip1;
+                bool grow = false;                                            // a tapped growth conv needs its slice in memory
+                for (int k = 0; k < 4; ++k) grow = grow || tapped(m, oi + k);
+                rc = block_launch(ctx, m->blocks[op.block].w, vi, B, h, w, m->view(o5.out), other.buf >= 0 ? m->view(other) : TensorView{}, o5.alpha, o5.beta1, o5.beta2,
+                                  x1 ? 1 : 2, grow ? 1 : 0, st);
+                break;
+            }
             case RT_CHAIN: {
                 const ChainSpec& ch = m->chains[op.chain];
                 const Op& ob = m->ops[oi + 1];

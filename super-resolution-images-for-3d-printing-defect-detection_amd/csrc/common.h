@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -273,6 +274,19 @@ int cell_pack_launch(sr_ctx* ctx, const void* src, int64_t src_cs, int src_coff,
 int cell_unpack_launch(sr_ctx* ctx, const void* src, int64_t src_C, int src_coff, int B, int H, int W, int C, void* dst, int64_t dst_C, int dst_coff, const CellGrid& g, hipStream_t st);
 int chain_launch(sr_ctx* ctx, const ChainWeights& w, TensorView in, int B, int H, int W, TensorView out, TensorView skip_o, float alpha, float beta_x,
                  float beta_o, hipStream_t st, bool seam = false);
+
+// ---------------------------------------------------------------------------------------------
+// a whole dense block at 8 growth channels as one LDS-resident kernel (dense_block.hip)
+// ---------------------------------------------------------------------------------------------
+struct BlockWeights { void* w = nullptr; float* bias = nullptr; size_t bytes = 0; };
+// k[i], b[i]: HWIO kernel and bias of conv i + 1 of the block
+int block_pack_weights(sr_ctx* ctx, const float* const k[5], const float* const b[5], BlockWeights* out);
+static inline void block_free_weights(sr_ctx* ctx, BlockWeights* w) { weights_free(ctx, w->w, w->bias); }
+// in / out / skip_o: row-blocked 96-channel concat buffers, out != in.  out[0:64) = alpha * (conv5 + b) + beta1 * skip1 + beta2 * skip2, where skip
+// x_skip (1 / 2) is in[0:64) and the other one skip_o (none: x_skip = 1, beta2 unused).  store_growth: also write conv1 .. conv4 to in[64:96) (taps).
+// The image must fit: sr_dense_block_lds_bytes(8, H, W) > 0.
+int block_launch(sr_ctx* ctx, const BlockWeights& w, TensorView in, int B, int H, int W, TensorView out, TensorView skip_o, float alpha, float beta1,
+                 float beta2, int x_skip, int store_growth, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // attention core: o = softmax(q k^T) v per image, tokens N=H*W.

@@ -67,6 +67,7 @@ SIGNATURES = {
     "sr_measure_clock": (_i, [_vp, _fp, _vp]),
     "sr_debug_set_chain_stamp_buffer": (_i, [_vp, _vp, _i64]),
     "sr_debug_set_fused": (_i, [_vp, _i, _i]),
+    "sr_dense_block_lds_bytes": (_i64, [_i, _i, _i]),
     "sr_debug_set_alloc_cap": (_i, [_vp, _i64]),
     "sr_debug_conv_routes": (_i, [_vp, _i, C.c_char_p, _i64]),
     "sr_profile_begin": (_i, [_vp]),

@@ -137,8 +137,15 @@ class Context:
         SelfAttention's f / g / h projections in the epilogue of the conv before it; FUSED_CELLS: batches of small images (VGG16 block 5) packed into one
         tall image with zero separators; FUSED_CONV1_STREAM: conv1 of a dense block on the streaming line-buffer kernel; FUSED_POOL: a 2x2 max-pool inside
         the epilogue of the conv in front of it; FUSED_CONV_STREAM: 3x3 convs from 64 input channels on the persistent kernel with resident weights;
-        FUSED_SRCNN_1X1: SRCNN's 1x1 conv in the 9x9 head's epilogue.  FUSED_ALL (the default): all of them; 0 = layer by layer."""
+        FUSED_SRCNN_1X1: SRCNN's 1x1 conv in the 9x9 head's epilogue.  FUSED_ALL (the default): all of them; 0 = layer by layer.
+        At 8 growth channels (bf16) the three FUSED_TWO_UP bits together run every dense block as one LDS-resident kernel, dense_block_lds<bf16,g8>, for
+        every image dense_block_lds_bytes accepts (24 x 24 patches among them); max_workgroups caps that kernel's persistent grid as well."""
         self.check(self.lib.sr_debug_set_fused(self.h, int(mask), int(max_workgroups)))
+
+    @staticmethod
+    def dense_block_lds_bytes(growth_channels, H, W):
+        """Dynamic LDS bytes the LDS-resident dense-block kernel needs for an H x W image, or -1 where it does not apply (sr_dense_block_lds_bytes)."""
+        return int(L.load().sr_dense_block_lds_bytes(int(growth_channels), int(H), int(W)))
 
     def set_alloc_cap(self, nbytes):
         """Test hook: allocations through this context fail once it would hold more than nbytes (0 = no cap)."""
