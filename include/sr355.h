@@ -214,6 +214,11 @@ int  sr_spectral_l1(sr_ctx* ctx, const void* a, const void* b, int B, int H, int
  * sr_space_to_depth: the inverse of tf.nn.depth_to_space (DCR order): x [B,H*r,W*r,C] -> y [B,H,W,r*r*C] (its gradient). */
 int  sr_conv2d_wgrad(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, int K,
                      float* dw_hwio, float* db, void* stream);
+/* sr_conv2d_wgrad for 3x3 layers on maps of at most 8 x 8 pixels (H <= 8, W <= 8; block5 of a fine-tuned VGG16 on 128-pixel patches): the same
+ * kernel scheme and summation structure, on staged tiles that hold 27 / (W + 1) images side by side (one shared zero column between neighbours)
+ * instead of one image in an 8 x 24 tile.  Deterministic; not bit-identical to sr_conv2d_wgrad (the pixels meet in another order). */
+int  sr_conv2d_wgrad_maps(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, float* dw_hwio, float* db,
+                          void* stream);
 /* sr_conv2d with DEVICE fp32 weights (the training loop keeps its parameters on the device between optimiser steps): d_w is a device
  * HWIO tensor [K,K,Cin,Cout]; with rot = 1 it is instead the forward kernel [K,K,Cout,Cin] of the layer whose INPUT gradient is wanted,
  * and the conv runs on its 180-degree-rotated, channel-swapped form (ESRGAN_model.py:505-533 via tf.GradientTape).  The kernel is packed
@@ -557,6 +562,19 @@ int64_t sr_dense_head_workspace_bytes(int n, int num_classes);
 int  sr_dense_head_step(sr_ctx* ctx, const float* feats, int n, int in_dim, int hidden, int num_classes, const int32_t* labels,
                         const uint8_t* keep0, const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads,
                         double* stats, void* work, int64_t work_bytes, void* stream);
+/* Fine-tuning of the conv base's last layers (FineTunedVGG16.setup_model(fine_tune_base=True)): the head step that also returns the gradient
+ * at its input, and the backward pass of block5_pool + GlobalAveragePooling2D down to the last conv's pre-activation.
+ * sr_dense_head_step_dx: sr_dense_head_step as a training step (grads required) plus dfeats DEVICE fp32 [n,512] = d loss / d feats =
+ *   (dz1 k1^T) times the keep0 mask and keep_scale.  grads and stats are the bits sr_dense_head_step writes for the same inputs (the same two
+ *   kernels run; a third writes dfeats, its 256-term sums in index order).  params must be 16-byte aligned; n <= 524280.
+ * sr_pool_gap_bwd: a DEVICE fp32 [B,H,W,C] the ReLU output of the conv in front of MaxPooling2D(2,2) + GlobalAveragePooling2D, dfeats DEVICE
+ *   fp32 [B,C] -> dz DEVICE fp32 [B,H,W,C]: per 2x2 window (floor: an odd last row / column gets zero) dfeats[b,c] / ((H/2)(W/2)) goes to the
+ *   first maximum in the order (0,0) (0,1) (1,0) (1,1) -- sr_maxpool2_bwd's rule -- where a > 0, every other element is zero.  Bit for bit the
+ *   spread, sr_maxpool2_bwd and SR_ELT_RELU_BWD in sequence.  H, W >= 2.  16-byte accesses when C is a multiple of 4 and the pointers allow. */
+int  sr_dense_head_step_dx(sr_ctx* ctx, const float* feats, int n, int in_dim, int hidden, int num_classes, const int32_t* labels,
+                           const uint8_t* keep0, const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads,
+                           float* dfeats, double* stats, void* work, int64_t work_bytes, void* stream);
+int  sr_pool_gap_bwd(sr_ctx* ctx, const float* a, const float* dfeats, int B, int H, int W, int C, float* dz, void* stream);
 
 /* ---- the discriminator's update inside ESRGAN._train_step besides its convs (reference ESRGAN_model.py:347-377, :475-533), csrc/disc_train.hip ----
  * sr_spectral_norm_bucket: tfa SpectralNormalization.normalize_weights, one power iteration, of n_layers kernels IN PLACE where they lie in a

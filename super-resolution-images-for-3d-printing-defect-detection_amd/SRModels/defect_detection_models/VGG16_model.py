@@ -28,7 +28,12 @@ class FineTunedVGG16(DeviceModelMixin):
 
     def setup_model(self, input_shape=(128, 128, 3), num_classes=2, train_last_n_layers=4, base_trainable=False, dropout_rate=0.2,
                     l2_reg=0.0, learning_rate=1e-3, loss="sparse_categorical_crossentropy", from_pretrained=False,
-                    pretrained_path=None):
+                    pretrained_path=None, fine_tune_base=False):
+        """VGG16_model.py:29-109.  fine_tune_base (not in the reference; default False = the reference's head-only training, whatever
+        base_trainable says, see below): True makes `fit` train, with the two Dense layers and under the same Adam, the convs among the last
+        `train_last_n_layers` of the base's 19 Keras layers (input_1, 13 convs, 5 pools in graph order: 4 -> block5_conv1..3, 6 -> those and
+        block4_conv3, 1 -> none, i.e. head-only, >= 18 -> all 13; sr355.vgg_train.vgg16_tail_convs) -- what the reference's flags read like and
+        never do.  `base_trainable` is not consulted by this flag."""
         assert input_shape[-1] == 3, "Input must have 3 channels (RGB)."
         self.input_shape = tuple(input_shape)
         weights = load_pretrained(pretrained_path) if from_pretrained else None
@@ -41,6 +46,7 @@ class FineTunedVGG16(DeviceModelMixin):
         # layers (VGG16.ipynb:L152,L161-165).  So both arguments are accepted and recorded, and training is the
         # same head-only training in either case -- the reference's behaviour, not its apparent intent.
         self.base_trainable, self.train_last_n_layers = bool(base_trainable), int(train_last_n_layers)
+        self.fine_tune_base = bool(fine_tune_base)
         self.dropout_rate, self.l2_reg, self.learning_rate = float(dropout_rate), float(l2_reg), float(learning_rate)
         if loss != "sparse_categorical_crossentropy":
             raise ValueError("only sparse_categorical_crossentropy (the reference's default, VGG16_model.py:29) is built")
@@ -51,9 +57,14 @@ class FineTunedVGG16(DeviceModelMixin):
         else:
             self._random_init(seed=4000)
 
+    def _tail_convs(self):
+        from sr355.vgg_train import vgg16_tail_convs
+        return vgg16_tail_convs(self.train_last_n_layers) if getattr(self, "fine_tune_base", False) else []
+
     def trainable_layers(self):
-        """Layers whose parameters `fit` updates: the two Dense layers, with or without base_trainable (see setup_model)."""
-        return ["dense", "predictions"]
+        """Layers whose parameters `fit` updates: the two Dense layers, with or without base_trainable; with fine_tune_base the base's
+        trainable convs in front of them (see setup_model)."""
+        return self._tail_convs() + ["dense", "predictions"]
 
     def count_params(self, trainable_only=False):
         """Keras `model.count_params()` / the "Trainable params" line of model.summary(): 14 846 530 / 131 842 at num_classes=2
@@ -68,6 +79,17 @@ class FineTunedVGG16(DeviceModelMixin):
         from sr355 import _lib as L
         _, taps = self.model.forward_with_taps(x, ["block5_conv3"])
         return self.ctx.spatial_op(L.SP_GAP, self.ctx.spatial_op(L.SP_MAXPOOL2, taps["block5_conv3"]))
+
+    def _prefix_device(self, x, first_conv):
+        """[n,H,W,3] device tensor (fp32, or the compute dtype) -> fp32 device [n,h,w,C]: the input of the base conv `first_conv`, from the
+        frozen layers in front of it (one tapped forward of the inference model, a max-pool launch where a pool sits between)."""
+        from sr355 import _lib as L
+        from sr355.vgg_train import vgg16_prefix_tap
+        tap, pooled = vgg16_prefix_tap(first_conv)
+        if tap is None:
+            return x.float()
+        _, taps = self.model.forward_with_taps(x, [tap])
+        return self.ctx.spatial_op(L.SP_MAXPOOL2, taps[tap]) if pooled else taps[tap]
 
     def _gap_features(self, images, batch_size=256):
         """[n,H,W,3] in [0,1] -> [n,512] host features (the host reference path of fit): _gap_device per chunk, downloaded."""
@@ -122,7 +144,14 @@ class FineTunedVGG16(DeviceModelMixin):
         X_train and / or X_val may be the X view of a sr355.patches.LabeledPatches (load_defects_dataset_as_patches(..., on_device=True)):
         then no fp32 patch array of that set exists anywhere -- each epoch's permutation goes up through set_order, a training batch is one
         sr_gather_warp_patches launch on the resident uint8 frames (the identity parameters without augmentation) and the validation
-        features come from batch() chunks of 256 -- and the history and the head are, bit for bit, those of the equivalent arrays."""
+        features come from batch() chunks of 256 -- and the history and the head are, bit for bit, those of the equivalent arrays.
+        With setup_model(fine_tune_base=True) and at least one conv among the last train_last_n_layers: the same fit, draws and callbacks over
+        the trainable convs and the head together (sr355.vgg_train.VGGFineTuner: one flat bucket, one Adam; ReduceLROnPlateau acts on it and
+        EarlyStopping restores convs and head of the best epoch; the host reads the whole bucket once per epoch for it).  Per batch the frozen
+        prefix runs in the inference model and the trained tail in fp32; validation runs through the tail with the epoch's weights, from the
+        validation set's frozen-prefix activations, which are computed once per fit and stay on the device as fp32 for the whole fit:
+        4 h w C bytes per validation image at the first trained conv's input -- 128 KiB at train_last_n_layers=4 on 128 x 128 (8 x 8 x 512),
+        512 KiB at 6 (16 x 16 x 512).  Afterwards set_weights carries the updated convs into the inference model."""
         from sr355.train import fit_head_device
         if self.model is None:
             raise ValueError("Model is not built yet.")
@@ -140,14 +169,26 @@ class FineTunedVGG16(DeviceModelMixin):
         bs = 32 if use_augmentation else int(batch_size)
         n, (h, w) = len(X_train), X_train.shape[1:3]
         Xd = self.ctx.to_device(X_train) if ds_train is None else None
+        convs, trainer = self._tail_convs(), None
+        if convs:
+            from sr355.vgg_train import VGGFineTuner
+            trainer = VGGFineTuner(self.ctx, self.weights, convs, self.learning_rate)
+        frozen = self._gap_device if trainer is None else (lambda x: self._prefix_device(x, convs[0]))
         if ds_val is None:
             Xv = self.ctx.to_device(X_val)
-            g_val = [self._gap_device(Xv[i:i + 256]) for i in range(0, len(X_val), 256)]
+            g_val = [frozen(Xv[i:i + 256]) for i in range(0, len(X_val), 256)]
             del Xv
         else:
             ov = ds_val.set_order(np.arange(len(ds_val))) if len(ds_val) else None
-            g_val = [self._gap_device(ds_val.batch(ov, i, min(256, len(ds_val) - i))) for i in range(0, len(ds_val), 256)]
-        g_val = g_val[0] if len(g_val) == 1 else (torch.cat(g_val) if g_val else self.ctx.empty((0, 512)))
+            g_val = [frozen(ds_val.batch(ov, i, min(256, len(ds_val) - i))) for i in range(0, len(ds_val), 256)]
+        if trainer is None:
+            g_val = g_val[0] if len(g_val) == 1 else (torch.cat(g_val) if g_val else self.ctx.empty((0, 512)))
+        else:
+            p_val = g_val                                   # the cached prefix activations, in chunks of 256 images
+
+            def g_val():
+                g = [trainer.tail_features(p[i:i + bs]) for p in p_val for i in range(0, len(p), bs)]
+                return g[0] if len(g) == 1 else torch.cat(g)
         epoch_order = {}
 
         def draw_epoch(epoch):
@@ -165,11 +206,11 @@ class FineTunedVGG16(DeviceModelMixin):
 
         def features(dev, i, j):
             if ds_train is None:
-                return self._gap_device(self.ctx.affine_warp(Xd, dev["idx"][i:j], dev["warp"][i:j]))
-            return self._gap_device(ds_train.warped_batch(epoch_order["dev"], i, j - i, dev["warp"][i:j]))
+                return frozen(self.ctx.affine_warp(Xd, dev["idx"][i:j], dev["warp"][i:j]))
+            return frozen(ds_train.warped_batch(epoch_order["dev"], i, j - i, dev["warp"][i:j]))
 
         head, history = fit_head_device(self.ctx, features, self.weights, draw_epoch, n, g_val, y_val, learning_rate=self.learning_rate, batch_size=bs,
-                                        epochs=epochs, dropout_rate=self.dropout_rate, l2_reg=self.l2_reg, seed=seed)
+                                        epochs=epochs, dropout_rate=self.dropout_rate, l2_reg=self.l2_reg, seed=seed, trainer=trainer)
         w_ = dict(self.weights)
         w_.update(head)
         self.set_weights(w_)

@@ -1392,6 +1392,13 @@ int sr_conv2d_wgrad(sr_ctx* ctx, const void* x, const void* dy, int B, int H, in
     return wgrad_launch(ctx, static_cast<const float*>(x), static_cast<const float*>(dy), B, H, W, Cin, Cout, K, dw_hwio, db, static_cast<hipStream_t>(stream));
 }
 
+int sr_conv2d_wgrad_maps(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, float* dw_hwio, float* db, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!x || !dy || !dw_hwio) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return wgrad_maps_launch(ctx, static_cast<const float*>(x), static_cast<const float*>(dy), B, H, W, Cin, Cout, dw_hwio, db, static_cast<hipStream_t>(stream));
+}
+
 int sr_eltwise(sr_ctx* ctx, int op, const void* a, const void* b, float alpha, float beta, void* out, int64_t n, void* stream) {
     DeviceGuard dg_(ctx);
     if (!ctx) return SR_ERR_INVALID;

@@ -15,11 +15,16 @@
 //        of train.ParamBucket), the sum over the batch rows in row order; then one thread sums the rows' losses and hits (fp64, row order).
 //     No float atomics: the gradients and the statistics are the same bits on every run.  At 32 x 512 x 256 the products are 4 MFLOP per step,
 //     ~1 us of VALU work spread over the grid: the step is bound by its launches, not by its arithmetic.
+//   sr_dense_head_step_dx: the same two launches (the same kernels: the same bits in grads and stats) and a third for the gradient at the
+//     features, dfeats = (dz1 k1^T) * m0 / keep -- what the fine-tuned conv base's backward pass starts from.
+//   sr_pool_gap_bwd: GlobalAveragePooling2D, MaxPooling2D(2,2) and the last conv's ReLU backward in one launch: dfeats [B,C] -> dz [B,H,W,C] at
+//     that conv's pre-activation, bit for bit the GAP spread (dfeats / ((H/2)(W/2))), sr_maxpool2_bwd and SR_ELT_RELU_BWD one after the other.
 #include "common.h"
 #include "warp_sample.h"
 
 #include <algorithm>
 #include <cmath>
+#include <string>
 
 namespace {
 
@@ -231,6 +236,117 @@ __global__ void __launch_bounds__(256) head_grads_kernel(int n, int C, const flo
     grads[e] = s;
 }
 
+// dfeats = (dz1 k1^T) * m0 / keep: one thread per input feature i for the workgroup's HROWS rows, dz1 staged in LDS, the 256 hidden units
+// summed in index order (thread i streams row i of k1 with 16-byte loads)
+__global__ void __launch_bounds__(256) head_dfeats_kernel(int n, const uint8_t* __restrict__ m0, float kscale, const float* __restrict__ prm, HeadWork wk,
+                                                          float* __restrict__ dfeats) {
+    __shared__ float sdz[HROWS][HHID];
+    const int tid = threadIdx.x;
+    const int r0 = blockIdx.y * HROWS;
+    const int nr = min(HROWS, n - r0);
+    for (int e = tid; e < HROWS * HHID; e += 256) {
+        const int r = e / HHID, j = e - r * HHID;
+        sdz[r][j] = r < nr ? wk.dz1[(int64_t)(r0 + r) * HHID + j] : 0.f;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + tid;          // < HIN: the grid is HIN / 256 wide
+    const f32x4* k1 = reinterpret_cast<const f32x4*>(prm + (int64_t)i * HHID);
+    float acc[HROWS];
+#pragma unroll
+    for (int r = 0; r < HROWS; ++r) acc[r] = 0.f;
+    for (int j4 = 0; j4 < HHID / 4; ++j4) {
+        const f32x4 w = k1[j4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int r = 0; r < HROWS; ++r) acc[r] = __fmaf_rn(sdz[r][j4 * 4 + q], w[q], acc[r]);
+        }
+    }
+    for (int r = 0; r < nr; ++r) {
+        const int64_t o = (int64_t)(r0 + r) * HIN + i;
+        float v = acc[r];
+        if (m0) v = m0[o] ? __fmul_rn(v, kscale) : 0.f;
+        dfeats[o] = v;
+    }
+}
+
+// GAP -> MaxPooling2D(2,2) -> ReLU backward in one pass: element (b,y,x,c) of dz receives dfeats[b,c] / ((H/2)(W/2)) when it is the first
+// maximum of its 2x2 window (maxpool2_bwd_kernel's rule and order) and a > 0, else zero.  VEC channels per thread.
+template <int VEC>
+__global__ void __launch_bounds__(256) pool_gap_bwd_kernel(const float* __restrict__ a, const float* __restrict__ dfeats, int B, int H, int W, int C,
+                                                           float* __restrict__ dz) {
+    const int oH = H / 2, oW = W / 2, Cv = C / VEC;
+    const float cnt = (float)(oH * oW);
+    const int64_t n = (int64_t)B * H * W * Cv;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i % Cv) * VEC;
+        int64_t t = i / Cv;
+        const int xq = (int)(t % W); t /= W;
+        const int yq = (int)(t % H);
+        const int64_t b = t / H;
+        const int oy = yq >> 1, ox = xq >> 1;
+        float out[VEC];
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) out[q] = 0.f;
+        if (oy < oH && ox < oW) {
+            const float* base = a + ((b * H + 2 * oy) * W + 2 * ox) * C + c;
+            const float* self = a + ((b * H + yq) * W + xq) * C + c;
+            const float* d = dfeats + b * C + c;
+            float v00[VEC], v01[VEC], v10[VEC], v11[VEC], av[VEC], dv[VEC];
+            if constexpr (VEC == 4) {
+                const f32x4 p00 = *reinterpret_cast<const f32x4*>(base), p01 = *reinterpret_cast<const f32x4*>(base + C);
+                const f32x4 p10 = *reinterpret_cast<const f32x4*>(base + (int64_t)W * C), p11 = *reinterpret_cast<const f32x4*>(base + (int64_t)W * C + C);
+                const f32x4 ps = *reinterpret_cast<const f32x4*>(self), pd = *reinterpret_cast<const f32x4*>(d);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { v00[q] = p00[q]; v01[q] = p01[q]; v10[q] = p10[q]; v11[q] = p11[q]; av[q] = ps[q]; dv[q] = pd[q]; }
+            } else {
+                v00[0] = base[0]; v01[0] = base[C]; v10[0] = base[(int64_t)W * C]; v11[0] = base[(int64_t)W * C + C]; av[0] = self[0]; dv[0] = d[0];
+            }
+            const int me = (yq & 1) * 2 + (xq & 1);
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const float m = fmaxf(fmaxf(v00[q], v01[q]), fmaxf(v10[q], v11[q]));
+                const int arg = v00[q] == m ? 0 : (v01[q] == m ? 1 : (v10[q] == m ? 2 : 3));
+                const float g = arg == me ? __fdiv_rn(dv[q], cnt) : 0.f;
+                out[q] = av[q] > 0.f ? g : 0.f;
+            }
+        }
+        float* o = dz + ((b * H + yq) * W + xq) * C + c;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<f32x4*>(o) = f32x4{out[0], out[1], out[2], out[3]};
+        } else {
+            o[0] = out[0];
+        }
+    }
+}
+
+// the checks and the two launches sr_dense_head_step and sr_dense_head_step_dx share; dfeats != nullptr adds the third
+int head_step(sr_ctx* ctx, const std::string& who, const float* feats, int n, int in_dim, int hidden, int num_classes, const int32_t* labels,
+              const uint8_t* keep0, const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads, float* dfeats, double* stats,
+              void* work, int64_t work_bytes, void* stream) {
+    if (!feats || !labels || !params || !stats || !work) return ctx->fail(SR_ERR_INVALID, who + ": null tensor");
+    if (in_dim != HIN || hidden != HHID) return ctx->fail(SR_ERR_INVALID, who + ": the head is Dense 512 -> 256 -> num_classes");
+    if (n < 1 || num_classes < 2 || (int64_t)n * num_classes >= ((int64_t)1 << 31) || (int64_t)HHID * num_classes >= ((int64_t)1 << 30))
+        return ctx->fail(SR_ERR_INVALID, who + ": need n >= 1 and num_classes >= 2");
+    if ((keep0 == nullptr) != (keep1 == nullptr)) return ctx->fail(SR_ERR_INVALID, who + ": both dropout masks or neither");
+    if (keep0 && !grads) return ctx->fail(SR_ERR_INVALID, who + ": dropout masks in inference mode");
+    if (work_bytes < head_work_bytes(n, num_classes)) return ctx->fail(SR_ERR_CAPACITY, who + ": workspace too small");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const HeadWork wk = head_work(work, n, num_classes);
+    const int train = grads != nullptr;
+    hipLaunchKernelGGL(head_rows_kernel, dim3((n + HROWS - 1) / HROWS), dim3(256), 0, st, feats, n, num_classes, labels, keep0, keep1, keep_scale, params, train, wk, stats);
+    SR_HIP(ctx, hipGetLastError());
+    const int64_t np = (int64_t)HIN * HHID + HHID + (int64_t)HHID * num_classes + num_classes;
+    const unsigned gg = train ? (unsigned)((np + 255) / 256) : 1u;
+    hipLaunchKernelGGL(head_grads_kernel, dim3(gg), dim3(256), 0, st, n, num_classes, params, 2.f * l2_reg, wk, grads, stats);
+    SR_HIP(ctx, hipGetLastError());
+    if (dfeats) {
+        hipLaunchKernelGGL(head_dfeats_kernel, dim3(HIN / 256, (n + HROWS - 1) / HROWS), dim3(256), 0, st, n, keep0, keep_scale, params, wk, dfeats);
+        SR_HIP(ctx, hipGetLastError());
+    }
+    return SR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -264,21 +380,38 @@ int sr_dense_head_step(sr_ctx* ctx, const float* feats, int n, int in_dim, int h
                        int64_t work_bytes, void* stream) {
     DeviceGuard dg_(ctx);
     if (!ctx) return SR_ERR_INVALID;
-    if (!feats || !labels || !params || !stats || !work) return ctx->fail(SR_ERR_INVALID, "dense_head_step: null tensor");
-    if (in_dim != HIN || hidden != HHID) return ctx->fail(SR_ERR_INVALID, "dense_head_step: the head is Dense 512 -> 256 -> num_classes");
-    if (n < 1 || num_classes < 2 || (int64_t)n * num_classes >= ((int64_t)1 << 31) || (int64_t)HHID * num_classes >= ((int64_t)1 << 30))
-        return ctx->fail(SR_ERR_INVALID, "dense_head_step: need n >= 1 and num_classes >= 2");
-    if ((keep0 == nullptr) != (keep1 == nullptr)) return ctx->fail(SR_ERR_INVALID, "dense_head_step: both dropout masks or neither");
-    if (keep0 && !grads) return ctx->fail(SR_ERR_INVALID, "dense_head_step: dropout masks in inference mode");
-    if (work_bytes < head_work_bytes(n, num_classes)) return ctx->fail(SR_ERR_CAPACITY, "dense_head_step: workspace too small");
+    return head_step(ctx, "dense_head_step", feats, n, in_dim, hidden, num_classes, labels, keep0, keep1, keep_scale, params, l2_reg, grads, nullptr, stats, work,
+                     work_bytes, stream);
+}
+
+int sr_dense_head_step_dx(sr_ctx* ctx, const float* feats, int n, int in_dim, int hidden, int num_classes, const int32_t* labels, const uint8_t* keep0,
+                          const uint8_t* keep1, float keep_scale, const float* params, float l2_reg, float* grads, float* dfeats, double* stats, void* work,
+                          int64_t work_bytes, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!grads || !dfeats) return ctx->fail(SR_ERR_INVALID, "dense_head_step_dx: null tensor");
+    if (n > 65535 * HROWS) return ctx->fail(SR_ERR_INVALID, "dense_head_step_dx: n <= 524280");
+    if (reinterpret_cast<uintptr_t>(params) & 15) return ctx->fail(SR_ERR_INVALID, "dense_head_step_dx: params must be 16-byte aligned");
+    return head_step(ctx, "dense_head_step_dx", feats, n, in_dim, hidden, num_classes, labels, keep0, keep1, keep_scale, params, l2_reg, grads, dfeats, stats, work,
+                     work_bytes, stream);
+}
+
+int sr_pool_gap_bwd(sr_ctx* ctx, const float* a, const float* dfeats, int B, int H, int W, int C, float* dz, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!a || !dfeats || !dz) return ctx->fail(SR_ERR_INVALID, "pool_gap_bwd: null tensor");
+    if (B < 1 || H < 2 || W < 2 || C < 1) return ctx->fail(SR_ERR_INVALID, "pool_gap_bwd: need B >= 1, H >= 2, W >= 2, C >= 1");
+    if (H >= (1 << 15) || W >= (1 << 15)) return ctx->fail(SR_ERR_INVALID, "pool_gap_bwd: map too large");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const HeadWork wk = head_work(work, n, num_classes);
-    const int train = grads != nullptr;
-    hipLaunchKernelGGL(head_rows_kernel, dim3((n + HROWS - 1) / HROWS), dim3(256), 0, st, feats, n, num_classes, labels, keep0, keep1, keep_scale, params, train, wk, stats);
-    SR_HIP(ctx, hipGetLastError());
-    const int64_t np = (int64_t)HIN * HHID + HHID + (int64_t)HHID * num_classes + num_classes;
-    const unsigned gg = train ? (unsigned)((np + 255) / 256) : 1u;
-    hipLaunchKernelGGL(head_grads_kernel, dim3(gg), dim3(256), 0, st, n, num_classes, params, 2.f * l2_reg, wk, grads, stats);
+    const bool v4 = C % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(dfeats) | reinterpret_cast<uintptr_t>(dz)) & 15) == 0;
+    const int64_t nthr = (int64_t)B * H * W * (v4 ? C / 4 : C);
+    const int64_t blocks = (nthr + 255) / 256;                 // one thread per VEC channels of a pixel, no cap: B H W C / VEC threads
+    if (blocks > 0x7fffffff) return ctx->fail(SR_ERR_INVALID, "pool_gap_bwd: tensor too large");
+    const unsigned gx = (unsigned)blocks;
+    if (v4)
+        hipLaunchKernelGGL(pool_gap_bwd_kernel<4>, dim3(gx), dim3(256), 0, st, a, dfeats, B, H, W, C, dz);
+    else
+        hipLaunchKernelGGL(pool_gap_bwd_kernel<1>, dim3(gx), dim3(256), 0, st, a, dfeats, B, H, W, C, dz);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
 }

@@ -78,10 +78,19 @@ __global__ void __launch_bounds__(256) wgrad_partial_kernel(const float* x, cons
 // its halo (10 x 26 pixels x 32 channels) and the dy tile (192 pixels x 32 couts) are staged into LDS with 16-byte loads, and every dy value meets the NINE shifted x
 // values of its pixel in nine accumulator tiles -- ten conflict-free ds_read_b32 per nine MFMAs.  The four waves interleave the tile's pixel pairs; their nine
 // tiles are summed through LDS in wave order, the runs of tiles (pixel splits) in wgrad_finish_kernel in split order: deterministic, no atomics.
-constexpr int WT_H = 8, WT_W = 24, WT_PW = WT_W + 2, WT_PH = WT_H + 2, WT_NPIX = WT_H * WT_W;
+//
+// PACK (sr_conv2d_wgrad_maps, maps of at most 8 x 8: a fine-tuned VGG16's block5 on 128-pixel patches): an 8 x 24 tile of ONE such image is two thirds padding.  A
+// tile then holds `ipt` = 27 / (W + 1) images side by side with ONE zero column between neighbours -- 3 images of width 8 in a 10 x 28 halo tile, 26 dy columns -- the
+// packing the two-up forward path uses for 24-pixel patches: the separator is both images' zero padding for x, and dy is zero in it, so the stencil stays regular and
+// nothing crosses the seam.  `tile` counts groups of ipt images (tilesX = tilesY = 1); the rest is the scheme above.  Maps lower than 8 rows multiply zero rows: a pair
+// count that depends on H moved the nine accumulator tiles out of the AGPRs (152 + 144 registers, one workgroup per CU instead of two), and H = 8 is the case this is for.
+constexpr int WT_H = 8, WT_W = 24, WT_PH = WT_H + 2;
+constexpr int WT_W_PACK = 26;
 
+template <int TW, bool PACK>
 __global__ void __launch_bounds__(256) wgrad3_tile_kernel(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, int nci, int nco,
-                                                          int tiles_per_wg, int tilesX, int tilesY, float* partial, double* bpart) {
+                                                          int tiles_per_wg, int tilesX, int tilesY, int ipt, float* partial, double* bpart) {
+    constexpr int WT_W = TW, WT_PW = WT_W + 2, WT_NPIX = WT_H * WT_W;
     // x / dy: NHWC views -- x_cs / dy_cs channels per pixel in the underlying buffer, the pointers already at the view's first channel (round 4: the
     // trainer's dense blocks keep their concat tensor in ONE buffer and hand every conv a channel range of it)
     __shared__ __attribute__((aligned(16))) float xt[WT_PH * WT_PW * 32];
@@ -89,7 +98,7 @@ __global__ void __launch_bounds__(256) wgrad3_tile_kernel(const float* x, int64_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, k = lane >> 5;
     const int cob = blockIdx.x % nco, cib = blockIdx.x / nco;
     const int ci0 = cib * 32, co0 = cob * 32;
-    const int ntile = B * tilesY * tilesX;
+    const int ntile = PACK ? (B + ipt - 1) / ipt : B * tilesY * tilesX;
     const int t0 = blockIdx.y * tiles_per_wg, t1 = min(ntile, t0 + tiles_per_wg);
     const bool vec_x = (Cin & 3) == 0 && (x_cs & 3) == 0 && ((uintptr_t)x & 15) == 0, vec_y = (Cout & 3) == 0 && (dy_cs & 3) == 0 && ((uintptr_t)dy & 15) == 0;
     f32x16 acc[9];
@@ -105,14 +114,21 @@ __global__ void __launch_bounds__(256) wgrad3_tile_kernel(const float* x, int64_
         const int ty = tt % tilesY;
         const int b = tt / tilesY;
         const int y0 = ty * WT_H, x0 = tx * WT_W;
+        [[maybe_unused]] const int b0 = tile * ipt, pitch = W + 1;                    // PACK: the tile's first image, columns per image with its separator
         __syncthreads();                                           // the previous tile's operands have been read
         for (int u = tid; u < WT_PH * WT_PW * 8; u += 256) {
             const int pix = u >> 3, sl = u & 7;
             const int py = pix / WT_PW, px = pix - py * WT_PW;
-            const int gy = y0 + py - 1, gx = x0 + px - 1, c = ci0 + sl * 4;
+            int gy = y0 + py - 1, gx = x0 + px - 1, bi = b;
+            const int c = ci0 + sl * 4;
+            if constexpr (PACK) {                                  // column q = px - 1 of the dy tile: image q / pitch, its column q % pitch (== W: the separator)
+                const int q = px - 1, slot = q >= 0 ? q / pitch : 0;
+                bi = b0 + slot;
+                gx = (q >= 0 && q < WT_W && slot < ipt && bi < B) ? q - slot * pitch : -1;
+            }
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && c < Cin) {
-                const float* src = x + (((int64_t)b * H + gy) * W + gx) * x_cs + c;
+                const float* src = x + (((int64_t)bi * H + gy) * W + gx) * x_cs + c;
                 if (vec_x) v = *reinterpret_cast<const f32x4*>(src);
                 else
                     for (int e = 0; e < 4; ++e) v[e] = c + e < Cin ? src[e] : 0.f;
@@ -122,10 +138,16 @@ __global__ void __launch_bounds__(256) wgrad3_tile_kernel(const float* x, int64_
         for (int u = tid; u < WT_NPIX * 8; u += 256) {
             const int pix = u >> 3, sl = u & 7;
             const int py = pix / WT_W, px = pix - py * WT_W;
-            const int gy = y0 + py, gx = x0 + px, c = co0 + sl * 4;
+            int gy = y0 + py, gx = x0 + px, bi = b;
+            const int c = co0 + sl * 4;
+            if constexpr (PACK) {
+                const int slot = px / pitch;
+                bi = b0 + slot;
+                gx = (slot < ipt && bi < B) ? px - slot * pitch : W;
+            }
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (gy < H && gx < W && c < Cout) {
-                const float* src = dy + (((int64_t)b * H + gy) * W + gx) * dy_cs + c;
+                const float* src = dy + (((int64_t)bi * H + gy) * W + gx) * dy_cs + c;
                 if (vec_y) v = *reinterpret_cast<const f32x4*>(src);
                 else
                     for (int e = 0; e < 4; ++e) v[e] = c + e < Cout ? src[e] : 0.f;
@@ -138,7 +160,7 @@ __global__ void __launch_bounds__(256) wgrad3_tile_kernel(const float* x, int64_
             for (int p = tid >> 5; p < WT_NPIX; p += 8) bsum += (double)dt[p * 32 + co];
         }
         for (int kk = wave; kk < WT_NPIX / 2; kk += 4) {
-            const int p = 2 * kk + k;                              // this lane's pixel of the pair (24 is even: both in one row)
+            const int p = 2 * kk + k;                              // this lane's pixel of the pair (the tile width is even: both in one row)
             const int py = p / WT_W, px = p - py * WT_W;
             const float bv = dt[p * 32 + i];
             const float* xb = xt + (py * WT_PW + px) * 32 + i;
@@ -504,7 +526,8 @@ int wgrad_launch_views(sr_ctx* ctx, const float* x, int64_t x_cs, const float* d
         float* partial = static_cast<float*>(ctx->scratch(tile_bytes + (size_t)nsplit * nco * 32 * sizeof(double)));
         if (!partial) return SR_ERR_OOM;
         double* bpart = db ? reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + tile_bytes) : nullptr;
-        hipLaunchKernelGGL(wgrad3_tile_kernel, dim3(nci * nco, nsplit), dim3(256), 0, st, x, x_cs, dy, dy_cs, B, H, W, Cin, Cout, nci, nco, tiles_per_wg, tilesX, tilesY, partial, bpart);
+        hipLaunchKernelGGL((wgrad3_tile_kernel<WT_W, false>), dim3(nci * nco, nsplit), dim3(256), 0, st, x, x_cs, dy, dy_cs, B, H, W, Cin, Cout, nci, nco, tiles_per_wg, tilesX, tilesY,
+                           1, partial, bpart);
         hipLaunchKernelGGL(wgrad_finish_kernel, dim3(ntiles, 4), dim3(256), 0, st, partial, ntiles, nsplit, Cin, Cout, nci, nco, dw, bpart, db);
         SR_HIP(ctx, hipGetLastError());
         return SR_OK;
@@ -517,6 +540,29 @@ int wgrad_launch_views(sr_ctx* ctx, const float* x, int64_t x_cs, const float* d
     hipLaunchKernelGGL(wgrad_partial_kernel, dim3(ntiles, nsplit), dim3(256), 0, st, x, dy, B, H, W, Cin, Cout, KS, nci, nco, nsplit, partial);
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3(ntiles, 4), dim3(256), 0, st, partial, ntiles, nsplit, Cin, Cout, nci, nco, dw, (const double*)nullptr, (float*)nullptr);
     if (db) hipLaunchKernelGGL(colsum_kernel, dim3(Cout), dim3(256), 0, st, dy, P, Cout, db);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+// 3x3 layers on maps of at most 8 x 8: the tile kernel on tiles that hold several images (see PACK above); the finish pass and the order of every sum are wgrad_launch's
+int wgrad_maps_launch(sr_ctx* ctx, const float* x, const float* dy, int B, int H, int W, int Cin, int Cout, float* dw, float* db, hipStream_t st) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return ctx->fail(SR_ERR_INVALID, "wgrad_maps: empty tensor");
+    if (H > WT_H || W > 8) return ctx->fail(SR_ERR_INVALID, "wgrad_maps: maps of at most 8 x 8 (sr_conv2d_wgrad takes any size)");
+    const int nci = (Cin + 31) / 32, nco = (Cout + 31) / 32, ntiles = 9 * nci * nco;
+    if ((int64_t)nci * nco > 0x7fffffff / 9) return ctx->fail(SR_ERR_INVALID, "wgrad_maps: too many channels");
+    const int ipt = (WT_W_PACK + 1) / (W + 1), ntile = (B + ipt - 1) / ipt;
+    int nsplit = (3 * ctx->cu_count() / 2 + nci * nco - 1) / (nci * nco);
+    if (nsplit > ntile) nsplit = ntile;
+    if (nsplit > 64) nsplit = 64;
+    const int tiles_per_wg = (ntile + nsplit - 1) / nsplit;
+    nsplit = (ntile + tiles_per_wg - 1) / tiles_per_wg;
+    const size_t tile_bytes = (size_t)nsplit * ntiles * 1024 * sizeof(float);
+    float* partial = static_cast<float*>(ctx->scratch(tile_bytes + (size_t)nsplit * nco * 32 * sizeof(double)));
+    if (!partial) return SR_ERR_OOM;
+    double* bpart = db ? reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + tile_bytes) : nullptr;
+    hipLaunchKernelGGL((wgrad3_tile_kernel<WT_W_PACK, true>), dim3(nci * nco, nsplit), dim3(256), 0, st, x, (int64_t)Cin, dy, (int64_t)Cout, B, H, W, Cin, Cout, nci, nco, tiles_per_wg,
+                       1, 1, ipt, partial, bpart);
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(ntiles, 4), dim3(256), 0, st, partial, ntiles, nsplit, Cin, Cout, nci, nco, dw, bpart, db);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
 }

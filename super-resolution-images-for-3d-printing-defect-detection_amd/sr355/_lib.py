@@ -93,6 +93,7 @@ SIGNATURES = {
     "sr_mse": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "sr_conv2d_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _f, _vp, _f, _i, _i, _vp, _vp]),
     "sr_conv2d_wgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_conv2d_wgrad_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_conv2d_dev_views": (_i, [_vp, _vw, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vw, _f, _vw, _vp]),
     "sr_conv_prepack": (_i, [_vp, C.POINTER(PackDesc), _i, _vp]),
     "sr_conv2d_wgrad_views": (_i, [_vp, _vw, _vw, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
@@ -136,6 +137,8 @@ SIGNATURES = {
     "sr_affine_warp": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "sr_dense_head_workspace_bytes": (_i64, [_i, _i]),
     "sr_dense_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _i64, _vp]),
+    "sr_dense_head_step_dx": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sr_pool_gap_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_spectral_norm_bucket": (_i, [_vp, _vp, _i64, _vp, _i64, C.POINTER(SnDesc), _i, _vp]),
     "sr_disc_head_step": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp]),
     "sr_lpips_shapes": (_i, [_i, _i, C.POINTER(_i)]),

@@ -47,6 +47,7 @@ class Tape:
         self.ops, self.grads = [], {}
         self.masks = None                                       # diagnostics: a dict here collects {layer: activation > 0} of every ReLU / LeakyReLU conv
         self.dev = devcache if devcache is not None else {}     # id(host array) -> (host array, device tensor): one upload per array
+        self.conv_wgrad = ctx.conv2d_wgrad                      # (x, dz, k) -> (dw, db): a trainer may route small maps to another kernel
 
     def _dev(self, a):
         hit = self.dev.get(id(a))
@@ -90,7 +91,7 @@ class Tape:
             if d2s > 1:
                 dz = ctx.space_to_depth(dz, d2s)                   # activation is element-wise: its mask commutes with the shuffle
             if self.wgrad:
-                dw, db = ctx.conv2d_wgrad(x.v, dz, k.shape[0])
+                dw, db = self.conv_wgrad(x.v, dz, k.shape[0])
                 self._pgrad(name, dw, db)
             if x.need:
                 self._acc(x, ctx.conv2d_dev(dz, kd, None, k.shape[2], rot=True))

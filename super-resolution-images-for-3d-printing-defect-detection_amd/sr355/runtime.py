@@ -748,17 +748,46 @@ class Context:
                                              self.stream()))
 
     # ------------------------------------------------------------------ backward-pass pieces (sr355/train.py)
-    def conv2d_wgrad(self, x, dy, k):
-        """Kernel and bias gradient of Conv2D(k x k, SAME, stride 1): x [B,H,W,Cin], dy [B,H,W,Cout] fp32 -> (dw HWIO, db) device tensors."""
+    def conv2d_wgrad(self, x, dy, k, out=None):
+        """Kernel and bias gradient of Conv2D(k x k, SAME, stride 1): x [B,H,W,Cin], dy [B,H,W,Cout] fp32 -> (dw HWIO, db) device tensors
+        (out: a (dw, db) pair to write into, views of a flat gradient bucket for instance)."""
         _check_tensor(self, x, "wgrad x")
         _check_tensor(self, dy, "wgrad dy")
         B, H, W, cin = x.shape
         if tuple(dy.shape[:3]) != (B, H, W):
             raise ValueError("wgrad: x and dy must share [B,H,W]")
         cout = dy.shape[3]
-        dw = self.empty((k, k, cin, cout), torch.float32)
-        db = self.empty((cout,), torch.float32)
+        if out is None:
+            dw = self.empty((k, k, cin, cout), torch.float32)
+            db = self.empty((cout,), torch.float32)
+        else:
+            dw, db = out
+            _check_tensor(self, dw, "wgrad out dw")
+            _check_tensor(self, db, "wgrad out db")
+            if tuple(dw.shape) != (k, k, cin, cout) or tuple(db.shape) != (cout,):
+                raise ValueError("wgrad: out must be (dw [k,k,Cin,Cout], db [Cout])")
         self.check(self.lib.sr_conv2d_wgrad(self.h, x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, int(k), dw.data_ptr(), db.data_ptr(), self.stream()))
+        return dw, db
+
+    def conv2d_wgrad_maps(self, x, dy, out=None):
+        """conv2d_wgrad of a 3x3 layer on maps of at most 8 x 8 (sr_conv2d_wgrad_maps: several images per staged tile)."""
+        _check_tensor(self, x, "wgrad_maps x")
+        _check_tensor(self, dy, "wgrad_maps dy")
+        if x.dim() != 4 or dy.dim() != 4 or tuple(dy.shape[:3]) != tuple(x.shape[:3]):
+            raise ValueError("wgrad_maps: x and dy must share [B,H,W]")
+        B, H, W, cin = x.shape
+        cout = dy.shape[3]
+        if H > 8 or W > 8:
+            raise ValueError(f"wgrad_maps: maps of at most 8 x 8, got {H} x {W}")
+        if out is None:
+            dw, db = self.empty((3, 3, cin, cout), torch.float32), self.empty((cout,), torch.float32)
+        else:
+            dw, db = out
+            _check_tensor(self, dw, "wgrad_maps out dw")
+            _check_tensor(self, db, "wgrad_maps out db")
+            if tuple(dw.shape) != (3, 3, cin, cout) or tuple(db.shape) != (cout,):
+                raise ValueError("wgrad_maps: out must be (dw [3,3,Cin,Cout], db [Cout])")
+        self.check(self.lib.sr_conv2d_wgrad_maps(self.h, x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, dw.data_ptr(), db.data_ptr(), self.stream()))
         return dw, db
 
     def eltwise(self, op, a, b=None, alpha=1.0, beta=0.0):
@@ -866,10 +895,12 @@ class Context:
             raise ValueError("dense_head_workspace: need n >= 1 and num_classes >= 2")
         return self.empty((nb,), torch.uint8)
 
-    def dense_head_step(self, feats, labels, params, num_classes, stats, work, grads=None, keep0=None, keep1=None, keep_scale=1.0, l2_reg=0.0):
+    def dense_head_step(self, feats, labels, params, num_classes, stats, work, grads=None, keep0=None, keep1=None, keep_scale=1.0, l2_reg=0.0,
+                        dfeats=None):
         """One step of the classifier head (sr_dense_head_step): feats fp32 [n,512], labels int32 [n], params the flat fp32 head bucket; with
         grads (fp32, same size) a training step that writes the gradient of mean sparse CCE + l2_reg sum(k1^2), with uint8 dropout keep masks
-        keep0 [n,512] / keep1 [n,256] (optional), else an inference pass.  stats fp64 [3] receives (loss sum, correct rows, sum k1^2)."""
+        keep0 [n,512] / keep1 [n,256] (optional), else an inference pass.  stats fp64 [3] receives (loss sum, correct rows, sum k1^2).
+        dfeats fp32 [n,512] (training steps only): sr_dense_head_step_dx instead -- the same grads and stats, and the gradient at feats."""
         C_ = int(num_classes)
         _check_tensor(self, feats, "dense_head feats")
         _check_tensor(self, labels, "dense_head labels", (torch.int32,))
@@ -896,8 +927,28 @@ class Context:
             if keep0.shape != (n, 512) or keep1.shape != (n, 256):
                 raise ValueError("dense_head_step: keep masks must be [n,512] and [n,256]")
         ptr = lambda t: None if t is None else t.data_ptr()
+        if dfeats is not None:
+            _check_tensor(self, dfeats, "dense_head dfeats")
+            if grads is None or tuple(dfeats.shape) != (n, 512):
+                raise ValueError("dense_head_step: dfeats [n,512] comes with grads, in training steps only")
+            self.check(self.lib.sr_dense_head_step_dx(self.h, feats.data_ptr(), n, 512, 256, C_, labels.data_ptr(), ptr(keep0), ptr(keep1), float(keep_scale),
+                                                      params.data_ptr(), float(l2_reg), grads.data_ptr(), dfeats.data_ptr(), stats.data_ptr(), work.data_ptr(),
+                                                      work.numel(), self.stream()))
+            return
         self.check(self.lib.sr_dense_head_step(self.h, feats.data_ptr(), n, 512, 256, C_, labels.data_ptr(), ptr(keep0), ptr(keep1), float(keep_scale),
                                                params.data_ptr(), float(l2_reg), ptr(grads), stats.data_ptr(), work.data_ptr(), work.numel(), self.stream()))
+
+    def pool_gap_bwd(self, a, dfeats):
+        """MaxPooling2D(2,2) + GlobalAveragePooling2D + the ReLU in front, backward in one launch (sr_pool_gap_bwd): a fp32 [B,H,W,C] the ReLU
+        output, dfeats fp32 [B,C] -> dz fp32 [B,H,W,C] at the pre-activation."""
+        _check_tensor(self, a, "pool_gap_bwd a")
+        _check_tensor(self, dfeats, "pool_gap_bwd dfeats")
+        if a.dim() != 4 or tuple(dfeats.shape) != (a.shape[0], a.shape[3]):
+            raise ValueError(f"pool_gap_bwd: a [B,H,W,C] and dfeats [B,C] expected, got {tuple(a.shape)} and {tuple(dfeats.shape)}")
+        B, H, W, Cx = a.shape
+        dz = torch.empty_like(a)
+        self.check(self.lib.sr_pool_gap_bwd(self.h, a.data_ptr(), dfeats.data_ptr(), B, H, W, Cx, dz.data_ptr(), self.stream()))
+        return dz
 
     # ------------------------------------------------------------------ the discriminator's update besides its convs (ESRGAN_model.py:347-377, :475-533)
     @staticmethod

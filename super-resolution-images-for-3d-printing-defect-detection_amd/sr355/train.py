@@ -510,27 +510,34 @@ def upload_packed(ctx, arrays):
 
 
 def fit_head_device(ctx, features, w, draw_epoch, n_train, g_val, y_val, learning_rate=1e-3, batch_size=32, epochs=50, dropout_rate=0.2,
-                    l2_reg=0.0, seed=42, verbose=True):
+                    l2_reg=0.0, seed=42, verbose=True, trainer=None):
     """fit_head on the device: the same fit (VGG16_model.py:111-157), history, print lines and callbacks, with the head in one flat device
     bucket (ParamBucket) trained by sr_dense_head_step + DeviceAdam.  draw_epoch(ep) -> {name: host array} of the epoch, one row per training
     sample in the epoch's order, with at least "labels" (int32); the dropout keep masks are drawn here on fit_head's own generator, in its order
     (m0 [n_b,512] then m1 [n_b,256] per batch), and everything goes up in one copy per epoch.  features(dev, i, j) -> fp32 device [j-i,512] GAP
     features of the epoch's samples i..j-1 (dev: the uploaded arrays).  g_val fp32 device [n_val,512].  The host reads the per-batch statistics
-    and the head (131 842 parameters at two classes, for EarlyStopping) once per epoch.  -> (head weights, History)."""
+    and the head (131 842 parameters at two classes, for EarlyStopping) once per epoch.  -> (head weights, History).
+    trainer (a vgg_train.VGGFineTuner built on w): the same fit of ITS bucket -- trainable convs and head under its one DeviceAdam.  features()
+    then returns what trainer.step consumes (the frozen prefix's activations), g_val is a callable that returns the validation features under
+    the epoch's weights, the callbacks see, snapshot and restore the whole bucket, and every layer of it is returned."""
     head = {n: (np.asarray(w[n][0], np.float32), np.asarray(w[n][1], np.float32)) for n in ("dense", "predictions")}
     num_classes = head["predictions"][0].shape[1]
     y_val = np.asarray(y_val, np.int64).reshape(-1)
     if len(y_val) and (y_val.min() < 0 or y_val.max() >= num_classes):
         raise ValueError(f"labels must lie in [0, {num_classes})")
-    bucket = ParamBucket(ctx, head)
-    opt = DeviceAdam(ctx, bucket.flat, learning_rate, epsilon=1e-7)
-    grads = torch.empty_like(bucket.flat)
+    if trainer is None:
+        bucket = ParamBucket(ctx, head)
+        opt = DeviceAdam(ctx, bucket.flat, learning_rate, epsilon=1e-7)
+        grads = torch.empty_like(bucket.flat)
+        head_flat = bucket.flat
+    else:
+        bucket, opt, head_flat = trainer.bucket, trainer.opt, trainer.head
     rng = np.random.default_rng(seed)
     hist = History(("loss", "accuracy", "val_loss", "val_accuracy", "lr"))
     callbacks = PlateauCallbacks(opt, 3, 2, 0.5, 1e-7, verbose)
     keep = 1.0 - dropout_rate
     spans = [(i, min(i + batch_size, n_train)) for i in range(0, n_train, batch_size)]
-    n_val = int(g_val.shape[0])
+    n_val = len(y_val) if callable(g_val) else int(g_val.shape[0])
     yv = ctx.to_device(y_val.astype(np.int32))
     stats = ctx.empty((len(spans) + 1, 3), torch.float64)
     work = ctx.dense_head_workspace(max(batch_size, n_val, 1), num_classes)
@@ -545,10 +552,13 @@ def fit_head_device(ctx, features, w, draw_epoch, n_train, g_val, y_val, learnin
         dev = upload_packed(ctx, plan)
         for s, (i, j) in enumerate(spans):
             k0, k1 = (dev["keep0"][i:j], dev["keep1"][i:j]) if dropout_rate > 0 else (None, None)
-            ctx.dense_head_step(features(dev, i, j), dev["labels"][i:j], bucket.flat, num_classes, stats[s], work, grads, k0, k1, 1.0 / keep, l2_reg)
-            opt.apply(bucket.flat, grads)
+            if trainer is None:
+                ctx.dense_head_step(features(dev, i, j), dev["labels"][i:j], bucket.flat, num_classes, stats[s], work, grads, k0, k1, 1.0 / keep, l2_reg)
+                opt.apply(bucket.flat, grads)
+            else:
+                trainer.step(features(dev, i, j), dev["labels"][i:j], stats[s], work, k0, k1, 1.0 / keep, l2_reg)
         if n_val:
-            ctx.dense_head_step(g_val, yv, bucket.flat, num_classes, stats[len(spans)], work)
+            ctx.dense_head_step(g_val() if callable(g_val) else g_val, yv, head_flat, num_classes, stats[len(spans)], work)
         bucket.stale = True
         weights = bucket.host()
         st = stats.cpu().numpy()
