@@ -266,6 +266,19 @@ int  sr_spatial_op(sr_ctx* ctx, int op, const void* x, int B, int H, int W, int 
 int  sr_matmul(sr_ctx* ctx, const void* A, const void* B, void* C, int batch, int M, int N, int K, int transA, int transB, float alpha, void* stream);
 int  sr_softmax_rows(sr_ctx* ctx, void* s, int64_t rows, int cols, void* stream);
 int  sr_softmax_bwd(sr_ctx* ctx, const void* p, const void* dp, void* ds, int64_t rows, int cols, void* stream);
+/* The STREAMED SelfAttention of training (ESRGAN_model.py:57-65: s = g f^T, beta = softmax(s), o = beta h, with q = g, k = f, v = h): the same
+ * core without any N x N tensor in memory, so that a training patch may be as large as an inference patch.  fp32; q, k: 8 channels, v: 32 channels,
+ * each a device pointer to its first element plus a row stride in ELEMENTS (token i of image b is row b * N + i; three dense tensors: 8, 8, 32; one
+ * fused f | g | h buffer [B,N,64]: pointers 0 / 8 / 16 floats in, all strides 64; pointers 16-byte aligned, strides multiples of 4).  o, dO, dv
+ * [B,N,32], dq, dk [B,N,8] and lse [B,N] are dense.
+ * sr_attention_fwd_lse: o as sr_self_attention's core computes it, and lse[b,i] = max_j s_ij + log sum_j exp(s_ij - max) (natural log).
+ * sr_attention_bwd: with P_ij = exp(s_ij - lse_i) recomputed tile by tile and D_i = <dO_i, o_i>:  dv_j = sum_i P_ij dO_i,
+ *   dS_ij = P_ij (dO_i . v_j - D_i),  dk_j = sum_i dS_ij q_i,  dq_i = sum_j dS_ij k_j.  No atomics: bit-identical from run to run.
+ * Wrong sizes, strides or alignment: SR_ERR_INVALID with a message. */
+int  sr_attention_fwd_lse(sr_ctx* ctx, const void* q, const void* k, const void* v, int64_t q_rs, int64_t k_rs, int64_t v_rs, int B, int N,
+                          void* o, void* lse, void* stream);
+int  sr_attention_bwd(sr_ctx* ctx, const void* q, const void* k, const void* v, const void* o, const void* dO, const void* lse,
+                      int64_t q_rs, int64_t k_rs, int64_t v_rs, int B, int N, void* dq, void* dk, void* dv, void* stream);
 int  sr_maxpool2_bwd(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int C, void* dx, void* stream);
 int  sr_zero_insert2(sr_ctx* ctx, const void* dy, int B, int H, int W, int C, void* out, void* stream);
 int  sr_spectral_l1_bwd(sr_ctx* ctx, const void* a, const void* b, int B, int H, int W, int C, float scale, void* da, void* stream);

@@ -26,12 +26,16 @@ class _Normalised:
 
 
 class ESRGAN(DeviceModelMixin):
-    def __init__(self, compute_dtype="f32", discriminator_update="host"):
+    def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
         >= 100 dB against the fp64 oracle) or "bf16" (opt-in: bf16 storage, fp32 accumulation -- BASELINE configs[2]'s dtype and what
         bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md).
         discriminator_update: where _train_step updates the discriminator -- "host" (default: NumPy, as before) or "device" (its parameters,
-        spectral-norm vectors and Adam stay on the GPU: sr355.gan_train.ESRGANTrainer); anything else raises when the trainer is built."""
+        spectral-norm vectors and Adam stay on the GPU: sr355.gan_train.ESRGANTrainer); anything else raises when the trainer is built.
+        train_attention: how fit() runs the SelfAttention layers -- "materialised" (default: the [B,N,N] attention map is kept for the backward
+        pass, as the reference does) or "streamed" (no [B,N,N] tensor in the forward or the backward pass, so training patches may be as large
+        as inference patches: sr_attention_fwd_lse / sr_attention_bwd); anything else raises ValueError here."""
+        from sr355.gan_train import check_attention_impl
         self.generator = None
         self.discriminator = None
         self.vgg_model = None
@@ -40,6 +44,7 @@ class ESRGAN(DeviceModelMixin):
         self.trained = False
         self.compute_dtype = compute_dtype
         self.discriminator_update = discriminator_update
+        self.train_attention = check_attention_impl(train_attention)
 
     def _mark_trained(self, v):
         self.trained = v
@@ -128,7 +133,7 @@ class ESRGAN(DeviceModelMixin):
             self._trainer = ESRGANTrainer(self.ctx, self.weights, self.d_weights, self.vgg_weights, self.scale_factor,
                                           self.num_rrdb_blocks, attention=self.use_attention, g_lr=1e-4, d_lr=1e-5,
                                           allreduce=getattr(self, "grad_allreduce", None), allreduce_flat=getattr(self, "grad_allreduce_flat", None),
-                                          discriminator=self.discriminator_update)
+                                          discriminator=self.discriminator_update, attention_impl=self.train_attention)
             self.g_optimizer, self.d_optimizer = self._trainer.g_opt, self._trainer.d_opt
         return self._trainer
 

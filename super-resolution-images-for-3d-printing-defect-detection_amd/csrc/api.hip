@@ -1459,6 +1459,21 @@ int sr_softmax_bwd(sr_ctx* ctx, const void* p, const void* dp, void* ds, int64_t
     if (!p || !dp || !ds) return ctx->fail(SR_ERR_INVALID, "null tensor");
     return softmax_bwd_launch(ctx, SR_F(p), SR_F(dp), SR_FM(ds), rows, cols, static_cast<hipStream_t>(stream));
 }
+int sr_attention_fwd_lse(sr_ctx* ctx, const void* q, const void* k, const void* v, int64_t q_rs, int64_t k_rs, int64_t v_rs, int B, int N, void* o,
+                         void* lse, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!q || !k || !v || !o || !lse) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return attention_fwd_lse_launch(ctx, SR_F(q), SR_F(k), SR_F(v), q_rs, k_rs, v_rs, B, N, SR_FM(o), SR_FM(lse), static_cast<hipStream_t>(stream));
+}
+int sr_attention_bwd(sr_ctx* ctx, const void* q, const void* k, const void* v, const void* o, const void* dO, const void* lse, int64_t q_rs,
+                     int64_t k_rs, int64_t v_rs, int B, int N, void* dq, void* dk, void* dv, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!q || !k || !v || !o || !dO || !lse || !dq || !dk || !dv) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return attention_bwd_launch(ctx, SR_F(q), SR_F(k), SR_F(v), SR_F(o), SR_F(dO), SR_F(lse), q_rs, k_rs, v_rs, B, N, SR_FM(dq), SR_FM(dk), SR_FM(dv),
+                                static_cast<hipStream_t>(stream));
+}
 int sr_maxpool2_bwd(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int C, void* dx, void* stream) {
     DeviceGuard dg_(ctx);
     if (!ctx) return SR_ERR_INVALID;

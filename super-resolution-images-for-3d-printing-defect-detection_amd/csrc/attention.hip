@@ -14,16 +14,12 @@
 // of 64; the V tile is transposed into LDS once per workgroup per tile.
 // HBM bytes per launch (algorithmic): B*N*(8+8+32+32)*sizeof(T); FLOP 2*B*N^2*(8+32);
 // exp count B*N^2 (the binding resource: d_qk/d_v are tiny).
+#include "attn_f32.h"
 #include "common.h"
 
 #include <cstdlib>
 
 namespace {
-
-constexpr int KV_TILE = 64;
-
-template <typename T> struct AT;
-template <> struct AT<float>  { static constexpr int PITCH = KV_TILE * 4 + 4; };    // bytes per V^T row in LDS
 
 struct AttnParams {
     const char* qkv; int64_t cs; int qoff, koff, voff;
@@ -32,101 +28,14 @@ struct AttnParams {
     const float* knorm;       // bf16 kernel: [B][ceil(N / 128)] largest Euclidean norm of a key in each 128-key group (attn_knorm_kernel)
 };
 
-__device__ __forceinline__ float xhalf(float v) { return __shfl_xor(v, 32); }
-
-// fp32 kernel (reference precision): exact fp32 MFMA (32x32x2_f32) for both products, one 32-query block per wave.
+// fp32 kernel (reference precision): the body is attn_f32.h's, shared with the training forward (attention_train.hip).
 __global__ void __launch_bounds__(256, 2) attn_f32_kernel(AttnParams p) {
-    constexpr int PITCH = AT<float>::PITCH;
-    __shared__ __attribute__((aligned(16))) char vt[32 * PITCH];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
+    __shared__ __attribute__((aligned(16))) char vt[32 * ATTN_VT_PITCH];
     const int b = blockIdx.y;
-    const int N = p.N;
-    const float* base = reinterpret_cast<const float*>(p.qkv) + (int64_t)b * N * p.cs;
-    const int q = blockIdx.x * 128 + wave * 32 + r;
-    const int qc = q < N ? q : N - 1;
-
-    // query fragment (B operand of S^T = K.Q^T)
-    float qf[4];
-    {
-        const float* qp = base + (int64_t)qc * p.cs + p.qoff;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) qf[j] = qp[2 * j + h];
-    }
-
-    f32x16 oacc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oacc[e] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    // V staging assignment: thread -> (key within tile, 8-channel octet)
-    const int skey = tid >> 2, soct = tid & 3;
-
-    for (int k0 = 0; k0 < N; k0 += KV_TILE) {
-        __syncthreads();   // previous tile's V^T reads are done
-        {
-            const int key = k0 + skey;
-            const float* vp = base + (int64_t)(key < N ? key : N - 1) * p.cs + p.voff + soct * 8;
-            f32x4 v0 = *reinterpret_cast<const f32x4*>(vp), v1 = *reinterpret_cast<const f32x4*>(vp + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                *reinterpret_cast<float*>(vt + (soct * 8 + e) * PITCH + skey * 4) = v0[e];
-                *reinterpret_cast<float*>(vt + (soct * 8 + 4 + e) * PITCH + skey * 4) = v1[e];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int sub = 0; sub < KV_TILE / 32; ++sub) {
-            const int kb = k0 + sub * 32;
-            if (kb >= N) break;
-            // ---- S^T = K . Q^T
-            f32x16 s;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) s[e] = 0.f;
-            {
-                const int key = kb + r;
-                const float* kp = base + (int64_t)(key < N ? key : N - 1) * p.cs + p.koff;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kp[2 * j + h], qf[j], s, 0, 0, 0);
-            }
-            // ---- online softmax over this tile's 32 keys (16 here, 16 in lane^32)
-            float mx = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int key = kb + (i & 3) + 8 * (i >> 2) + 4 * h;
-                if (key >= N) s[i] = -INFINITY;
-                mx = fmaxf(mx, s[i]);
-            }
-            mx = fmaxf(mx, xhalf(mx));
-            const float m_new = fmaxf(m_run, mx);          // finite: every tile has >= 1 live key
-            const float alpha = __expf(m_run - m_new);     // exp(-inf) = 0 on the first tile
-            float psum = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { s[i] = __expf(s[i] - m_new); psum += s[i]; }
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) oacc[e] *= alpha;
-            // ---- O^T += V^T . P^T
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int krow = sub * 32 + (i & 3) + 8 * (i >> 2);
-                const float va = *reinterpret_cast<const float*>(vt + r * PITCH + (krow + 4 * h) * 4);
-                oacc = __builtin_amdgcn_mfma_f32_32x32x2f32(va, s[i], oacc, 0, 0, 0);
-            }
-        }
-    }
-    const float l_tot = l_run + xhalf(l_run);
-    const float inv = 1.f / l_tot;
-    if (q < N) {
-        float* op = reinterpret_cast<float*>(p.o) + ((int64_t)b * N + q) * p.o_cs + p.o_coff;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d0 = 8 * g + 4 * h;
-            f32x4 t = {oacc[4 * g] * inv, oacc[4 * g + 1] * inv, oacc[4 * g + 2] * inv, oacc[4 * g + 3] * inv};
-            *reinterpret_cast<f32x4*>(op + d0) = t;
-        }
-    }
+    const float* base = reinterpret_cast<const float*>(p.qkv) + (int64_t)b * p.N * p.cs;
+    const AttnF32Args a{base + p.qoff, base + p.koff, base + p.voff, p.cs, p.cs, p.cs,
+                        reinterpret_cast<float*>(p.o) + (int64_t)b * p.N * p.o_cs + p.o_coff, p.o_cs, nullptr, p.N};
+    attn_f32_body<false>(a, blockIdx.x * 128, vt);
 }
 
 // ------------------------------------------------------------------------------------------------

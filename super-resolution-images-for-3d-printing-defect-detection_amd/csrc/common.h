@@ -52,6 +52,7 @@ struct sr_ctx {
     void* tab_buf = nullptr; size_t tab_cap = 0;   // tap tables of sr_resize (stream-ordered reuse)
     struct Arena { void* p = nullptr; size_t cap = 0; };
     Arena attn_kn;                // attention: per-key-group largest key norm (stream-ordered reuse)
+    Arena attn_d;                 // attention_train.hip: D_i = <dO_i, o_i> of the backward pass in flight (stream-ordered reuse)
     Arena dev_w, dev_b, dev_x;    // sr_conv2d_dev: packed weights / padded bias / padded input of the call in flight (stream-ordered reuse)
     Arena cls_tab, cls_work, cls_fft;   // classic.hip: tap tables, per-call work buffers, the DFT products' operands (stream-ordered reuse)
     std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape;
@@ -295,6 +296,13 @@ int block_launch(sr_ctx* ctx, const BlockWeights& w, TensorView in, int B, int H
 // ---------------------------------------------------------------------------------------------
 int attention_launch(sr_ctx* ctx, int dtype, const void* qkv, int64_t cs, int qoff, int koff, int voff,
                      int B, int N, void* o, int64_t o_cs, int o_coff, hipStream_t st);
+// The same core for training (attention_train.hip), fp32: q, k [B,N,8] and v [B,N,32] as pointer + row stride in elements (image b starts at row
+// b * N), o / dO / dv [B,N,32], dq / dk [B,N,8], lse [B,N] dense.  The forward also stores lse = m + log(l); the backward streams over it and
+// writes no N x N intermediate (its only scratch is ctx->attn_d, B * N floats).
+int attention_fwd_lse_launch(sr_ctx* ctx, const float* q, const float* k, const float* v, int64_t q_rs, int64_t k_rs, int64_t v_rs, int B, int N,
+                             float* o, float* lse, hipStream_t st);
+int attention_bwd_launch(sr_ctx* ctx, const float* q, const float* k, const float* v, const float* o, const float* dout, const float* lse,
+                         int64_t q_rs, int64_t k_rs, int64_t v_rs, int B, int N, float* dq, float* dk, float* dv, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // small ops (imgops.hip)

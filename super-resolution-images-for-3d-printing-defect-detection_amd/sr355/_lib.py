@@ -105,6 +105,8 @@ SIGNATURES = {
     "sr_matmul": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "sr_softmax_rows": (_i, [_vp, _vp, _i64, _i, _vp]),
     "sr_softmax_bwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
+    "sr_attention_fwd_lse": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "sr_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "sr_maxpool2_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_zero_insert2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_spectral_l1_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),

@@ -7,8 +7,9 @@ renormalising their kernels in place on each of the three training=True calls (S
 The forward and backward passes are host orchestration over the C ABI's single ops, fp32 as the reference trains:
   * convs: the MFMA forward kernels; input gradients are the same kernels on 180-degree-rotated, channel-swapped weights; kernel / bias
     gradients the fp32-MFMA wgrad kernel (csrc/train_ops.hip);
-  * SelfAttention of the small training patches is materialised (sr_matmul + row softmax) so that its backward is six GEMMs and a
-    softmax-backward kernel; pooling / stride-2 sampling / depth_to_space / activations / the (W,C)-FFT loss have their own adjoint kernels;
+  * SelfAttention of the small training patches is materialised by default (sr_matmul + row softmax) so that its backward is six GEMMs and a
+    softmax-backward kernel; attention_impl="streamed" runs it through sr_attention_fwd_lse / sr_attention_bwd instead, which keep no
+    [B,N,N] tensor (csrc/attention_train.hip); pooling / stride-2 sampling / depth_to_space / activations / the (W,C)-FFT loss have their own adjoint kernels;
   * a minimal reverse-mode tape (below) keeps the graph bookkeeping out of the kernels; torch is used for memory only (cat / slice /
     flip / expand: data movement).
 ESRGANTrainer.train_step is ONE body for both homes of the discriminator's tiny vectors -- its [B,256] dense head, BCE on [B,1], spectral-norm
@@ -31,6 +32,17 @@ from .train import Adam, DeviceAdam, ParamBucket, _rot
 
 
 # ----------------------------------------------------------------------------------------------------------------- tape
+ATTENTION_IMPLS = ("materialised", "streamed")
+
+
+def check_attention_impl(value):
+    """How the tape runs SelfAttention's core: "materialised" (the default: beta = softmax(g f^T) as a [B, N, N] tensor, its backward six GEMMs)
+    or "streamed" (sr_attention_fwd_lse / sr_attention_bwd: O(B N) state, no [B, N, N] tensor)."""
+    if value not in ATTENTION_IMPLS:
+        raise ValueError(f"attention_impl must be one of {ATTENTION_IMPLS}, got {value!r}")
+    return value
+
+
 class Var:
     __slots__ = ("v", "g", "need")
 
@@ -42,8 +54,9 @@ class Tape:
     """Reverse-mode bookkeeping: ops push a closure; backward() runs them last-to-first.  Parameter gradients land in `grads`
     ({layer: [dk, db]}, summed over uses) when `wgrad` is on."""
 
-    def __init__(self, ctx, weights, wgrad=True, devcache=None):
+    def __init__(self, ctx, weights, wgrad=True, devcache=None, attention_impl="materialised"):
         self.ctx, self.w, self.wgrad = ctx, weights, wgrad
+        self.attention_impl = check_attention_impl(attention_impl)
         self.ops, self.grads = [], {}
         self.masks = None                                       # diagnostics: a dict here collects {layer: activation > 0} of every ReLU / LeakyReLU conv
         self.dev = devcache if devcache is not None else {}     # id(host array) -> (host array, device tensor): one upload per array
@@ -172,24 +185,37 @@ class Tape:
         return y
 
     def attention(self, x, name):
-        """SelfAttention.call (ESRGAN_model.py:48-70), materialised: s = g f^T, beta = softmax(s), o = beta h, y = x + v(o)."""
+        """SelfAttention.call (ESRGAN_model.py:48-70): s = g f^T, beta = softmax(s), o = beta h, y = x + v(o).  attention_impl "materialised" keeps
+        beta as a [B,N,N] tensor; "streamed" keeps o and one softmax statistic per query and recomputes beta tile by tile in the backward kernels."""
         ctx = self.ctx
         B, H, W, C = x.v.shape
         N = H * W
         f, g, h = self.conv(x, name + "_f"), self.conv(x, name + "_g"), self.conv(x, name + "_h")
         f3, g3, h3 = f.v.reshape(B, N, -1), g.v.reshape(B, N, -1), h.v.reshape(B, N, -1)
-        beta = ctx.softmax_rows_(ctx.matmul(g3, f3, trans_b=True))            # [B,N,N]
-        o = Var(ctx.matmul(beta, h3).reshape(B, H, W, -1))
+        if self.attention_impl == "streamed":
+            o3, lse = ctx.attention_fwd_lse(g3, f3, h3)                       # [B,N,32], [B,N]
+            o = Var(o3.reshape(B, H, W, -1))
 
-        def bwd():
-            if o.g is None:
-                return
-            do = o.g.reshape(B, N, -1)
-            dbeta = ctx.matmul(do, h3, trans_b=True)                           # [B,N,N]
-            self._acc(h, ctx.matmul(beta, do, trans_a=True).reshape(h.v.shape))
-            ds = ctx.softmax_bwd(beta, dbeta)
-            self._acc(g, ctx.matmul(ds, f3).reshape(g.v.shape))
-            self._acc(f, ctx.matmul(ds, g3, trans_a=True).reshape(f.v.shape))
+            def bwd():
+                if o.g is None:
+                    return
+                dg, df, dh = ctx.attention_bwd(g3, f3, h3, o3, o.g.reshape(B, N, -1), lse)
+                self._acc(h, dh.reshape(h.v.shape))
+                self._acc(g, dg.reshape(g.v.shape))
+                self._acc(f, df.reshape(f.v.shape))
+        else:
+            beta = ctx.softmax_rows_(ctx.matmul(g3, f3, trans_b=True))            # [B,N,N]
+            o = Var(ctx.matmul(beta, h3).reshape(B, H, W, -1))
+
+            def bwd():
+                if o.g is None:
+                    return
+                do = o.g.reshape(B, N, -1)
+                dbeta = ctx.matmul(do, h3, trans_b=True)                           # [B,N,N]
+                self._acc(h, ctx.matmul(beta, do, trans_a=True).reshape(h.v.shape))
+                ds = ctx.softmax_bwd(beta, dbeta)
+                self._acc(g, ctx.matmul(ds, f3).reshape(g.v.shape))
+                self._acc(f, ctx.matmul(ds, g3, trans_a=True).reshape(f.v.shape))
         self.ops.append(bwd)
         ov = self.conv(o, name + "_v")
         return self.axpby(x, ov, 1.0, 1.0)
@@ -504,9 +530,10 @@ class ESRGANTrainer:
     dw, u, d_opt, d_params = (_discriminator_attr(name) for name in ("weights", "u", "opt", "params"))
 
     def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None, discriminator="host"):
+                 allreduce_flat=None, discriminator="host", attention_impl="materialised"):
         if discriminator not in ("host", "device"):
             raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
+        self.attention_impl = check_attention_impl(attention_impl)      # the generator tape's SelfAttention core (Tape.attention)
         self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
         self.discriminator = discriminator
         # Generator (16.9 M parameters at the default depth): resident on the device as ONE flat fp32 bucket with its Adam moments beside it;
@@ -574,7 +601,7 @@ class ESRGANTrainer:
 
     def generator_tape(self, wgrad=True):
         """A tape over the generator's device-resident parameters (no upload, no host copy)."""
-        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache))
+        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache), attention_impl=self.attention_impl)
 
     @property
     def last_grads(self):

@@ -1135,6 +1135,45 @@ class Context:
         self.check(self.lib.sr_softmax_bwd(self.h, p.data_ptr(), dp.data_ptr(), ds.data_ptr(), p.numel() // p.shape[-1], p.shape[-1], self.stream()))
         return ds
 
+    def _attention_operand(self, t, name, channels, B=None, N=None):
+        """q / k / v of the streamed attention: fp32 [B, N, channels], dense or a channel range of a wider [B, N, C] buffer (e.g. one of a fused
+        f | g | h tensor) -> its row stride in elements."""
+        if not isinstance(t, torch.Tensor) or t.device != self.torch_device or t.dtype != torch.float32:
+            raise ValueError(f"{name}: expected a float32 tensor on {self.torch_device}")
+        if t.dim() != 3 or t.shape[2] != channels or t.numel() == 0 or (B is not None and tuple(t.shape[:2]) != (B, N)):
+            raise ValueError(f"{name}: expected shape [B, N, {channels}]" + ("" if B is None else f" with B = {B}, N = {N}") + f", got {tuple(t.shape)}")
+        rs = t.stride(1)
+        if t.stride(2) != 1 or rs < channels or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * rs):
+            raise ValueError(f"{name}: rows must be unit-stride channel ranges of one [B, N, C] buffer")
+        return rs
+
+    def attention_fwd_lse(self, q, k, v):
+        """The SelfAttention core o = softmax(q k^T) v (ESRGAN_model.py:57-65; q = g, k = f: [B, N, 8], v = h: [B, N, 32], fp32) by the streaming
+        kernel, plus lse [B, N] = log sum_j exp(q_i . k_j), what attention_bwd needs to recompute the softmax: -> (o [B, N, 32], lse).  The operands
+        may be channel ranges of one fused buffer."""
+        q_rs = self._attention_operand(q, "attention q", 8)
+        B, N = q.shape[:2]
+        k_rs, v_rs = self._attention_operand(k, "attention k", 8, B, N), self._attention_operand(v, "attention v", 32, B, N)
+        o, lse = self.empty((B, N, 32)), self.empty((B, N))
+        self.check(self.lib.sr_attention_fwd_lse(self.h, q.data_ptr(), k.data_ptr(), v.data_ptr(), q_rs, k_rs, v_rs, B, N, o.data_ptr(), lse.data_ptr(),
+                                                 self.stream()))
+        return o, lse
+
+    def attention_bwd(self, q, k, v, o, do, lse):
+        """Gradients of attention_fwd_lse's o with respect to q, k, v given do = dL/do, streamed over key / query tiles (no [B, N, N] tensor, no
+        atomics: the same bits every run) -> (dq [B, N, 8], dk [B, N, 8], dv [B, N, 32])."""
+        q_rs = self._attention_operand(q, "attention q", 8)
+        B, N = q.shape[:2]
+        k_rs, v_rs = self._attention_operand(k, "attention k", 8, B, N), self._attention_operand(v, "attention v", 32, B, N)
+        for t, name, shape in ((o, "attention o", (B, N, 32)), (do, "attention do", (B, N, 32)), (lse, "attention lse", (B, N))):
+            _check_tensor(self, t, name)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: expected shape {shape}, got {tuple(t.shape)}")
+        dq, dk, dv = self.empty((B, N, 8)), self.empty((B, N, 8)), self.empty((B, N, 32))
+        self.check(self.lib.sr_attention_bwd(self.h, q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(), q_rs, k_rs,
+                                             v_rs, B, N, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), self.stream()))
+        return dq, dk, dv
+
     def maxpool2_bwd(self, x, dy):
         _check_tensor(self, x, "maxpool_bwd x")
         _check_tensor(self, dy, "maxpool_bwd dy")
