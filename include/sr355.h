@@ -244,6 +244,31 @@ int  sr_eltwise_views(sr_ctx* ctx, int op, const sr_view* a, const sr_view* b, f
  * start of every step) -- the library cannot see a write to w. */
 typedef struct { const float* w; const float* bias; int32_t K, Cin, Cout, rot; } sr_pack_desc;
 int  sr_conv_prepack(sr_ctx* ctx, const sr_pack_desc* uses, int n, void* stream);
+/* Mixed-precision training: Keras model.fit of EDSR_model.py:127-176 with bf16 activations and activation gradients between kernels, fp32 master weights, fp32 weight /
+ * bias gradients, fp32 loss and optimiser ("Mixed-precision training").  Every kernel widens its operands to fp32, accumulates and applies its epilogue in
+ * fp32 and rounds once, to nearest even, on store.  All asynchronous on `stream`; one stream per context.
+ * sr_conv2d_dev_bf16 (EDSR_model.py:127-176, the forward and input-gradient convs): sr_conv2d_dev with x, skip1, skip2 and y in bf16; d_w (fp32 device kernel, HWIO or with
+ *   rot = 1 the forward kernel of the layer whose input gradient is wanted) and d_bias stay fp32.  The kernel is rounded to bf16 once by a device pack kernel, into the very
+ *   image sr_conv2d packs on the host, and runs on the bf16 conv kernels sr_conv2d runs: the same bits as sr_conv2d on the same values.
+ * sr_conv_prepack_bf16 (EDSR_model.py:127-176, once per step): sr_conv_prepack for sr_conv2d_dev_bf16 -- one launch for all of a step's uses; every call replaces the whole
+ *   bf16 list, n = 0 forgets it.  The bf16 list and sr_conv_prepack's fp32 list are separate: the same (w, K, Cin, Cout, rot) may stand in both.
+ * sr_conv2d_wgrad_bf16 (EDSR_model.py:127-176, the kernel and bias gradients): dw HWIO [3,3,Cin,Cout] = scale * sum over pixels of x[b, y+ky-1, x+kx-1, ci] * dy[b,y,x,co] and
+ *   db [Cout] = scale * sum of dy (NULL to skip), fp32, from bf16 x [B,H,W,x_cs] and dy [B,H,W,dy_cs] of which the first Cin / Cout channels of every pixel count (a
+ *   channel-padded input buffer: x_cs = 8, Cin = 3).  Products of bf16 values are exact in fp32; only the fp32 summation rounds, in a fixed order (no atomics).  K must be 3.
+ * sr_relu_bwd_bf16 (EDSR_model.py:127-176, ReLU's gradient): out = dy where y > 0, else +0, on n bf16 elements; a select, no rounding.
+ * sr_space_to_depth_bf16 (EDSR_model.py:127-176, depth_to_space's gradient): sr_space_to_depth on bf16, a permutation.
+ * sr_mse_clip_grad_bf16 (EDSR_model.py:127-176, the clip, loss = mean_squared_error and its gradient): pre bf16 [n], t fp32 [n] (the target is NOT rounded) ->
+ *   loss1 fp32 [1] = mean((clip(pre, 0, 1) - t)^2), summed in fp64 in a fixed order; dpre bf16 [n] = bf16(fp32(2 / n) * (clip(pre, 0, 1) - t)) where 0 <= pre <= 1, else 0;
+ *   y fp32 [n] = clip(pre, 0, 1) (NULL to skip). */
+int  sr_conv2d_dev_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, const float* d_w, const float* d_bias, int K, int Cout,
+                        int rot, int act, float alpha, const void* skip1, float beta1, const void* skip2, float beta2, int clip01,
+                        int d2s_r, void* y, void* stream);
+int  sr_conv_prepack_bf16(sr_ctx* ctx, const sr_pack_desc* uses, int n, void* stream);
+int  sr_conv2d_wgrad_bf16(sr_ctx* ctx, const void* x, int64_t x_cs, const void* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, int K, float scale,
+                          float* dw_hwio, float* db, void* stream);
+int  sr_relu_bwd_bf16(sr_ctx* ctx, const void* dy, const void* y, void* out, int64_t n, void* stream);
+int  sr_space_to_depth_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int C, int r, void* y, void* stream);
+int  sr_mse_clip_grad_bf16(sr_ctx* ctx, const void* pre, const float* t, int64_t n, float* loss1, void* dpre, float* y, void* stream);
 int  sr_eltwise(sr_ctx* ctx, int op, const void* a, const void* b, float alpha, float beta, void* out, int64_t n, void* stream);
 /* keras.optimizers.Adam's dense update (the optimiser of ESRGAN_model.py:176-195, SRCNN_model.py:55-60, EDSR_model.py:127-140) over one flat
  * fp32 bucket of n parameters, in place on the device: g is first multiplied by grad_scale (1 / world size after a summing all-reduce; 1 leaves

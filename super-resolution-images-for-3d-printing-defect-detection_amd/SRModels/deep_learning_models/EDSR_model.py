@@ -16,12 +16,20 @@ class EDSR(DeviceModelMixin):
     _init_scheme = "he_normal"   # kernel_initializer="he_normal" (EDSR_model.py:61)
     clipnorm = 1.0               # Adam(clipnorm=1.0) (EDSR_model.py:130-136)
 
-    def __init__(self, compute_dtype="f32", update="host"):
-        """update: where fit() applies Adam and its per-variable clip-by-norm -- "host" (NumPy on downloaded gradients, the default) or "device"
+    def __init__(self, compute_dtype="f32", update="host", train_dtype="f32"):
+        """train_dtype: "f32" (the default: the reference's fp32 training) or "bf16" -- mixed precision: bf16 activations and activation gradients between
+        kernels, fp32 master weights, gradients, clip-by-norm and Adam (sr355.train.edsr_loss_and_grads_bf16); needs update="device".  Independent of
+        compute_dtype, which governs the inference model.
+        update: where fit() applies Adam and its per-variable clip-by-norm -- "host" (NumPy on downloaded gradients, the default) or "device"
         (one flat parameter bucket for the whole fit: sr_clip_by_norm_bucket, then sr_adam, in place).  The device clip factor can differ from
         the host's by one fp32 ulp (its fp64 norm is summed in another order); where no factor differs the weights are the same bits."""
         if update not in ("host", "device"):
             raise ValueError("update must be 'host' or 'device'")
+        if train_dtype not in ("f32", "bf16"):
+            raise ValueError("train_dtype must be 'f32' or 'bf16'")
+        if train_dtype == "bf16" and update != "device":
+            raise ValueError("train_dtype='bf16' keeps its fp32 master weights and optimiser on the device: it needs update='device'")
+        self.train_dtype = train_dtype
         self.model = None
         self.scale_factor = None
         self.trained = False
@@ -69,9 +77,13 @@ class EDSR(DeviceModelMixin):
             start, opt = self.weights, T.Adam(self.weights, learning_rate=self.learning_rate, epsilon=1e-8, clipnorm=self.clipnorm)
         opt.scales_log = self.clip_scales_log
         self._optimizer = opt
-        lg = partial(T.edsr_loss_and_grads, scale=self.scale_factor, num_res_blocks=self.num_res_blocks, res_scaling=self.res_scaling)
-        weights, history, tcb, mcb = T.fit(self.ctx, start, lg, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
-                                           batch_size=batch_size, epochs=epochs, es_patience=5, lr_patience=3, shuffle=shuffle, verbose=verbose)
+        lg = partial(T.edsr_loss_and_grads_bf16 if self.train_dtype == "bf16" else T.edsr_loss_and_grads, scale=self.scale_factor, num_res_blocks=self.num_res_blocks, res_scaling=self.res_scaling)
+        try:
+            weights, history, tcb, mcb = T.fit(self.ctx, start, lg, self._predict_with, opt, X_train, Y_train, X_val, Y_val,
+                                               batch_size=batch_size, epochs=epochs, es_patience=5, lr_patience=3, shuffle=shuffle, verbose=verbose)
+        finally:
+            if self.train_dtype == "bf16":
+                self.ctx.conv_prepack_bf16(None)     # the step's prepack list names this fit's bucket: forget it with the bucket
         self.set_weights(weights)
         self.trained = True
         return history, tcb, mcb

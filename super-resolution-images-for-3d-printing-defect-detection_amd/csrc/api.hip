@@ -1283,8 +1283,74 @@ int sr_conv2d_dev_views(sr_ctx* ctx, const sr_view* x, int B, int H, int W, int 
 int sr_conv_prepack(sr_ctx* ctx, const sr_pack_desc* uses, int n, void* stream) {
     DeviceGuard dg_(ctx);
     if (!ctx) return SR_ERR_INVALID;
-    if (n < 0 || (n > 0 && !uses)) { ctx->pack_cache.clear(); return ctx->fail(SR_ERR_INVALID, "conv prepack: bad list"); }
+    if (n < 0 || (n > 0 && !uses)) { ctx->pack32.cache.clear(); return ctx->fail(SR_ERR_INVALID, "conv prepack: bad list"); }
     return conv_prepack_dev(ctx, uses, n, static_cast<hipStream_t>(stream));
+}
+
+// Mixed-precision training (bf16 activations, fp32 master weights): sr_conv2d_dev on bf16 tensors.  The fp32 device kernel is rounded to bf16 by the device pack kernel
+// into the image conv_pack_weights makes on the host, the input is padded as sr_conv2d pads it, and conv_launch picks the kernel as it does for sr_conv2d: the result is
+// sr_conv2d's on the same numbers, bit for bit.
+int sr_conv2d_dev_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, const float* d_w, const float* d_bias, int K, int Cout, int rot,
+                       int act, float alpha, const void* skip1, float beta1, const void* skip2, float beta2, int clip01, int d2s_r, void* y,
+                       void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!x || !d_w || !y) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return ctx->fail(SR_ERR_INVALID, "bad tensor shape");
+    ConvWeights cw;
+    int rc = conv_pack_weights_dev_bf16(ctx, d_w, d_bias, K, Cin, Cout, rot, &cw, st);
+    if (rc) return rc;
+    const int Cp = padded_cin(cw);
+    const void* xp = x;
+    if (Cp != Cin || ((uintptr_t)x % 16) != 0) {          // channel padding needed: a padded copy in the arena (else the conv reads x in place)
+        void* xa = ctx->arena(ctx->dev_x, (size_t)B * H * W * Cp * 2 + 4096, st);
+        if (!xa) return SR_ERR_OOM;
+        rc = convert_pad_launch(ctx, x, SR_DTYPE_BF16, (int64_t)B * H * W, Cin, xa, SR_DTYPE_BF16, Cp, 1.f, 0.f, st);
+        if (rc) return rc;
+        xp = xa;
+    }
+    auto skip_view = [&](const void* s) { return (s == x && Cout == Cin) ? TensorView{xp, Cp, 0} : TensorView{s, Cout, 0}; };      // (as sr_conv2d presents a skip that is the input)
+    const ConvEpilogue ep = single_op_epilogue(act, alpha, clip01, d2s_r, skip_view(skip1), beta1, skip_view(skip2), beta2);
+    const int r = ep.d2s_r;
+    return conv_launch(ctx, cw, TensorView{xp, Cp, 0}, B, H, W, y, Cout / (r * r), 0, ep, st);
+}
+
+int sr_conv_prepack_bf16(sr_ctx* ctx, const sr_pack_desc* uses, int n, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (n < 0 || (n > 0 && !uses)) { ctx->pack16.cache.clear(); return ctx->fail(SR_ERR_INVALID, "conv prepack: bad list"); }
+    return conv_prepack_dev_bf16(ctx, uses, n, static_cast<hipStream_t>(stream));
+}
+
+int sr_conv2d_wgrad_bf16(sr_ctx* ctx, const void* x, int64_t x_cs, const void* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, int K, float scale, float* dw_hwio,
+                         float* db, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!x || !dy || !dw_hwio) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    if (K != 3) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: 3x3 layers only");
+    return wgrad_bf16_launch(ctx, static_cast<const bf16_t*>(x), x_cs, static_cast<const bf16_t*>(dy), dy_cs, B, H, W, Cin, Cout, scale, dw_hwio, db, static_cast<hipStream_t>(stream));
+}
+
+int sr_relu_bwd_bf16(sr_ctx* ctx, const void* dy, const void* y, void* out, int64_t n, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!dy || !y || !out) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return relu_bwd_bf16_launch(ctx, static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(y), static_cast<bf16_t*>(out), n, static_cast<hipStream_t>(stream));
+}
+
+int sr_space_to_depth_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int C, int r, void* y, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!x || !y) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return space_to_depth_bf16_launch(ctx, static_cast<const bf16_t*>(x), B, H, W, C, r, static_cast<bf16_t*>(y), static_cast<hipStream_t>(stream));
+}
+
+int sr_mse_clip_grad_bf16(sr_ctx* ctx, const void* pre, const float* t, int64_t n, float* loss1, void* dpre, float* y, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!pre || !t || !loss1 || !dpre) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    return mse_clip_grad_bf16_launch(ctx, static_cast<const bf16_t*>(pre), t, n, loss1, static_cast<bf16_t*>(dpre), y, static_cast<hipStream_t>(stream));
 }
 
 int sr_conv2d_wgrad_views(sr_ctx* ctx, const sr_view* x, const sr_view* dy, int B, int H, int W, int Cin, int Cout, int K, float* dw_hwio, float* db, void* stream) {

@@ -79,10 +79,13 @@ struct sr_ctx {
             return std::hash<const void*>()(k.w) ^ (std::hash<const void*>()(k.b) * 31u) ^ ((size_t)k.rot << 1) ^ ((size_t)k.Cin << 20) ^ ((size_t)k.Cout << 36) ^ ((size_t)k.K << 52);
         }
     };
-    std::unordered_map<PackKey, std::pair<void*, float*>, PackKeyHash> pack_cache;
-    Arena pack_w, pack_b, pack_tab;
-    std::vector<char> pack_tab_host;     // the job table as last uploaded
-    void* pack_tab_dev = nullptr;
+    struct PackSet {
+        std::unordered_map<PackKey, std::pair<void*, float*>, PackKeyHash> cache;
+        Arena w, b, tab;
+        std::vector<char> tab_host;      // the job table as last uploaded
+        void* tab_dev = nullptr;
+    };
+    PackSet pack32, pack16;              // the lists of sr_conv_prepack (fp32 images) and sr_conv_prepack_bf16 (bf16 images): one never answers for the other
     static constexpr int ZERO_PAGE_BYTES = 32768;
     void* zero_page = nullptr;    // ZERO_PAGE_BYTES of zeros (DMA source of padding rows / halo pixels in dense_fused.hip, conv_stream.hip): allocated and cleared
                                   // synchronously in sr_init, so that no launch on any stream can see it before it is zero
@@ -231,6 +234,9 @@ struct ConvEpilogue {
 // the context's arenas (valid until the next sr_conv2d_dev on the stream)
 int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st);
 int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st);
+// the same two with a bf16 packed image, rounded to nearest even on the device (sr_conv2d_dev_bf16, sr_conv_prepack_bf16); their list is a separate one
+int conv_pack_weights_dev_bf16(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st);
+int conv_prepack_dev_bf16(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st);
 // on the host (f32 and bf16), into tracked allocations that conv_free_weights releases.
 // rows_head = 1 (bf16 3x3 only): a conv whose Cin fits one 16-byte slice (an RGB head) is packed for the row-sliding kernel on one
 // zero-padded 32-channel chunk instead of the thin kernel -- the caller then provides a 32-channel input view
@@ -336,6 +342,12 @@ int adam_launch(sr_ctx* ctx, float* w, const float* g, float* m, float* v, int64
                 float gscale, hipStream_t st);
 int eltwise_launch(sr_ctx* ctx, int op, const float* a, const float* b, float alpha, float beta, float* out, int64_t n, hipStream_t st);
 int space_to_depth_launch(sr_ctx* ctx, const float* x, int B, int H, int W, int C, int r, float* y, hipStream_t st);
+// wgrad_bf16.hip: the bf16-storage pieces of a mixed-precision training step (include/sr355.h)
+int wgrad_bf16_launch(sr_ctx* ctx, const bf16_t* x, int64_t x_cs, const bf16_t* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, float scale, float* dw, float* db,
+                      hipStream_t st);
+int relu_bwd_bf16_launch(sr_ctx* ctx, const bf16_t* dy, const bf16_t* y, bf16_t* out, int64_t n, hipStream_t st);
+int space_to_depth_bf16_launch(sr_ctx* ctx, const bf16_t* x, int B, int H, int W, int C, int r, bf16_t* y, hipStream_t st);
+int mse_clip_grad_bf16_launch(sr_ctx* ctx, const bf16_t* pre, const float* t, int64_t n, float* loss, bf16_t* dpre, float* y, hipStream_t st);
 int matmul_launch(sr_ctx* ctx, const float* A, const float* B, float* C, int batch, int M, int N, int K, int tA, int tB, float alpha, hipStream_t st);
 int softmax_rows_launch(sr_ctx* ctx, float* s, int64_t rows, int cols, hipStream_t st);
 int softmax_bwd_launch(sr_ctx* ctx, const float* p, const float* dp, float* ds, int64_t rows, int cols, hipStream_t st);

@@ -790,13 +790,33 @@ __global__ void pack_weights_f32_kernel(const float* __restrict__ src, float* __
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) dst[idx] = pack_source(src, conv_pack_decode(idx, q), q);
 }
 
+// The same packing with a bf16 destination (sr_conv2d_dev_bf16: mixed-precision training keeps fp32 master weights and rounds every kernel once per step): the source
+// value is rounded to nearest even exactly as f32_to_bf16_host rounds it, so for the same fp32 kernel the packed image is the bits conv_pack_weights makes on the host.
+__device__ __forceinline__ uint16_t f32_to_bf16_dev(float f) {
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+__global__ void pack_weights_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n, PackPlan q, const float* __restrict__ bias, float* __restrict__ bias_out) {
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < q.CoutP; i += blockDim.x) bias_out[i] = (bias && i < q.Cout) ? bias[i] : 0.f;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x)
+        dst[idx] = f32_to_bf16_dev(pack_source(src, conv_pack_decode(idx, q), q));
+}
+
 // Many convs' weights by ONE launch (sr_conv_prepack: a training step's ~800 per-use packs were 3.9 ms of 4.9-us launches): job j owns blocks [blk0, next job's blk0),
 // PACK_JOB_ELEMS packed elements per block; a block finds its job by bisection of the table.
 constexpr int PACK_JOB_ELEMS = 2048;
-struct PackJob { const float* src; const float* bias; float* dst; float* bias_out; int64_t n; PackPlan q; int blk0; };
+struct PackJob { const float* src; const float* bias; void* dst; float* bias_out; int64_t n; PackPlan q; int blk0; };
 static_assert(sizeof(PackJob) == 4 * sizeof(void*) + sizeof(int64_t) + sizeof(PackPlan) + sizeof(int), "conv_prepack_dev compares job tables bytewise: no padding");
 
-__global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJob* __restrict__ jobs, int njobs) {
+struct PackKeepF32 { typedef float T; __device__ static float round(float v) { return v; } };
+struct PackRoundBf16 { typedef uint16_t T; __device__ static uint16_t round(float v) { return f32_to_bf16_dev(v); } };
+
+template <typename R>
+__device__ __forceinline__ void pack_job_block(const PackJob* __restrict__ jobs, int njobs) {
     int lo = 0, hi = njobs - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
@@ -806,7 +826,7 @@ __global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJo
     const PackPlan q = jb.q;
     const int lb = (int)blockIdx.x - jb.blk0;
     const float* __restrict__ src = jb.src;
-    float* __restrict__ dst = jb.dst;
+    typename R::T* __restrict__ dst = static_cast<typename R::T*>(jb.dst);
     const int64_t n = jb.n;
     if (lb == 0) {
         const float* bias = jb.bias;
@@ -816,18 +836,23 @@ __global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJo
     const int64_t base = (int64_t)lb * PACK_JOB_ELEMS;
 #pragma unroll 4
     for (int i = threadIdx.x; i < PACK_JOB_ELEMS; i += 256)
-        if (base + i < n) dst[base + i] = pack_source(src, conv_pack_decode(base + i, q), q);
+        if (base + i < n) dst[base + i] = R::round(pack_source(src, conv_pack_decode(base + i, q), q));
 }
 
-int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st) {
+__global__ void __launch_bounds__(256) pack_weights_f32_many_kernel(const PackJob* __restrict__ jobs, int njobs) { pack_job_block<PackKeepF32>(jobs, njobs); }
+__global__ void __launch_bounds__(256) pack_weights_bf16_many_kernel(const PackJob* __restrict__ jobs, int njobs) { pack_job_block<PackRoundBf16>(jobs, njobs); }
+
+// One use's pack: the prepacked image of this dtype's list when the use is on it, else a pack of its own into the call arenas
+static int pack_weights_dev(sr_ctx* ctx, int dtype, sr_ctx::PackSet& ps, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out,
+                            hipStream_t st) {
     ConvWeights w;
     PackPlan plan;
     int64_t n;
-    const int rc = conv_plan(ctx, SR_DTYPE_F32, KS, Cin, Cout, 0, rot, &w, &plan, &n);
+    const int rc = conv_plan(ctx, dtype, KS, Cin, Cout, 0, rot, &w, &plan, &n);
     if (rc) return rc;
-    if (!ctx->pack_cache.empty()) {                                   // sr_conv_prepack: this use was packed with the step's other weights
-        const auto it = ctx->pack_cache.find(sr_ctx::PackKey{d_hwio, d_bias, KS, Cin, Cout, rot});
-        if (it != ctx->pack_cache.end()) {
+    if (!ps.cache.empty()) {                                          // sr_conv_prepack: this use was packed with the step's other weights
+        const auto it = ps.cache.find(sr_ctx::PackKey{d_hwio, d_bias, KS, Cin, Cout, rot});
+        if (it != ps.cache.end()) {
             w.w = it->second.first; w.bias = it->second.second;
             *out = w;
             return SR_OK;
@@ -836,15 +861,29 @@ int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias,
     w.w = ctx->arena(ctx->dev_w, w.bytes, st);
     w.bias = static_cast<float*>(ctx->arena(ctx->dev_b, sizeof(float) * round_up(w.CoutP, 64), st));
     if (!w.w || !w.bias) return SR_ERR_OOM;
-    const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(pack_weights_f32_kernel, dim3(blocks), dim3(256), 0, st, d_hwio, static_cast<float*>(w.w), n, plan, d_bias, w.bias);
+    if (dtype == SR_DTYPE_F32) {
+        const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(pack_weights_f32_kernel, dim3(blocks), dim3(256), 0, st, d_hwio, static_cast<float*>(w.w), n, plan, d_bias, w.bias);
+    } else {                                                          // one thread per packed element, no second round: the grid is not clamped
+        const int64_t threads16 = n + 255;
+        if (threads16 / 256 > 0x7fffffff) return ctx->fail(SR_ERR_INVALID, "conv pack: too many elements for one launch");
+        hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3((unsigned)(threads16 / 256)), dim3(256), 0, st, d_hwio, static_cast<uint16_t*>(w.w), n, plan, d_bias, w.bias);
+    }
     SR_HIP(ctx, hipGetLastError());
     *out = w;
     return SR_OK;
 }
 
-int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st) {
-    ctx->pack_cache.clear();                                          // whatever happens below, no stale pack survives this call
+int conv_pack_weights_dev(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st) {
+    return pack_weights_dev(ctx, SR_DTYPE_F32, ctx->pack32, d_hwio, d_bias, KS, Cin, Cout, rot, out, st);
+}
+
+int conv_pack_weights_dev_bf16(sr_ctx* ctx, const float* d_hwio, const float* d_bias, int KS, int Cin, int Cout, int rot, ConvWeights* out, hipStream_t st) {
+    return pack_weights_dev(ctx, SR_DTYPE_BF16, ctx->pack16, d_hwio, d_bias, KS, Cin, Cout, rot, out, st);
+}
+
+static int prepack_dev(sr_ctx* ctx, int dtype, sr_ctx::PackSet& ps, const sr_pack_desc* descs, int n, hipStream_t st) {
+    ps.cache.clear();                                                 // whatever happens below, no stale pack survives this call
     if (n <= 0) return SR_OK;
     std::vector<PackJob> jobs((size_t)n);
     std::vector<sr_ctx::PackKey> keys((size_t)n);
@@ -856,7 +895,7 @@ int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t 
         if (!d.w || d.Cin <= 0 || d.Cout <= 0) return ctx->fail(SR_ERR_INVALID, "conv prepack: null kernel or bad shape");
         ConvWeights w;
         PackJob& jb = jobs[(size_t)i];
-        const int rc = conv_plan(ctx, SR_DTYPE_F32, d.K, d.Cin, d.Cout, 0, d.rot ? 1 : 0, &w, &jb.q, &jb.n);
+        const int rc = conv_plan(ctx, dtype, d.K, d.Cin, d.Cout, 0, d.rot ? 1 : 0, &w, &jb.q, &jb.n);
         if (rc) return rc;
         jb.src = d.w; jb.bias = d.bias; jb.blk0 = (int)blocks;
         blocks += (jb.n + PACK_JOB_ELEMS - 1) / PACK_JOB_ELEMS;
@@ -866,27 +905,31 @@ int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t 
         keys[(size_t)i] = sr_ctx::PackKey{d.w, d.bias, d.K, d.Cin, d.Cout, d.rot ? 1 : 0};
     }
     if (blocks > 0x7fffffff) return ctx->fail(SR_ERR_INVALID, "conv prepack: too many elements for one launch");
-    char* wb = static_cast<char*>(ctx->arena(ctx->pack_w, wbytes, st));
-    char* bb = static_cast<char*>(ctx->arena(ctx->pack_b, bbytes, st));
+    char* wb = static_cast<char*>(ctx->arena(ps.w, wbytes, st));
+    char* bb = static_cast<char*>(ctx->arena(ps.b, bbytes, st));
     const size_t tbytes = sizeof(PackJob) * (size_t)n;
-    void* tab = ctx->arena(ctx->pack_tab, tbytes, st);
+    void* tab = ctx->arena(ps.tab, tbytes, st);
     if (!wb || !bb || !tab) return SR_ERR_OOM;
     for (int i = 0; i < n; ++i) {
-        jobs[(size_t)i].dst = reinterpret_cast<float*>(wb + woff[(size_t)i]);
+        jobs[(size_t)i].dst = wb + woff[(size_t)i];
         jobs[(size_t)i].bias_out = reinterpret_cast<float*>(bb + boff[(size_t)i]);
     }
     // the table is uploaded when it differs from the one on the device (a trainer's list is the same every step: pointers into its parameter bucket)
-    if (ctx->pack_tab_host.size() != tbytes || ctx->pack_tab_dev != tab || memcmp(ctx->pack_tab_host.data(), jobs.data(), tbytes) != 0) {
+    if (ps.tab_host.size() != tbytes || ps.tab_dev != tab || memcmp(ps.tab_host.data(), jobs.data(), tbytes) != 0) {
         SR_HIP(ctx, hipStreamSynchronize(st));                         // an earlier launch may still be reading the old table
         SR_HIP(ctx, hipMemcpy(tab, jobs.data(), tbytes, hipMemcpyHostToDevice));
-        ctx->pack_tab_host.assign(reinterpret_cast<const char*>(jobs.data()), reinterpret_cast<const char*>(jobs.data()) + tbytes);
-        ctx->pack_tab_dev = tab;
+        ps.tab_host.assign(reinterpret_cast<const char*>(jobs.data()), reinterpret_cast<const char*>(jobs.data()) + tbytes);
+        ps.tab_dev = tab;
     }
-    hipLaunchKernelGGL(pack_weights_f32_many_kernel, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const PackJob*>(tab), n);
+    if (dtype == SR_DTYPE_F32) hipLaunchKernelGGL(pack_weights_f32_many_kernel, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const PackJob*>(tab), n);
+    else hipLaunchKernelGGL(pack_weights_bf16_many_kernel, dim3((unsigned)blocks), dim3(256), 0, st, static_cast<const PackJob*>(tab), n);
     SR_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < n; ++i) ctx->pack_cache[keys[(size_t)i]] = {jobs[(size_t)i].dst, jobs[(size_t)i].bias_out};
+    for (int i = 0; i < n; ++i) ps.cache[keys[(size_t)i]] = {jobs[(size_t)i].dst, jobs[(size_t)i].bias_out};
     return SR_OK;
 }
+
+int conv_prepack_dev(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st) { return prepack_dev(ctx, SR_DTYPE_F32, ctx->pack32, descs, n, st); }
+int conv_prepack_dev_bf16(sr_ctx* ctx, const sr_pack_desc* descs, int n, hipStream_t st) { return prepack_dev(ctx, SR_DTYPE_BF16, ctx->pack16, descs, n, st); }
 
 int conv_launch(sr_ctx* ctx, const ConvWeights& w, TensorView x, int B, int H, int W, void* y, int64_t y_cs, int y_coff,
                 const ConvEpilogue& ep, hipStream_t st) {

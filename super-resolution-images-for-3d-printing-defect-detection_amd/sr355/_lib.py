@@ -96,6 +96,12 @@ SIGNATURES = {
     "sr_conv2d_wgrad_maps": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_conv2d_dev_views": (_i, [_vp, _vw, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vw, _f, _vw, _vp]),
     "sr_conv_prepack": (_i, [_vp, C.POINTER(PackDesc), _i, _vp]),
+    "sr_conv2d_dev_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _f, _vp, _f, _i, _i, _vp, _vp]),
+    "sr_conv_prepack_bf16": (_i, [_vp, C.POINTER(PackDesc), _i, _vp]),
+    "sr_conv2d_wgrad_bf16": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    "sr_relu_bwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "sr_space_to_depth_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_mse_clip_grad_bf16": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "sr_conv2d_wgrad_views": (_i, [_vp, _vw, _vw, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_eltwise_views": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
     "sr_eltwise": (_i, [_vp, _i, _vp, _vp, _f, _f, _vp, _i64, _vp]),

@@ -813,6 +813,108 @@ class Context:
         self.check(self.lib.sr_adam(self.h, w.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), w.numel(), f(lr_t), f(beta_1), f(1.0 - beta_1),
                                     f(beta_2), f(1.0 - beta_2), f(epsilon), f(grad_scale), self.stream()))
 
+    # ------------------------------------------------------------------ mixed-precision training pieces (sr355/train.py, edsr_loss_and_grads_bf16)
+    _BF16 = (torch.bfloat16,)
+
+    def conv2d_dev_bf16(self, x, w_dev, b_dev, cout, rot=False, act="linear", d2s=1, alpha=1.0, skip1=None, beta1=0.0, skip2=None, beta2=0.0):
+        """conv2d_dev on bf16 tensors with the fp32 DEVICE kernel w_dev ([K,K,Cin,Cout], or with rot=True the forward kernel [K,K,Cout,Cin] of the layer whose
+        input gradient is wanted) and fp32 bias: the kernel is rounded to bf16 once on the device, the conv accumulates in fp32, applies
+        alpha * act(conv + b) + beta1 * skip1 + beta2 * skip2 in fp32 and rounds once (sr_conv2d_dev_bf16)."""
+        _check_tensor(self, x, "conv2d_dev_bf16 input", self._BF16)
+        _check_tensor(self, w_dev, "conv2d_dev_bf16 kernel")
+        if b_dev is not None:
+            _check_tensor(self, b_dev, "conv2d_dev_bf16 bias")
+        if x.dim() != 4 or w_dev.dim() != 4:
+            raise ValueError("conv2d_dev_bf16: x must be [B,H,W,C], the kernel [K,K,I,O]")
+        B, H, W, Cx = x.shape
+        k = w_dev.shape[0]
+        want = (k, k, cout, Cx) if rot else (k, k, Cx, cout)
+        if tuple(w_dev.shape) != want:
+            raise ValueError(f"conv2d_dev_bf16: kernel shape {tuple(w_dev.shape)} does not match {want}")
+        r = max(1, int(d2s))
+        for nm, sk in (("skip1", skip1), ("skip2", skip2)):
+            if sk is not None:
+                _check_tensor(self, sk, f"conv2d_dev_bf16 {nm}", self._BF16)
+                if tuple(sk.shape) != (B, H * r, W * r, cout // (r * r)):
+                    raise ValueError(f"conv2d_dev_bf16: {nm} must have the output's shape")
+        y = self.empty((B, H * r, W * r, cout // (r * r)), torch.bfloat16)
+        actc = {"linear": L.ACT_LINEAR, None: L.ACT_LINEAR, "relu": L.ACT_RELU, "lrelu": L.ACT_LRELU, "tanh": L.ACT_TANH}[act]
+        self.check(self.lib.sr_conv2d_dev_bf16(self.h, x.data_ptr(), B, H, W, Cx, w_dev.data_ptr(), None if b_dev is None else b_dev.data_ptr(), k,
+                                               int(cout), int(bool(rot)), actc, float(alpha), None if skip1 is None else skip1.data_ptr(), float(beta1),
+                                               None if skip2 is None else skip2.data_ptr(), float(beta2), 0, r, y.data_ptr(), self.stream()))
+        return y
+
+    def conv_prepack_bf16(self, packed_list):
+        """sr_conv_prepack_bf16: conv_prepack for conv2d_dev_bf16 (a pack_list; None forgets the bf16 list).  The fp32 list of conv_prepack is a separate one."""
+        if packed_list is None:
+            self.check(self.lib.sr_conv_prepack_bf16(self.h, None, 0, self.stream()))
+            return
+        arr, n, _ = packed_list
+        self.check(self.lib.sr_conv_prepack_bf16(self.h, arr, n, self.stream()))
+
+    def conv2d_wgrad_bf16(self, x, dy, k=3, scale=1.0, cin=None, out=None):
+        """Kernel and bias gradient of Conv2D(3 x 3, SAME, stride 1) from bf16 x [B,H,W,Cx] and dy [B,H,W,Cout] -> fp32 (dw HWIO, db), both times `scale`
+        (sr_conv2d_wgrad_bf16).  cin: the channels of x that count (x a channel-padded buffer; default all).  out: a (dw, db) pair to write into."""
+        _check_tensor(self, x, "wgrad_bf16 x", self._BF16)
+        _check_tensor(self, dy, "wgrad_bf16 dy", self._BF16)
+        if x.dim() != 4 or dy.dim() != 4 or tuple(dy.shape[:3]) != tuple(x.shape[:3]):
+            raise ValueError("wgrad_bf16: x and dy must share [B,H,W]")
+        if int(k) != 3:
+            raise ValueError("wgrad_bf16: 3x3 layers only")
+        B, H, W, cx = x.shape
+        cin = cx if cin is None else int(cin)
+        if not 0 < cin <= cx:
+            raise ValueError(f"wgrad_bf16: cin {cin} outside the buffer's {cx} channels")
+        cout = dy.shape[3]
+        if out is None:
+            dw, db = self.empty((3, 3, cin, cout), torch.float32), self.empty((cout,), torch.float32)
+        else:
+            dw, db = out
+            _check_tensor(self, dw, "wgrad_bf16 out dw")
+            _check_tensor(self, db, "wgrad_bf16 out db")
+            if tuple(dw.shape) != (3, 3, cin, cout) or tuple(db.shape) != (cout,):
+                raise ValueError("wgrad_bf16: out must be (dw [3,3,Cin,Cout], db [Cout])")
+        self.check(self.lib.sr_conv2d_wgrad_bf16(self.h, x.data_ptr(), cx, dy.data_ptr(), cout, B, H, W, cin, cout, 3, float(scale), dw.data_ptr(), db.data_ptr(),
+                                                 self.stream()))
+        return dw, db
+
+    def relu_bwd_bf16(self, dy, y):
+        """dy where y > 0, else 0, on bf16 tensors of one shape (sr_relu_bwd_bf16)."""
+        _check_tensor(self, dy, "relu_bwd_bf16 dy", self._BF16)
+        _check_tensor(self, y, "relu_bwd_bf16 y", self._BF16)
+        if y.shape != dy.shape:
+            raise ValueError("relu_bwd_bf16: operands must have the same shape")
+        out = torch.empty_like(dy)
+        self.check(self.lib.sr_relu_bwd_bf16(self.h, dy.data_ptr(), y.data_ptr(), out.data_ptr(), dy.numel(), self.stream()))
+        return out
+
+    def space_to_depth_bf16(self, x, r):
+        """space_to_depth on a bf16 tensor (sr_space_to_depth_bf16)."""
+        _check_tensor(self, x, "space_to_depth_bf16 input", self._BF16)
+        if x.dim() != 4:
+            raise ValueError("space_to_depth_bf16: x must be [B,H,W,C]")
+        B, Hr, Wr, Cx = x.shape
+        r = int(r)
+        if r < 1 or Hr % r or Wr % r:
+            raise ValueError("space_to_depth_bf16: spatial size not divisible by the block")
+        y = self.empty((B, Hr // r, Wr // r, r * r * Cx), torch.bfloat16)
+        self.check(self.lib.sr_space_to_depth_bf16(self.h, x.data_ptr(), B, Hr // r, Wr // r, Cx, r, y.data_ptr(), self.stream()))
+        return y
+
+    def mse_clip_grad_bf16(self, pre, t, want_y=True):
+        """pre bf16, t fp32 (same shape) -> (y fp32 = clip(pre, 0, 1) or None, loss fp32 [1] = mean((y - t)^2), dpre bf16 = 2 / n * (y - t) inside the clip
+        range, else 0) by one kernel and its reduction (sr_mse_clip_grad_bf16)."""
+        _check_tensor(self, pre, "mse_clip_grad_bf16 pre", self._BF16)
+        _check_tensor(self, t, "mse_clip_grad_bf16 target")
+        if t.shape != pre.shape:
+            raise ValueError("mse_clip_grad_bf16: pre and the target must have the same shape")
+        loss = self.empty((1,), torch.float32)
+        dpre = torch.empty_like(pre)
+        y = torch.empty_like(t) if want_y else None
+        self.check(self.lib.sr_mse_clip_grad_bf16(self.h, pre.data_ptr(), t.data_ptr(), pre.numel(), loss.data_ptr(), dpre.data_ptr(),
+                                                  None if y is None else y.data_ptr(), self.stream()))
+        return y, loss, dpre
+
     def space_to_depth(self, x, r):
         """Inverse of tf.nn.depth_to_space (DCR): [B,H*r,W*r,C] -> [B,H,W,r*r*C]."""
         _check_tensor(self, x, "space_to_depth input")

@@ -84,6 +84,8 @@ class ParamBucket:
     def gather(self, grads):
         """{layer: [dk, db]} device tensors -> one flat device tensor in parameter order (zeros where the loss does not reach a variable:
         its moments and value then stay put, as Keras' skipping of None gradients leaves them)."""
+        if isinstance(grads, FlatGrads):                             # written in place into views of one flat tensor: nothing to gather
+            return grads.flat
         parts = []
         for n, views in self.dev.items():
             g = grads.get(n)
@@ -98,6 +100,15 @@ class ParamBucket:
     def dgrad(self, dy, name):
         k = self.dev[name][0]
         return self.ctx.conv2d_dev(dy, k, None, k.shape[2], rot=True)
+
+
+class FlatGrads(dict):
+    """{layer: (dw, db)} whose tensors are the views of ONE flat fp32 device tensor `flat` in a ParamBucket's parameter order: the kernels wrote the
+    gradients straight into the bucket the optimiser reads (ParamBucket.gather hands `flat` on)."""
+
+    def __init__(self, bucket):
+        self.flat = torch.zeros_like(bucket.flat)                   # (zeros where no kernel writes: a variable the loss does not reach)
+        super().__init__(bucket.split(self.flat))
 
 
 def as_bucket(ctx, w):
@@ -237,6 +248,97 @@ def edsr_loss_and_grads(ctx, w, x, t, scale=2, num_res_blocks=16, res_scaling=0.
         d = ctx.eltwise(L.ELT_AXPBY, d, dw.dgrad(dt, na), 1.0, 1.0)
     d = ctx.eltwise(L.ELT_AXPBY, d, d_h0, 1.0, 1.0)
     g[n_head] = ctx.conv2d_wgrad(x, d, 3)
+    return y, loss, g
+
+
+def edsr_loss_and_grads_bf16(ctx, bucket, x, t, scale=2, num_res_blocks=16, res_scaling=0.1, tape=None):
+    """edsr_loss_and_grads in bf16 mixed precision ("Mixed-precision training").  bucket: the fit's ParamBucket -- fp32 master weights; every conv
+    kernel is rounded to bf16 once per step, for its forward and its rotated input-gradient use, by ONE pack launch.  x: the input batch, rounded to bf16
+    here when it is fp32; t: the fp32 target, never rounded.  Every activation and activation gradient between kernels is a bf16 tensor written with one
+    rounding after an fp32 epilogue; weight and bias gradients are fp32, written into views of one flat tensor in the bucket's order (a FlatGrads).
+    tape: a list that receives (name, tensor) for every stored tensor, by reference, in the order they are made:
+      x, h0, tt_i / nxt_i per block i = 1.., body, up_j per up-sampling conv j = 1.., pre, dpre, d_out, then per up-sampling conv in reverse dv_j / d_up_j,
+      d_body, then per block in reverse du_i (res_scaling * dgrad, before the mask) / dt_i / d_i (d_1 is the head conv's output gradient, both skips added).
+    -> (y fp32 = clip(pre), loss fp32 [1], FlatGrads)."""
+    if not isinstance(bucket, ParamBucket):
+        raise ValueError("edsr_loss_and_grads_bf16: the weights must be a ParamBucket (train_dtype='bf16' needs update='device')")
+    if num_res_blocks < 1:
+        raise ValueError("edsr_loss_and_grads_bf16: at least one residual block")
+    rec = tape.append if tape is not None else (lambda item: None)
+    names = ["conv2d"] + [f"conv2d_{i}" for i in range(1, 2 * num_res_blocks + 5)]
+    it = iter(names)
+    n_head = next(it)
+    dev = bucket.dev
+    packs = getattr(bucket, "_packs_bf16", None)
+    if packs is None:                                                # every layer's forward use, and the input-gradient use of all but the head
+        uses = [(dev[n][0], dev[n][1], False) for n in dev] + [(dev[n][0], None, True) for n in dev if n != n_head]
+        packs = bucket._packs_bf16 = ctx.pack_list(uses)
+    ctx.conv_prepack_bf16(packs)
+
+    def conv(a, name, **kw):
+        k, b = dev[name]
+        return ctx.conv2d_dev_bf16(a, k, b, k.shape[3], **kw)
+
+    def dgrad(dy, name, **kw):
+        k = dev[name][0]
+        return ctx.conv2d_dev_bf16(dy, k, None, k.shape[2], rot=True, **kw)
+
+    g = FlatGrads(bucket)
+
+    def wgrad(name, a, dy, s=1.0):
+        ctx.conv2d_wgrad_bf16(a, dy, 3, scale=s, out=g[name])
+
+    x = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    rec(("x", x))
+    h0 = conv(x, n_head)
+    rec(("h0", h0))
+    cur, blocks = h0, []
+    for i in range(1, num_res_blocks + 1):
+        na, nb = next(it), next(it)
+        tt = conv(cur, na, act="relu")
+        nxt = conv(tt, nb, alpha=res_scaling, skip1=cur, beta1=1.0)
+        rec((f"tt_{i}", tt))
+        rec((f"nxt_{i}", nxt))
+        blocks.append((i, na, nb, cur, tt))
+        cur = nxt
+    n_body = next(it)
+    body = conv(cur, n_body, skip1=h0, beta1=1.0)
+    rec(("body", body))
+    ups, up = [], body
+    for j, r in enumerate([scale] if scale in (2, 3) else [2, 2], 1):
+        nu = next(it)
+        v = conv(up, nu, d2s=r)
+        rec((f"up_{j}", v))
+        ups.append((j, nu, up, r))
+        up = v
+    n_out = next(it)
+    pre = conv(up, n_out)
+    rec(("pre", pre))
+    y, loss, dpre = ctx.mse_clip_grad_bf16(pre, t)
+    rec(("dpre", dpre))
+    wgrad(n_out, up, dpre)
+    d = dgrad(dpre, n_out)
+    rec(("d_out", d))
+    for j, nu, uin, r in reversed(ups):
+        dv = ctx.space_to_depth_bf16(d, r)
+        rec((f"dv_{j}", dv))
+        wgrad(nu, uin, dv)
+        d = dgrad(dv, nu)
+        rec((f"d_up_{j}", d))
+    d_h0 = d                                                  # global skip: body = conv(cur) + h0
+    wgrad(n_body, cur, d)
+    d = dgrad(d, n_body)
+    rec(("d_body", d))
+    for i, na, nb, cin, tt in reversed(blocks):
+        wgrad(nb, tt, d, res_scaling)                         # no stored res_scaling * d: the factor is applied to the finished fp32 sums
+        du = dgrad(d, nb, alpha=res_scaling)
+        rec((f"du_{i}", du))
+        dt = ctx.relu_bwd_bf16(du, tt)
+        rec((f"dt_{i}", dt))
+        wgrad(na, cin, dt)
+        d = dgrad(dt, na, skip1=d, beta1=1.0, skip2=d_h0 if i == 1 else None, beta2=1.0 if i == 1 else 0.0)
+        rec((f"d_{i}", d))
+    wgrad(n_head, x, d)
     return y, loss, g
 
 
