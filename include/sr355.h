@@ -188,7 +188,11 @@ int  sr_bicubic(sr_ctx* ctx, const void* x, int dtype, int B, int H, int W, int 
  * per-file codes of interpolation_map.pkl in load_dataset_as_patches(mode="srcnn") (loading_methods.py:131-148, which hands an
  * integer entry of the map to cv2.resize as it is).  f32: float path; u8: OpenCV's 11-bit fixed-point path; uint8 INTER_AREA
  * shrinking: integer cell sums for whole-number factors ((sum + 2) >> 2 for 2 x 2, a rounded float product otherwise), the
- * float taps rounded half to even for the others.  Any other code: SR_ERR_INVALID. */
+ * float taps rounded half to even for the others.  Any other code: SR_ERR_INVALID.
+ * The float path (f32 LINEAR / AREA / LANCZOS4, and the uint8 fractional INTER_AREA shrink before its rint) is OpenCV's two passes in
+ * float: per source row the horizontal taps in ascending source order, then the vertical taps, every product and every sum rounded
+ * on its own (no fused multiply-add) -- bit for bit NumPy's `acc += x * w` in that order.  The tap coordinates are fp64, likewise
+ * uncontracted: d * scale, (d + 0.5) * scale - 0.5 and (d + 1) - (s + 1) * inv_scale round the product first. */
 int  sr_resize(sr_ctx* ctx, const void* x, int dtype, int B, int H, int W, int C,
                int outH, int outW, int interpolation, void* y, void* stream);
 /* tf.image.psnr / tf.image.ssim(max_val) (metrics.py:3-7): a,b f32 [B,H,W,C] -> out f32 [B] (device). */
@@ -310,7 +314,8 @@ int  sr_spectral_l1_bwd(sr_ctx* ctx, const void* a, const void* b, int B, int H,
 /* add_padding + sliding-window extraction (SRCNN_model.py:127-162, EDSR_model.py:201-223,
  * ESRGAN_model.py:883-901, VGG16_model.py:216-239): img f32 [H,W,C] (unpadded), reflect padding
  * bottom/right computed from (patch,stride); out [P,patch,patch,C] of out_dtype, each value
- * v*mul+add (ESRGAN: *2-1).  *n_patches receives P.  out may be NULL to query P only. */
+ * v*mul+add (ESRGAN: *2-1), product and sum rounded separately as NumPy's two ufuncs round them.  *n_patches receives P.  out may be
+ * NULL to query P only. */
 int  sr_extract_patches(sr_ctx* ctx, const float* img, int H, int W, int C, int patch, int stride,
                         float mul, float add, int out_dtype, void* out, int64_t out_capacity,
                         int* n_patches, void* stream);
@@ -347,14 +352,20 @@ int  sr_classification_counts(sr_ctx* ctx, const int32_t* y_true_N, const int32_
  * sr_back_projection: back_projection (classic_algorithms.py:23-43).  hr_u8 [B,H,W] is the starting estimate (the reference starts
  *   from its first argument), lr_u8 [B,h,w] the observation, H >= h, W >= w.  Each of `iterations` rounds: diff = float32(lr) -
  *   resize(est, (w, h), INTER_LINEAR); est += resize(diff, (W, H), INTER_LINEAR), sr_resize's float32 rules (an exact 2x shrink is the
- *   2 x 2 area mean).  y_u8 [B,H,W] = clip(est, 0, 255) truncated; y_f32 [B,H,W] (may be NULL) receives est before the clip.
+ *   2 x 2 area mean).  y_u8 [B,H,W] = clip(est, 0, 255) truncated; y_f32 [B,H,W] (may be NULL) receives est before the clip.  Every
+ *   product and every sum is rounded on its own, in sr_resize's order (horizontal taps, then vertical, then the difference or the
+ *   update): y_f32 is bit for bit the float32 NumPy evaluation.
  * sr_noise_sigma: estimate_sigma(x) as non_local_means calls it (classic_algorithms.py:45): median of |dd band of pywt.dwtn(x, 'db2')|
  *   ('symmetric' mode, 0..255 units) over its non-zero entries / norm.ppf(0.75) -> sigma_f64 [B] (device; NaN when every entry is 0).
+ *   Per axis (axis 0 first) d[o] = sum_{j<3} dec_hi[j] * (x[2o+1-j] - x[2o-2]) in fp64, j ascending, every product and sum rounded on its
+ *   own; the median is exact (the mean of the middle two for an even count): bit for bit the NumPy evaluation.
  * sr_nl_means: denoise_nl_means(x / 255, h = h_scale * sigma_f64[b], patch_size = patch (odd, <= 9), patch_distance = distance (<= 12),
  *   fast_mode=True) (classic_algorithms.py:47-53): y_f32 [B,h,w]; sigma_f64 is read on the device.
  * sr_edge_guided: edge_guided_interpolation (classic_algorithms.py:64-85): clip(addWeighted(resize_u8(x, (W, H), INTER_LINEAR), 1,
  *   resize(hypot(Sobel_x, Sobel_y), (W, H)), weight, 0), 0, 255) truncated -> y_u8 [B,H,W]; up_e_f32 [B,H,W] (may be NULL) receives the
- *   float32 up-sized edge magnitude.  H >= h, W >= w.
+ *   float32 up-sized edge magnitude.  H >= h, W >= w.  The edge resize is OpenCV's fp64 path (float tap weights widened, horizontal
+ *   pass first, e0 * w0 + e1 * w1 with every product and sum rounded on its own), addWeighted float32(up) * 1 + up_e * weight + 0
+ *   likewise in float32: both outputs are bit for bit the NumPy evaluation.
  * sr_freq_extrapolate: frequency_extrapolation (classic_algorithms.py:87-108): |ifft2 of the centred LR spectrum zero-padded to H x W|
  *   as the separable fp64 map |A_H X A_W^T| -> y_f64 [B,H,W].  H >= h, W >= w. */
 int  sr_back_projection(sr_ctx* ctx, const uint8_t* hr_u8, const uint8_t* lr_u8, int B, int H, int W, int h, int w, int iterations,

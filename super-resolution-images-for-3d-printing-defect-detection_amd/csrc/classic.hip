@@ -6,6 +6,7 @@
 // sr_resize computes.
 #include "cgemm_f64.h"
 #include "common.h"
+#include "fp_sep.h"
 
 #include <cmath>
 
@@ -71,10 +72,10 @@ __global__ void ibp_lr_kernel(const float* est, const uint8_t* lr, int B, int H,
         for (int j = 0; j < TY; ++j) {
             const float* row = est + (b * H + iy[oy * TY + j]) * W;
             float r = 0.f;
-            for (int k = 0; k < TX; ++k) r = __fadd_rn(r, __fmul_rn(row[ix[ox * TX + k]], wx[ox * TX + k]));
-            acc = __fadd_rn(acc, __fmul_rn(r, wy[oy * TY + j]));
+            for (int k = 0; k < TX; ++k) r = add_sep(r, mul_sep(row[ix[ox * TX + k]], wx[ox * TX + k]));
+            acc = add_sep(acc, mul_sep(r, wy[oy * TY + j]));
         }
-        diff[i] = __fsub_rn((float)lr[i], acc);
+        diff[i] = sub_sep((float)lr[i], acc);
     }
 }
 
@@ -90,10 +91,10 @@ __global__ void ibp_hr_kernel(const float* diff, int B, int H, int W, int h, int
         float acc = 0.f;
         for (int j = 0; j < 2; ++j) {
             const float* row = diff + (b * h + iy[oy * 2 + j]) * w;
-            const float r = __fadd_rn(__fadd_rn(0.f, __fmul_rn(row[ix[ox * 2]], wx[ox * 2])), __fmul_rn(row[ix[ox * 2 + 1]], wx[ox * 2 + 1]));
-            acc = __fadd_rn(acc, __fmul_rn(r, wy[oy * 2 + j]));
+            const float r = add_sep(add_sep(0.f, mul_sep(row[ix[ox * 2]], wx[ox * 2])), mul_sep(row[ix[ox * 2 + 1]], wx[ox * 2 + 1]));
+            acc = add_sep(acc, mul_sep(r, wy[oy * 2 + j]));
         }
-        const float e = __fadd_rn(est[i], acc);
+        const float e = add_sep(est[i], acc);
         est[i] = e;
         if (y) y[i] = (uint8_t)fminf(fmaxf(e, 0.f), 255.f);  // astype(uint8) truncates toward zero
     }
@@ -122,11 +123,11 @@ __global__ void db2_hh_abs_kernel(const uint8_t* x, int B, int h, int w, int oh,
         for (int q = 0; q < 4; ++q) {
             const double base = (double)img[(int64_t)r[3] * w + c[q]];
             double s = 0.0;
-            for (int j = 0; j < 3; ++j) s = __dadd_rn(s, __dmul_rn(DB2_DEC_HI[j], (double)img[(int64_t)r[j] * w + c[q]] - base));
+            for (int j = 0; j < 3; ++j) s = add_sep(s, mul_sep(DB2_DEC_HI[j], (double)img[(int64_t)r[j] * w + c[q]] - base));
             col[q] = s;
         }
         double s = 0.0;
-        for (int j = 0; j < 3; ++j) s = __dadd_rn(s, __dmul_rn(DB2_DEC_HI[j], __dsub_rn(col[j], col[3])));
+        for (int j = 0; j < 3; ++j) s = add_sep(s, mul_sep(DB2_DEC_HI[j], sub_sep(col[j], col[3])));
         d[i] = fabs(s);
     }
 }
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(1024) median_sigma_kernel(const double* d, int
     }
     const double lo = select_kth_nonzero(v, per, (nz - 1) / 2, hist, sh);
     const double hi = (nz & 1) ? lo : select_kth_nonzero(v, per, nz / 2, hist, sh);
-    if (threadIdx.x == 0) sigma[blockIdx.x] = __ddiv_rn(__dmul_rn(__dadd_rn(lo, hi), 0.5), 0.6744897501960817);   // even count: the mean of the middle two
+    if (threadIdx.x == 0) sigma[blockIdx.x] = __ddiv_rn(mul_sep(add_sep(lo, hi), 0.5), 0.6744897501960817);   // even count: the mean of the middle two
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -286,13 +287,13 @@ __global__ void egi_hr_kernel(const uint8_t* x, const double* e, int B, int h, i
         for (int j = 0; j < 2; ++j) {
             const int64_t ro = (b * h + iy[oy * 2 + j]) * w;
             rows[j] = (long long)x[ro + ix[ox * 2]] * iwx[ox * 2] + (long long)x[ro + ix[ox * 2 + 1]] * iwx[ox * 2 + 1];
-            erow[j] = __dadd_rn(__dmul_rn(e[ro + ix[ox * 2]], (double)wx[ox * 2]), __dmul_rn(e[ro + ix[ox * 2 + 1]], (double)wx[ox * 2 + 1]));
+            erow[j] = add_sep(mul_sep(e[ro + ix[ox * 2]], (double)wx[ox * 2]), mul_sep(e[ro + ix[ox * 2 + 1]], (double)wx[ox * 2 + 1]));
         }
         const long long v = (((iwy[oy * 2] * (rows[0] >> 4)) >> 16) + ((iwy[oy * 2 + 1] * (rows[1] >> 4)) >> 16) + 2) >> 2;   // VResizeLinear<uchar>
         const float up = (float)min(max(v, 0ll), 255ll);
-        const float ue = (float)__dadd_rn(__dmul_rn(erow[0], (double)wy[oy * 2]), __dmul_rn(erow[1], (double)wy[oy * 2 + 1]));
+        const float ue = (float)add_sep(mul_sep(erow[0], (double)wy[oy * 2]), mul_sep(erow[1], (double)wy[oy * 2 + 1]));
         if (up_e) up_e[i] = ue;
-        const float s = __fadd_rn(__fadd_rn(__fmul_rn(up, 1.0f), __fmul_rn(ue, weight)), 0.0f);
+        const float s = add_sep(add_sep(mul_sep(up, 1.0f), mul_sep(ue, weight)), 0.0f);
         y[i] = (uint8_t)fminf(fmaxf(s, 0.f), 255.f);
     }
 }

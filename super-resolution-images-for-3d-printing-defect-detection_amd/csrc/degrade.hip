@@ -18,6 +18,7 @@
 // A bad row (a kernel size, tap set, deviation or quality outside the contract) is never acted on: the image is copied through and the
 // first such row is recorded in the context's status words, which sr_degrade_status reads back (the stage entries themselves only launch).
 #include "common.h"
+#include "fp_sep.h"
 
 #include <algorithm>
 #include <string>
@@ -178,12 +179,12 @@ __global__ void __launch_bounds__(256) degrade_noise_kernel(const uint8_t* x, in
         }
         for (int k = 0; k < cnt; ++k) {
             if (z_out) z_out[(int64_t)b * n + e0 + k] = z[k];
-            nz[k] = __fmul_rn(sd, z[k]);
+            nz[k] = mul_sep(sd, z[k]);
         }
     }
     for (int k = 0; k < cnt; ++k) {
         if (!on) { out[k] = in[k]; continue; }
-        const float v = fminf(fmaxf(__fadd_rn((float)in[k], nz[k]), 0.f), 255.f);
+        const float v = fminf(fmaxf(add_sep((float)in[k], nz[k]), 0.f), 255.f);
         out[k] = (uint8_t)(int)v;
     }
 }

@@ -18,6 +18,7 @@
 //     2. grads: one thread per parameter of the head's slice of the flat gradient bucket (kernel, bias, kernel, bias -- train.ParamBucket's
 //        order), the batch rows summed in row order, stored or added onto what is there; thread 0 also writes the mean loss.
 #include "common.h"
+#include "fp_sep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -212,7 +213,7 @@ __global__ void __launch_bounds__(256) disc_head_grads_kernel(int B, DiscHeadWor
     } else {
         return;
     }
-    grads[e] = accumulate ? __fadd_rn(grads[e], (float)s) : (float)s;
+    grads[e] = accumulate ? add_sep(grads[e], (float)s) : (float)s;
 }
 
 }  // namespace

@@ -30,6 +30,7 @@
 // No float atomics anywhere: a pair's row is the same bits on every run and for any B.
 #include "cgemm_f64.h"
 #include "common.h"
+#include "fp_sep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -321,7 +322,7 @@ __global__ void __launch_bounds__(256) eda_ring_kernel(const int* lab, const uin
 //    levels 0: the gray values themselves (256 levels).  grid (bands, B); LDSM: the matrices of the band in LDS (nang L L <= 16384).
 // ------------------------------------------------------------------------------------------------
 __device__ inline int quantise(int gv, int levels) {
-    return levels ? (int)__fmul_rn(__fdiv_rn((float)gv, 255.f), (float)(levels - 1)) : gv;
+    return levels ? (int)mul_sep(__fdiv_rn((float)gv, 255.f), (float)(levels - 1)) : gv;
 }
 
 template <bool LDSM>

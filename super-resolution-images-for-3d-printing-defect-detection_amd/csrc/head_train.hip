@@ -20,6 +20,7 @@
 //   sr_pool_gap_bwd: GlobalAveragePooling2D, MaxPooling2D(2,2) and the last conv's ReLU backward in one launch: dfeats [B,C] -> dz [B,H,W,C] at
 //     that conv's pre-activation, bit for bit the GAP spread (dfeats / ((H/2)(W/2))), sr_maxpool2_bwd and SR_ELT_RELU_BWD one after the other.
 #include "common.h"
+#include "fp_sep.h"
 #include "warp_sample.h"
 
 #include <algorithm>
@@ -116,7 +117,7 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
         if (r < nr) {
             const int64_t o = (int64_t)(r0 + r) * HIN + i;
             v = g[o];
-            if (m0) v = m0[o] ? __fmul_rn(v, kscale) : 0.f;
+            if (m0) v = m0[o] ? mul_sep(v, kscale) : 0.f;
             if (train) wk.x0[o] = v;
         }
         sx0[r][i] = v;
@@ -139,11 +140,11 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
     float z1[HROWS], f1[HROWS];               // f1: the factor of dz1 = dx1 * m1 / keep * [z1 > 0]
 #pragma unroll
     for (int r = 0; r < HROWS; ++r) {
-        z1[r] = __fadd_rn(acc[r], b1[j]);
+        z1[r] = add_sep(acc[r], b1[j]);
         float a = fmaxf(z1[r], 0.f);
         float m = 1.f;
         if (m1 && r < nr) m = m1[(int64_t)(r0 + r) * HHID + j] ? kscale : 0.f;
-        a = __fmul_rn(a, m);
+        a = mul_sep(a, m);
         f1[r] = z1[r] > 0.f ? m : 0.f;
         sx1[r][j] = a;
         if (train && r < nr) wk.x1[(int64_t)(r0 + r) * HHID + j] = a;
@@ -164,7 +165,7 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
         const int r = e / C, c = e - r * C;
         float s = 0.f;
         for (int q = 0; q < HHID; ++q) s = __fmaf_rn(sx1[r][q], k2[(int64_t)q * C + c], s);
-        wk.dz2[(int64_t)(r0 + r) * C + c] = __fadd_rn(s, b2[c]);
+        wk.dz2[(int64_t)(r0 + r) * C + c] = add_sep(s, b2[c]);
     }
     __syncthreads();
 
@@ -175,7 +176,7 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
         float mx = z[0];
         for (int c = 1; c < C; ++c) mx = fmaxf(mx, z[c]);
         float sum = 0.f;
-        for (int c = 0; c < C; ++c) { const float ex = expf(__fsub_rn(z[c], mx)); z[c] = ex; sum = __fadd_rn(sum, ex); }
+        for (int c = 0; c < C; ++c) { const float ex = expf(sub_sep(z[c], mx)); z[c] = ex; sum = add_sep(sum, ex); }
         int am = 0;
         float pm = -1.f;
         for (int c = 0; c < C; ++c) { const float p = __fdiv_rn(z[c], sum); z[c] = p; if (p > pm) { pm = p; am = c; } }
@@ -185,7 +186,7 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
         if (y >= 0 && y < C) {
             l = -log(fmin(fmax((double)z[y], 1e-7), 1.0 - 1e-7));
             hit = am == y;
-            if (train) z[y] = __fsub_rn(z[y], 1.f);
+            if (train) z[y] = sub_sep(z[y], 1.f);
         }
         if (train) for (int c = 0; c < C; ++c) z[c] = __fdiv_rn(z[c], (float)n);
         wk.loss[r] = l;
@@ -199,7 +200,7 @@ __global__ void __launch_bounds__(256) head_rows_kernel(const float* __restrict_
         const float* d = wk.dz2 + (int64_t)(r0 + r) * C;
         float s = 0.f;
         for (int c = 0; c < C; ++c) s = __fmaf_rn(d[c], k2[(int64_t)j * C + c], s);
-        wk.dz1[(int64_t)(r0 + r) * HHID + j] = __fmul_rn(s, f1[r]);
+        wk.dz1[(int64_t)(r0 + r) * HHID + j] = mul_sep(s, f1[r]);
     }
 }
 
@@ -219,17 +220,17 @@ __global__ void __launch_bounds__(256) head_grads_kernel(int n, int C, const flo
     if (e < nk1) {
         const int i = (int)(e / HHID), j = (int)(e - (int64_t)i * HHID);
         for (int r = 0; r < n; ++r) s = __fmaf_rn(wk.x0[(int64_t)r * HIN + i], wk.dz1[(int64_t)r * HHID + j], s);
-        if (l2x2 != 0.f) s = __fadd_rn(s, __fmul_rn(l2x2, prm[e]));
+        if (l2x2 != 0.f) s = add_sep(s, mul_sep(l2x2, prm[e]));
     } else if (e < nk1 + nb1) {
         const int j = (int)(e - nk1);
-        for (int r = 0; r < n; ++r) s = __fadd_rn(s, wk.dz1[(int64_t)r * HHID + j]);
+        for (int r = 0; r < n; ++r) s = add_sep(s, wk.dz1[(int64_t)r * HHID + j]);
     } else if (e < nk1 + nb1 + nk2) {
         const int64_t q = e - nk1 - nb1;
         const int j = (int)(q / C), c = (int)(q - (int64_t)j * C);
         for (int r = 0; r < n; ++r) s = __fmaf_rn(wk.x1[(int64_t)r * HHID + j], wk.dz2[(int64_t)r * C + c], s);
     } else if (e < nk1 + nb1 + nk2 + C) {
         const int c = (int)(e - nk1 - nb1 - nk2);
-        for (int r = 0; r < n; ++r) s = __fadd_rn(s, wk.dz2[(int64_t)r * C + c]);
+        for (int r = 0; r < n; ++r) s = add_sep(s, wk.dz2[(int64_t)r * C + c]);
     } else {
         return;
     }
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(256) head_dfeats_kernel(int n, const uint8_t* 
     for (int r = 0; r < nr; ++r) {
         const int64_t o = (int64_t)(r0 + r) * HIN + i;
         float v = acc[r];
-        if (m0) v = m0[o] ? __fmul_rn(v, kscale) : 0.f;
+        if (m0) v = m0[o] ? mul_sep(v, kscale) : 0.f;
         dfeats[o] = v;
     }
 }

@@ -3,6 +3,7 @@
 // extraction with reflect padding, overlap-add reconstruction, max-pool, global average pool,
 // dense head + softmax.  Each is priced against HBM bytes in DESIGN.md; none is GEMM-shaped.
 #include "common.h"
+#include "fp_sep.h"
 #include <algorithm>
 
 namespace {
@@ -440,7 +441,7 @@ __global__ void extract_patches_kernel(const float* img, int H, int W, int C, in
         const int jx = (int)(t % nx);
         const int jy = (int)(t / nx);
         const int y = reflect(jy * stride + py, H), x = reflect(jx * stride + px, W);
-        st_dt(out, i, img[((int64_t)y * W + x) * C + c] * mul + add, out_dt);
+        st_dt(out, i, add_sep(mul_sep(img[((int64_t)y * W + x) * C + c], mul), add), out_dt);   // NumPy's img * mul + add: two roundings
     }
 }
 
@@ -838,6 +839,10 @@ int clock_probe_launch(sr_ctx* ctx, float* mhz_out, hipStream_t st) {
 constexpr int RS_MAXT = 16;
 
 __global__ void resize_taps_kernel(int n_src, int n_dst, int interp, int area_up, int T, int* idx, float* w, int* iw) {
+    // No operator of this kernel may be contracted into an fma: a fused d * scale + scale or (d + 0.5) * scale - 0.5 changes which side of
+    // an integer a coordinate falls on, and with it the taps (OpenCV's x86 builds round the product first).  The pragma governs the plain
+    // operators written in this body; the products that feed a sum go through fp_sep.h's helpers, which hold whatever surrounds them.
+#pragma clang fp contract(off)
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= n_dst) return;
     const double inv_scale = (double)n_dst / (double)n_src, scale = 1.0 / inv_scale;
@@ -845,9 +850,7 @@ __global__ void resize_taps_kernel(int n_src, int n_dst, int interp, int area_up
     float* wd = w + (size_t)d * T;
     for (int k = 0; k < T; ++k) { id[k] = 0; wd[k] = 0.f; }
     if (interp == 3 && !area_up) {                                 // INTER_AREA, shrinking
-        // (explicit *_rn operations throughout: a contracted fma changes which side of an integer a coordinate falls on -- OpenCV's
-        //  x86 builds round the product first)
-        const double f1 = __dmul_rn((double)d, scale), f2 = __dadd_rn(f1, scale);
+        const double f1 = mul_sep((double)d, scale), f2 = add_sep(f1, scale);
         const double cell = fmin(scale, (double)n_src - f1);
         int s1 = (int)ceil(f1), s2 = (int)floor(f2);
         s2 = min(s2, n_src - 1);
@@ -859,11 +862,11 @@ __global__ void resize_taps_kernel(int n_src, int n_dst, int interp, int area_up
     } else if (interp == 1 || interp == 3) {                       // linear taps; INTER_AREA enlarging uses "area" coordinates
         int s; float f;
         if (interp == 3) {
-            s = (int)floor(__dmul_rn((double)d, scale));
-            f = (float)__dsub_rn((double)(d + 1), __dmul_rn((double)(s + 1), inv_scale));
+            s = (int)floor(mul_sep((double)d, scale));
+            f = (float)sub_sep((double)(d + 1), mul_sep((double)(s + 1), inv_scale));
             f = f <= 0.f ? 0.f : f - floorf(f);
         } else {
-            const float fx = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);
+            const float fx = (float)sub_sep(mul_sep((double)d + 0.5, scale), 0.5);
             s = (int)floorf(fx);
             f = fx - (float)s;
         }
@@ -872,7 +875,7 @@ __global__ void resize_taps_kernel(int n_src, int n_dst, int interp, int area_up
         id[0] = min(max(s, 0), n_src - 1); id[1] = min(max(s + 1, 0), n_src - 1);
         wd[0] = 1.f - f; wd[1] = f;
     } else {                                                       // INTER_LANCZOS4: 8 taps at s-3 .. s+4
-        const float fx = (float)__dsub_rn(__dmul_rn((double)d + 0.5, scale), 0.5);
+        const float fx = (float)sub_sep(mul_sep((double)d + 0.5, scale), 0.5);
         int s = (int)floorf(fx);
         float x = fx - (float)s;
         if (x >= 1.f) { s += 1; x = 0.f; }                           // fx a hair below an integer: (s, 1.0) is (s + 1, 0.0) -- and 1.0 would divide by zero below
@@ -912,8 +915,8 @@ __global__ void resize_apply_f32_kernel(const float* x, int B, int H, int W, int
             const float wyj = wy[oy * TY + j];
             const float* row = x + ((int64_t)b * H + iy[oy * TY + j]) * W * C + c;
             float r = 0.f;
-            for (int k = 0; k < TX; ++k) r = __fadd_rn(r, __fmul_rn(row[(int64_t)ix[ox * TX + k] * C], wx[ox * TX + k]));
-            acc = __fadd_rn(acc, __fmul_rn(r, wyj));
+            for (int k = 0; k < TX; ++k) r = add_sep(r, mul_sep(row[(int64_t)ix[ox * TX + k] * C], wx[ox * TX + k]));
+            acc = add_sep(acc, mul_sep(r, wyj));
         }
         y[i] = acc;
     }
@@ -956,7 +959,7 @@ __global__ void resize_nearest_kernel(const E* x, int B, int H, int W, int C, in
         const int ox = (int)(t % oW); t /= oW;
         const int oy = (int)(t % oH);
         const int b = (int)(t / oH);
-        const int sx = min((int)floor(__dmul_rn((double)ox, ifx)), W - 1), sy = min((int)floor(__dmul_rn((double)oy, ify)), H - 1);
+        const int sx = min((int)floor(mul_sep((double)ox, ifx)), W - 1), sy = min((int)floor(mul_sep((double)oy, ify)), H - 1);
         y[i] = x[(((int64_t)b * H + sy) * W + sx) * C + c];
     }
 }
@@ -979,7 +982,7 @@ __global__ void resize_area_fast_u8_kernel(const uint8_t* x, int B, int H, int W
             const uint8_t* row = x + (((int64_t)b * H + oy * fy + j) * W + (int64_t)ox * fx) * C + c;
             for (int k = 0; k < fx; ++k) sum += row[(int64_t)k * C];
         }
-        y[i] = shift2 ? (uint8_t)((sum + 2) >> 2) : (uint8_t)fminf(fmaxf(rintf(__fmul_rn((float)sum, scale)), 0.f), 255.f);
+        y[i] = shift2 ? (uint8_t)((sum + 2) >> 2) : (uint8_t)fminf(fmaxf(rintf(mul_sep((float)sum, scale)), 0.f), 255.f);
     }
 }
 
@@ -999,8 +1002,8 @@ __global__ void resize_apply_area_u8_kernel(const uint8_t* x, int B, int H, int 
             const float wyj = wy[oy * TY + j];
             const uint8_t* row = x + ((int64_t)b * H + iy[oy * TY + j]) * W * C + c;
             float r = 0.f;
-            for (int k = 0; k < TX; ++k) r = __fadd_rn(r, __fmul_rn((float)row[(int64_t)ix[ox * TX + k] * C], wx[ox * TX + k]));
-            acc = __fadd_rn(acc, __fmul_rn(r, wyj));
+            for (int k = 0; k < TX; ++k) r = add_sep(r, mul_sep((float)row[(int64_t)ix[ox * TX + k] * C], wx[ox * TX + k]));
+            acc = add_sep(acc, mul_sep(r, wyj));
         }
         y[i] = (uint8_t)fminf(fmaxf(rintf(acc), 0.f), 255.f);
     }

@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp_sep.h"
 
 namespace {
 
@@ -95,7 +96,7 @@ __global__ void __launch_bounds__(256) lpips_input_kernel(const void* __restrict
         if (y >= 0 && y < H && x >= 0 && x < W) {
             const int64_t o = img + ((int64_t)y * W + x) * 3;
             if (U8) s = tab[c * 256 + static_cast<const uint8_t*>(src)[o + (2 - c)]];        // BGR -> R, G, B
-            else s = __fdiv_rn(__fsub_rn(static_cast<const float*>(src)[o + c], lp_shift(c)), lp_scale(c));
+            else s = __fdiv_rn(sub_sep(static_cast<const float*>(src)[o + c], lp_shift(c)), lp_scale(c));
         }
         v[e] = s;
     }

@@ -21,6 +21,7 @@
 //      sr_ssim_map, the pair-statistics pass's SSIM part over the whole image with scipy's 'reflect' border.
 #include "cgemm_f64.h"
 #include "common.h"
+#include "fp_sep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -66,7 +67,7 @@ __device__ inline float gray_val(const void* img, int dt, int C, int64_t pix) {
 
 // what np.histogram(range=(0, 255)) bins: uint8 as float32, float as clip(x, 0, 1) * 255 in float32
 __device__ inline double hist_val(float x, int dt) {
-    return dt == SR_DTYPE_U8 ? (double)x : (double)__fmul_rn(fminf(fmaxf(x, 0.f), 1.f), 255.f);
+    return dt == SR_DTYPE_U8 ? (double)x : (double)mul_sep(fminf(fmaxf(x, 0.f), 1.f), 255.f);
 }
 
 // np.histogram's bin of v in [0, 255] with `bins` equal bins: ((v - 0) / 255) * bins truncated, the right edge folded into the last bin,
@@ -387,7 +388,7 @@ __global__ void __launch_bounds__(256) freq_to_u8_kernel(const double* f, int64_
     uint8_t* out = y + (int64_t)b * per;
     for (int64_t i = (int64_t)blockIdx.x * FQ_PER_WG + threadIdx.x, e = min((int64_t)(blockIdx.x + 1) * FQ_PER_WG, per); i < e; i += 256) {
         const double v = img[i];
-        out[i] = (uint8_t)(long long)(scale ? __dmul_rn(__ddiv_rn(v, mx), 255.0) : v);
+        out[i] = (uint8_t)(long long)(scale ? mul_sep(__ddiv_rn(v, mx), 255.0) : v);
     }
 }
 

@@ -14,6 +14,7 @@
 // sr_gather_warp_patches does the same for the classifier's fit (load_defects_dataset_as_patches: one stack, no padding) and applies the
 // augmentation warp of sr_affine_warp on the way, with that kernel's own arithmetic (warp_sample.h): no fp32 patch ever lies in memory.
 #include "common.h"
+#include "fp_sep.h"
 #include "warp_sample.h"
 
 #include <algorithm>
@@ -57,10 +58,9 @@ __device__ __forceinline__ void gather_pixel(const Side& s, const int32_t* __res
         for (int c = 0; c < 3; ++c) v[c] = p[c];
     }
     if (s.swap) { const float t = v[0]; v[0] = v[2]; v[2] = t; }
-    if (s.affine) {
-#pragma clang fp contract(off)                                       // two roundings, as NumPy's two ufuncs: no fma
+    if (s.affine) {                                                  // two roundings, as NumPy's two ufuncs: no fma (fp_sep.h)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = __fadd_rn(__fmul_rn(v[c], s.mul), s.add);
+        for (int c = 0; c < 3; ++c) v[c] = add_sep(mul_sep(v[c], s.mul), s.add);
     }
     float* o = s.out + pix * 3;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2];

@@ -7,7 +7,8 @@
 //                           owns four consecutive destination values: one 16-byte (fp32) or 8-byte (bf16) store, and one 16-byte (fp32) or
 //                           4-byte (uint8) load where the four sources are contiguous and aligned, four scalar loads in the reflected tail
 //                           or at an odd source offset.  Otherwise one value per thread.  The value is sr_extract_patches' expression
-//                           (v * mul + add, same contraction), so a frame's slice is that call's output bit for bit.  Indices are 64-bit.
+//                           (v * mul + add, product and sum rounded separately), so a frame's slice is that call's output bit for bit.
+//                           Indices are 64-bit.
 //   patch_vote              one workgroup per frame.  Thread t owns column t % Kp (Kp = K rounded up to a power of two <= 64) of the rows
 //                           t / Kp, t / Kp + 256 / Kp, ...: loads are coalesced, a row's argmax is a butterfly over its Kp lanes (larger value,
 //                           then lower index: np.argmax's first maximum), votes are integer atomics in LDS, and every column sum is one fp64
@@ -15,6 +16,7 @@
 //                           same bits on every run.  Thread 0 then applies the reference's tie rule.
 //   classification_counts   one workgroup per method: integer atomics into the (zeroed) K x K matrix, fp64 per-thread sums and an LDS tree.
 #include "common.h"
+#include "fp_sep.h"
 
 #include <string>
 
@@ -26,7 +28,7 @@ __device__ __forceinline__ int reflect_br(int y, int n) { return y < n ? y : 2 *
 
 struct PatchGeom { int F, H, W, C, patch, stride, ny, nx; };
 
-__device__ __forceinline__ float affine(float v, float mul, float add) { return v * mul + add; }
+__device__ __forceinline__ float affine(float v, float mul, float add) { return add_sep(mul_sep(v, mul), add); }   // two roundings (fp_sep.h)
 
 // one value per thread: any patch*C, any alignment
 template <typename TIn>

@@ -9,6 +9,7 @@
 //     range is split over workgroups; partial 32x32 tiles are summed in a second pass in a fixed order (reproducible, no atomics).
 //   * element-wise backward ops and the space_to_depth that undoes depth_to_space (TF "DCR" order).
 #include "common.h"
+#include "fp_sep.h"
 
 #include <cmath>
 
@@ -569,17 +570,18 @@ int wgrad_maps_launch(sr_ctx* ctx, const float* x, const float* dy, int B, int H
 
 // keras.optimizers.Adam (TF 2.10 optimizer_v2, dense update) over a flat fp32 bucket, in place:
 //   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  w = w - lr_t m / (sqrt(v) + eps),  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) from the host.
-// Every operation is rounded on its own (no fma contraction), in the order sr355.train.Adam's NumPy expression evaluates them, so the device
-// update is bit for bit the host one (tests/test_train_gpu.py compares the two on one bucket).
+// Every operation is rounded on its own, in the order sr355.train.Adam's NumPy expression evaluates them, so the device update is bit for bit the
+// host one (tests/test_train_gpu.py compares the two on one bucket).  fp_sep.h's helpers keep the products out of the sums; the __fmul_rn /
+// __fadd_rn spelling this kernel had did not -- that it was not fused was the code generator's choice (it had paired the products).
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    float lr_t, float b1, float omb1, float b2, float omb2, float eps, float gscale) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = gscale == 1.f ? g[i] : __fmul_rn(g[i], gscale);
-        const float mi = __fadd_rn(__fmul_rn(b1, m[i]), __fmul_rn(omb1, gi));
-        const float vi = __fadd_rn(__fmul_rn(b2, v[i]), __fmul_rn(__fmul_rn(omb2, gi), gi));
+        const float gi = gscale == 1.f ? g[i] : mul_sep(g[i], gscale);
+        const float mi = add_sep(mul_sep(b1, m[i]), mul_sep(omb1, gi));
+        const float vi = add_sep(mul_sep(b2, v[i]), mul_sep(mul_sep(omb2, gi), gi));
         m[i] = mi;
         v[i] = vi;
-        w[i] = __fsub_rn(w[i], __fdiv_rn(__fmul_rn(lr_t, mi), __fadd_rn(sqrtf(vi), eps)));      // sqrtf: correctly rounded, as np.sqrt is (__fsqrt_rn is the 1-ulp v_sqrt_f32)
+        w[i] = sub_sep(w[i], __fdiv_rn(mul_sep(lr_t, mi), add_sep(sqrtf(vi), eps)));      // sqrtf: correctly rounded, as np.sqrt is (__fsqrt_rn is the 1-ulp v_sqrt_f32)
     }
 }
 
@@ -608,11 +610,11 @@ __global__ void __launch_bounds__(CLIP_THREADS) clip_by_norm_kernel(float* __res
     len = len < 0 ? 0 : (len > bucket_len - off ? bucket_len - off : len);
     float* p = g + off;
     double s = 0.0;
-    for (int64_t i = tid; i < len; i += CLIP_THREADS) { const double x = (double)p[i]; s = __dadd_rn(s, __dmul_rn(x, x)); }
+    for (int64_t i = tid; i < len; i += CLIP_THREADS) { const double x = (double)p[i]; s = add_sep(s, mul_sep(x, x)); }
     red[tid] = s;
     __syncthreads();
     for (int o = CLIP_THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = __dadd_rn(red[tid], red[tid + o]);
+        if (tid < o) red[tid] = add_sep(red[tid], red[tid + o]);
         __syncthreads();
     }
     const double nrm = __dsqrt_rn(red[0]);
@@ -620,7 +622,7 @@ __global__ void __launch_bounds__(CLIP_THREADS) clip_by_norm_kernel(float* __res
     const float f = clip ? (float)__ddiv_rn(clipnorm, nrm) : 1.f;
     if (tid == 0) scales[v] = f;
     if (!clip) return;                                                    // uniform per workgroup
-    for (int64_t i = tid; i < len; i += CLIP_THREADS) p[i] = __fmul_rn(p[i], f);
+    for (int64_t i = tid; i < len; i += CLIP_THREADS) p[i] = mul_sep(p[i], f);
 }
 
 int clip_by_norm_launch(sr_ctx* ctx, float* g, int64_t bucket_len, const int64_t* table, int n_vars, double clipnorm, float* scales, hipStream_t st) {

@@ -5,6 +5,7 @@
 //     channel per lane) are transposes of what memory holds: the tiles are staged PIXEL-major, as they lie in memory, and read with ds_read_b64_tr_b16.
 //   * relu_bwd / space_to_depth on bf16 (selects and permutations: bit-exact), and the fused clip + MSE loss + loss gradient.
 #include "common.h"
+#include "fp_sep.h"
 
 #include <cmath>
 
@@ -156,7 +157,7 @@ __global__ void wgrad_bf16_finish_kernel(const float* partial, int ntiles, int n
             float s = 0.f;
 #pragma unroll 16
             for (int sp = 0; sp < nsplit; ++sp) s += partial[((size_t)sp * ntiles + tile) * 1024 + e];
-            dw[((size_t)tap * Cin + ci) * Cout + co] = __fmul_rn(scale, s);
+            dw[((size_t)tap * Cin + ci) * Cout + co] = mul_sep(scale, s);
         }
     }
     if (bpart && db && tap == 0 && cib == 0 && blockIdx.y == 0 && threadIdx.x < 32 && cob * 32 + (int)threadIdx.x < Cout) {
@@ -218,14 +219,14 @@ __global__ void __launch_bounds__(256) mse_clip_grad_bf16_kernel(const uint16_t*
         const float ti = t[i];
         const float yi = inside ? bf16_bits_to_f32(pb) : ((neg || mag > 0x7f80u) ? 0.f : 1.f);
         const double d = (double)yi - (double)ti;
-        s = __dadd_rn(s, __dmul_rn(d, d));
-        dpre[i] = inside ? f32_to_bf16_rne(__fmul_rn(c, __fsub_rn(yi, ti))) : (uint16_t)0;
+        s = add_sep(s, mul_sep(d, d));
+        dpre[i] = inside ? f32_to_bf16_rne(mul_sep(c, sub_sep(yi, ti))) : (uint16_t)0;
         if (y) y[i] = yi;
     }
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] = __dadd_rn(red[threadIdx.x], red[threadIdx.x + o]);
+        if ((int)threadIdx.x < o) red[threadIdx.x] = add_sep(red[threadIdx.x], red[threadIdx.x + o]);
         __syncthreads();
     }
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
@@ -234,7 +235,7 @@ __global__ void __launch_bounds__(256) mse_clip_grad_bf16_kernel(const uint16_t*
 __global__ void mse_finish_kernel(const double* partial, int nblk, double n, float* loss) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, partial[b]);
+        for (int b = 0; b < nblk; ++b) s = add_sep(s, partial[b]);
         loss[0] = (float)(s / n);
     }
 }
