@@ -273,6 +273,23 @@ int  sr_conv2d_wgrad_bf16(sr_ctx* ctx, const void* x, int64_t x_cs, const void* 
 int  sr_relu_bwd_bf16(sr_ctx* ctx, const void* dy, const void* y, void* out, int64_t n, void* stream);
 int  sr_space_to_depth_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int C, int r, void* y, void* stream);
 int  sr_mse_clip_grad_bf16(sr_ctx* ctx, const void* pre, const float* t, int64_t n, float* loss1, void* dpre, float* y, void* stream);
+/* Mixed-precision training of ESRGAN's RRDB trunk (ESRGAN_model.py:212-300 under _train_step, :475-533): the dense blocks' virtual-concat plumbing on bf16 buffers
+ * (DESIGN.md 3.26).  sr_view here addresses bf16 elements: cs and coff multiples of 8 (16 bytes).
+ * sr_conv2d_dev_views_bf16 (ESRGAN_model.py:212-254, a dense block's forward and input-gradient convs): sr_conv2d_dev_views with x, skip1, skip2 and y channel ranges of
+ *   bf16 buffers and fp32 device kernels, out = alpha * act(conv + b) + beta1 * skip1 + beta2 * skip2 in fp32, rounded once; a skip may be the output range itself.  Cin
+ *   is a whole number of 32-channel chunks.  The kernel is rounded to bf16 as sr_conv2d_dev_bf16 rounds it (sr_conv_prepack_bf16's list answers for it).
+ * sr_conv2d_wgrad_group_bf16 (ESRGAN_model.py:212-254, the kernel and bias gradients of a dense block's layers): sr_conv2d_wgrad_bf16 of n = 1..SR_WGRAD_GROUP_MAX 3x3
+ *   layers that share [B,H,W], by one main and one finish launch: job j gives dw [3,3,Cin,Cout] = scale * sum x * dy and db [Cout] = scale * sum dy (NULL to skip) from
+ *   the views x and dy.  The job table travels in the kernel arguments: no copy, no sync.  One job alone gives sr_conv2d_wgrad_bf16's bits; a view that is not 16-byte
+ *   aligned, or a channel count that is no multiple of 8, is staged element by element.
+ * sr_eltwise_views_bf16 (ESRGAN_model.py:212-300, ReLU's gradient read off the concat buffers; an RRDB's two gradient paths joined): SR_ELT_RELU_BWD -- out = a where
+ *   b > 0, else +0, a select on bits -- and SR_ELT_AXPBY -- out = bf16(alpha * a + beta * b) in fp32, b may be NULL -- over npix pixels x C channels of bf16 views. */
+#define SR_WGRAD_GROUP_MAX 8
+typedef struct { sr_view x; sr_view dy; int32_t Cin, Cout; float scale; float* dw; float* db; } sr_wgrad_job;
+int  sr_conv2d_dev_views_bf16(sr_ctx* ctx, const sr_view* x, int B, int H, int W, int Cin, const float* d_w, const float* d_bias, int K, int Cout, int rot,
+                              int act, float alpha, const sr_view* skip1, float beta1, const sr_view* skip2, float beta2, const sr_view* y, void* stream);
+int  sr_conv2d_wgrad_group_bf16(sr_ctx* ctx, const sr_wgrad_job* jobs, int n, int B, int H, int W, void* stream);
+int  sr_eltwise_views_bf16(sr_ctx* ctx, int op, const sr_view* a, const sr_view* b, float alpha, float beta, const sr_view* out, int64_t npix, int C, void* stream);
 int  sr_eltwise(sr_ctx* ctx, int op, const void* a, const void* b, float alpha, float beta, void* out, int64_t n, void* stream);
 /* keras.optimizers.Adam's dense update (the optimiser of ESRGAN_model.py:176-195, SRCNN_model.py:55-60, EDSR_model.py:127-140) over one flat
  * fp32 bucket of n parameters, in place on the device: g is first multiplied by grad_scale (1 / world size after a summing all-reduce; 1 leaves

@@ -1332,6 +1332,47 @@ int sr_conv2d_wgrad_bf16(sr_ctx* ctx, const void* x, int64_t x_cs, const void* d
     return wgrad_bf16_launch(ctx, static_cast<const bf16_t*>(x), x_cs, static_cast<const bf16_t*>(dy), dy_cs, B, H, W, Cin, Cout, scale, dw_hwio, db, static_cast<hipStream_t>(stream));
 }
 
+// The dense blocks of the RRDB trunk in bf16: sr_conv2d_dev_views on bf16 buffers.  No kernel of its own -- the bf16 pack (or the step's prepacked image)
+// and conv_launch on the views, which picks the kernel as it does for sr_conv2d_dev_bf16.
+int sr_conv2d_dev_views_bf16(sr_ctx* ctx, const sr_view* x, int B, int H, int W, int Cin, const float* d_w, const float* d_bias, int K, int Cout, int rot, int act, float alpha,
+                             const sr_view* skip1, float beta1, const sr_view* skip2, float beta2, const sr_view* y, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!x || !x->p || !d_w || !y || !y->p) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return ctx->fail(SR_ERR_INVALID, "bad tensor shape");
+    for (const sr_view* v : {x, y, skip1, skip2})
+        if (v && v->p && (v->coff < 0 || v->cs <= 0 || v->coff >= v->cs || v->cs % 8 != 0 || v->coff % 8 != 0 || ((uintptr_t)v->p % 16) != 0))
+            return ctx->fail(SR_ERR_INVALID, "conv views bf16: a view's channel stride and first channel must be multiples of 8 (16 bytes), its buffer 16-byte aligned");
+    if (x->cs - x->coff < Cin || y->cs - y->coff < Cout || (skip1 && skip1->p && skip1->cs - skip1->coff < Cout) || (skip2 && skip2->p && skip2->cs - skip2->coff < Cout))
+        return ctx->fail(SR_ERR_INVALID, "a view is narrower than its channel count");
+    if (Cin % 32 != 0) return ctx->fail(SR_ERR_INVALID, "conv views bf16: the input channel count must be a whole number of the kernel's 32-channel chunks");
+    ConvWeights cw;
+    int rc = conv_pack_weights_dev_bf16(ctx, d_w, d_bias, K, Cin, Cout, rot, &cw, st);
+    if (rc) return rc;
+    if (cw.thin || cw.CinP != Cin) return ctx->fail(SR_ERR_INVALID, "conv views bf16: the input channel count must be a whole number of the kernel's 32-channel chunks");
+    auto tv = [](const sr_view* v) { return (v && v->p) ? TensorView{v->p, v->cs, v->coff} : TensorView{}; };
+    const ConvEpilogue ep = single_op_epilogue(act, alpha, 0, 1, tv(skip1), beta1, tv(skip2), beta2);
+    return conv_launch(ctx, cw, tv(x), B, H, W, tv(y), ep, st);
+}
+
+int sr_conv2d_wgrad_group_bf16(sr_ctx* ctx, const sr_wgrad_job* jobs, int n, int B, int H, int W, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    return wgrad_group_bf16_launch(ctx, jobs, n, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+int sr_eltwise_views_bf16(sr_ctx* ctx, int op, const sr_view* a, const sr_view* b, float alpha, float beta, const sr_view* out, int64_t npix, int C, void* stream) {
+    DeviceGuard dg_(ctx);
+    if (!ctx) return SR_ERR_INVALID;
+    if (!a || !a->p || !out || !out->p) return ctx->fail(SR_ERR_INVALID, "null tensor");
+    for (const sr_view* v : {a, b, out})
+        if (v && v->p && (v->coff < 0 || v->cs - v->coff < C)) return ctx->fail(SR_ERR_INVALID, "a view is narrower than its channel count");
+    const bf16_t* bp = (b && b->p) ? static_cast<const bf16_t*>(b->p) + b->coff : nullptr;
+    return eltwise_views_bf16_launch(ctx, op, static_cast<const bf16_t*>(a->p) + a->coff, a->cs, bp, bp ? b->cs : 0, alpha, beta,
+                                     static_cast<bf16_t*>(const_cast<void*>(out->p)) + out->coff, out->cs, npix, C, static_cast<hipStream_t>(stream));
+}
+
 int sr_relu_bwd_bf16(sr_ctx* ctx, const void* dy, const void* y, void* out, int64_t n, void* stream) {
     DeviceGuard dg_(ctx);
     if (!ctx) return SR_ERR_INVALID;

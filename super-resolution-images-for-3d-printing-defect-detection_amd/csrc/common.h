@@ -345,6 +345,9 @@ int space_to_depth_launch(sr_ctx* ctx, const float* x, int B, int H, int W, int 
 // wgrad_bf16.hip: the bf16-storage pieces of a mixed-precision training step (include/sr355.h)
 int wgrad_bf16_launch(sr_ctx* ctx, const bf16_t* x, int64_t x_cs, const bf16_t* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, float scale, float* dw, float* db,
                       hipStream_t st);
+int wgrad_group_bf16_launch(sr_ctx* ctx, const sr_wgrad_job* jobs, int n, int B, int H, int W, hipStream_t st);
+int eltwise_views_bf16_launch(sr_ctx* ctx, int op, const bf16_t* a, int64_t a_cs, const bf16_t* b, int64_t b_cs, float alpha, float beta, bf16_t* out, int64_t o_cs, int64_t npix,
+                              int C, hipStream_t st);
 int relu_bwd_bf16_launch(sr_ctx* ctx, const bf16_t* dy, const bf16_t* y, bf16_t* out, int64_t n, hipStream_t st);
 int space_to_depth_bf16_launch(sr_ctx* ctx, const bf16_t* x, int B, int H, int W, int C, int r, bf16_t* y, hipStream_t st);
 int mse_clip_grad_bf16_launch(sr_ctx* ctx, const bf16_t* pre, const float* t, int64_t n, float* loss, bf16_t* dpre, float* y, hipStream_t st);

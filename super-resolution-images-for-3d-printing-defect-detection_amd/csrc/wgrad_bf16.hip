@@ -1,9 +1,10 @@
 // wgrad_bf16.hip -- the bf16-storage pieces of a mixed-precision training step (EDSR_model.py:127-176 trained with bf16 activations and activation
 // gradients, fp32 master weights / gradients / optimiser; include/sr355.h, DESIGN.md "Mixed-precision training"):
-//   * wgrad3_bf16_kernel: dW[ky,kx,ci,co] = scale * sum over pixels of X[b, y+ky-1, x+kx-1, ci] * dY[b,y,x,co] of a 3x3 SAME conv on bf16 X and dY, fp32 out, on
+//   * wgrad3_bf16_group_kernel: dW[ky,kx,ci,co] = scale * sum over pixels of X[b, y+ky-1, x+kx-1, ci] * dY[b,y,x,co] of a 3x3 SAME conv on bf16 X and dY, fp32 out, on
 //     v_mfma_f32_32x32x16_bf16.  The reduction axis is the pixel axis and both tensors are channel-contiguous, so both MFMA operands (8 consecutive pixels of one
 //     channel per lane) are transposes of what memory holds: the tiles are staged PIXEL-major, as they lie in memory, and read with ds_read_b64_tr_b16.
-//   * relu_bwd / space_to_depth on bf16 (selects and permutations: bit-exact), and the fused clip + MSE loss + loss gradient.
+//     One launch serves up to SR_WGRAD_GROUP_MAX layers that share [B,H,W] (sr_conv2d_wgrad_group_bf16: the five layers of a dense block read prefixes of one buffer).
+//   * relu_bwd / space_to_depth on bf16 (selects and permutations: bit-exact), the same select and an axpby on channel ranges, and the fused clip + MSE loss + loss gradient.
 #include "common.h"
 #include "fp_sep.h"
 
@@ -48,13 +49,36 @@ __device__ __forceinline__ u16x8 stage8(const uint16_t* src, int c, int C, bool 
     return v;
 }
 
-__global__ void __launch_bounds__(256) wgrad3_bf16_kernel(const uint16_t* x, int64_t x_cs, const uint16_t* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, int nci,
-                                                          int nco, int tiles_per_wg, int tilesX, int tilesY, float* partial, double* bpart) {
+// A group of layers in one launch: blockIdx.x enumerates the (cin block, cout block) pairs of all jobs in job order, job j owning pairs [pair0, next job's pair0); the table
+// travels by value in the kernel arguments (no upload, no sync).  Every job shares [B,H,W], hence the tile walk and the trip counts below: workgroup-uniform whatever the job.
+struct WgJob {
+    const uint16_t* x;  int64_t x_cs;     // first channel of the view, channels per pixel of its buffer
+    const uint16_t* dy; int64_t dy_cs;
+    float* dw; float* db;                 // HWIO [9][Cin][Cout], [Cout] or null
+    int Cin, Cout, nci, nco;
+    int pair0, bco0;                      // first pair; first 32-cout block among the group's bias partials
+    float scale;
+};
+struct WgTable { WgJob j[SR_WGRAD_GROUP_MAX]; int n, npairs, nbco; };
+
+__device__ __forceinline__ int wg_job_of(const WgTable& t, int pair) {
+    int j = 0;
+#pragma unroll
+    for (int q = 1; q < SR_WGRAD_GROUP_MAX; ++q) j += (q < t.n && pair >= t.j[q].pair0) ? 1 : 0;
+    return j;
+}
+
+__global__ void __launch_bounds__(256) wgrad3_bf16_group_kernel(const WgTable tab, int B, int H, int W, int tiles_per_wg, int tilesX, int tilesY, float* partial, double* bpart) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[WB_XT_BYTES + WB_DT_BYTES];
     uint16_t* xt = reinterpret_cast<uint16_t*>(smem);                     // [WB_PH * WB_PW pixels][32 channels]
     uint16_t* dt = reinterpret_cast<uint16_t*>(smem + WB_XT_BYTES);       // [WB_NPIX pixels][32 channels]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, k = lane >> 5;
-    const int cob = blockIdx.x % nco, cib = blockIdx.x / nco;
+    const WgJob& jb = tab.j[wg_job_of(tab, blockIdx.x)];
+    const uint16_t* x = jb.x; const uint16_t* dy = jb.dy;
+    const int64_t x_cs = jb.x_cs, dy_cs = jb.dy_cs;
+    const int Cin = jb.Cin, Cout = jb.Cout, nco = jb.nco;
+    const int lp = blockIdx.x - jb.pair0;                                 // the pair within its job
+    const int cob = lp % nco, cib = lp / nco;
     const int ci0 = cib * 32, co0 = cob * 32;
     const int ntile = B * tilesY * tilesX;
     const int t0 = blockIdx.y * tiles_per_wg, t1 = min(ntile, t0 + tiles_per_wg);
@@ -64,7 +88,7 @@ __global__ void __launch_bounds__(256) wgrad3_bf16_kernel(const uint16_t* x, int
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-    const bool do_b = bpart != nullptr && cib == 0;
+    const bool do_b = jb.db != nullptr && cib == 0;
     double bsum = 0.0;                                             // cout tid & 31, pixel group tid >> 5
     // this lane's share of a transposed read: pixel q of the 4-pixel block of its 16-lane group, channels 4 p .. 4 p + 3 of the group's 16
     const int tg = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
@@ -117,7 +141,6 @@ __global__ void __launch_bounds__(256) wgrad3_bf16_kernel(const uint16_t* x, int
         }
     }
     float* red = reinterpret_cast<float*>(smem);                   // 4 x 1024 floats over the two tiles' space
-    const int ntiles_out = 9 * nci * nco;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         __syncthreads();
@@ -127,7 +150,7 @@ __global__ void __launch_bounds__(256) wgrad3_bf16_kernel(const uint16_t* x, int
             red[wave * 1024 + row * 32 + i] = acc[t][e];
         }
         __syncthreads();
-        float* out = partial + (((size_t)blockIdx.y * ntiles_out + (t * nci + cib) * nco + cob) * 1024);
+        float* out = partial + (((size_t)blockIdx.y * tab.npairs + blockIdx.x) * 9 + t) * 1024;
         for (int e = tid; e < 1024; e += 256) out[e] = (red[e] + red[1024 + e]) + (red[2048 + e] + red[3072 + e]);
     }
     if (do_b) {
@@ -138,33 +161,35 @@ __global__ void __launch_bounds__(256) wgrad3_bf16_kernel(const uint16_t* x, int
         if (tid < 32) {
             double t2 = 0.0;
             for (int j = 0; j < 8; ++j) t2 += bred[j * 32 + tid];
-            bpart[((size_t)blockIdx.y * nco + cob) * 32 + tid] = t2;
+            bpart[((size_t)blockIdx.y * tab.nbco + jb.bco0 + cob) * 32 + tid] = t2;
         }
     }
 }
 
-// one thread per element of a quarter (blockIdx.y) of one 32x32 tile: the splits' partial tiles in split order, times `scale` in fp32; dw is HWIO [tap][Cin][Cout]
-__global__ void wgrad_bf16_finish_kernel(const float* partial, int ntiles, int nsplit, int Cin, int Cout, int nci, int nco, float scale, float* dw, const double* bpart, float* db) {
-    const int tile = blockIdx.x;
-    int t = tile;
-    const int cob = t % nco; t /= nco;
-    const int cib = t % nci;
-    const int tap = t / nci;
+// one thread per element of a quarter (blockIdx.y) of one 32x32 tile (blockIdx.x = pair * 9 + tap): the splits' partial tiles in split order, times the job's `scale` in
+// fp32; dw is the job's HWIO [tap][Cin][Cout]
+__global__ void wgrad_bf16_finish_kernel(const WgTable tab, const float* partial, int nsplit, const double* bpart) {
+    const int pair = blockIdx.x / 9, tap = blockIdx.x - pair * 9;
+    const WgJob& jb = tab.j[wg_job_of(tab, pair)];
+    const int Cin = jb.Cin, Cout = jb.Cout, nco = jb.nco;
+    const int lp = pair - jb.pair0;
+    const int cob = lp % nco, cib = lp / nco;
+    const float scale = jb.scale;
     {
         const int e = blockIdx.y * 256 + threadIdx.x;
         const int ci = cib * 32 + e / 32, co = cob * 32 + (e & 31);
         if (ci < Cin && co < Cout) {
             float s = 0.f;
 #pragma unroll 16
-            for (int sp = 0; sp < nsplit; ++sp) s += partial[((size_t)sp * ntiles + tile) * 1024 + e];
-            dw[((size_t)tap * Cin + ci) * Cout + co] = mul_sep(scale, s);
+            for (int sp = 0; sp < nsplit; ++sp) s += partial[(((size_t)sp * tab.npairs + pair) * 9 + tap) * 1024 + e];
+            jb.dw[((size_t)tap * Cin + ci) * Cout + co] = mul_sep(scale, s);
         }
     }
-    if (bpart && db && tap == 0 && cib == 0 && blockIdx.y == 0 && threadIdx.x < 32 && cob * 32 + (int)threadIdx.x < Cout) {
+    if (jb.db && tap == 0 && cib == 0 && blockIdx.y == 0 && threadIdx.x < 32 && cob * 32 + (int)threadIdx.x < Cout) {
         double t2 = 0.0;
 #pragma unroll 16
-        for (int sp = 0; sp < nsplit; ++sp) t2 += bpart[((size_t)sp * nco + cob) * 32 + threadIdx.x];
-        db[cob * 32 + threadIdx.x] = (float)((double)scale * t2);
+        for (int sp = 0; sp < nsplit; ++sp) t2 += bpart[((size_t)sp * tab.nbco + jb.bco0 + cob) * 32 + threadIdx.x];
+        jb.db[cob * 32 + threadIdx.x] = (float)((double)scale * t2);
     }
 }
 
@@ -179,6 +204,33 @@ __global__ void relu_bwd_bf16_kernel(const uint16_t* dy, const uint16_t* y, uint
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const uint16_t v = y[i], mag = v & 0x7fffu;
         out[i] = (!(v & 0x8000u) && mag != 0 && mag <= 0x7f80u) ? dy[i] : (uint16_t)0;
+    }
+}
+
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+// the same select, and alpha * a + beta * b (fp32 arithmetic on the widened values, one rounding to nearest even), over C channels of every pixel of bf16 buffers: a / b /
+// out point at their view's first channel, *_cs are the buffers' channels per pixel (a dense block's dz_k read off G and F where they lie; an RRDB's dX1 + dR)
+template <bool RELU>
+__global__ void eltwise_views_bf16_kernel(const uint16_t* a, int64_t a_cs, const uint16_t* b, int64_t b_cs, float alpha, float beta, uint16_t* out, int64_t o_cs, int64_t npix, int C) {
+    const int64_t n = npix * C;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n; idx += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t pix = idx / C;
+        const int c = (int)(idx - pix * C);
+        const uint16_t av = a[pix * a_cs + c];
+        if (RELU) {
+            const uint16_t v = b[pix * b_cs + c], mag = v & 0x7fffu;
+            out[pix * o_cs + c] = (!(v & 0x8000u) && mag != 0 && mag <= 0x7f80u) ? av : (uint16_t)0;
+        } else {
+            float r = alpha * bf16_bits_to_f32(av);
+            if (b) r += beta * bf16_bits_to_f32(b[pix * b_cs + c]);
+            out[pix * o_cs + c] = f32_to_bf16_rne(r);
+        }
     }
 }
 
@@ -200,13 +252,6 @@ __global__ void space_to_depth_bf16_kernel(const uint16_t* x, int B, int H, int 
 // evaluation of np.float32(2 / n) * (y - t)), then one round to nearest even; loss = mean (y - t)^2: every difference and square exact in fp64, a thread adds its
 // elements in index order, the workgroup's 256 sums go through a fixed LDS tree, the workgroups' partial sums are added by one thread in block order.
 constexpr int MSE_MAX_BLOCKS = 1024;
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
 
 __global__ void __launch_bounds__(256) mse_clip_grad_bf16_kernel(const uint16_t* __restrict__ pre, const float* __restrict__ t, int64_t n, float c, uint16_t* __restrict__ dpre,
                                                                  float* __restrict__ y, double* __restrict__ partial) {
@@ -242,30 +287,70 @@ __global__ void mse_finish_kernel(const double* partial, int nblk, double n, flo
 
 }  // namespace
 
-int wgrad_bf16_launch(sr_ctx* ctx, const bf16_t* x, int64_t x_cs, const bf16_t* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, float scale, float* dw, float* db,
-                      hipStream_t st) {
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: empty tensor");
-    if (x_cs < Cin || dy_cs < Cout) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: a channel stride is smaller than its channel count");
-    const int nci = (Cin + 31) / 32, nco = (Cout + 31) / 32;
-    if ((int64_t)nci * nco > 0x7fffffff / 9) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: too many channels");
-    const int ntiles = 9 * nci * nco;
+int wgrad_group_bf16_launch(sr_ctx* ctx, const sr_wgrad_job* jobs, int n, int B, int H, int W, hipStream_t st) {
+    if (n < 1 || n > SR_WGRAD_GROUP_MAX || !jobs) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: a group has 1 to 8 jobs");
+    if (B <= 0 || H <= 0 || W <= 0) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: empty tensor");
+    WgTable tab = {};
+    int64_t npairs = 0;
+    int nbco = 0;
+    bool any_b = false;
+    for (int q = 0; q < n; ++q) {
+        const sr_wgrad_job& s = jobs[q];
+        WgJob& d = tab.j[q];
+        if (!s.x.p || !s.dy.p || !s.dw) return ctx->fail(SR_ERR_INVALID, "null tensor");
+        if (s.Cin <= 0 || s.Cout <= 0) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: empty tensor");
+        if (s.x.coff < 0 || s.dy.coff < 0 || s.x.cs - s.x.coff < s.Cin || s.dy.cs - s.dy.coff < s.Cout)
+            return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: a channel stride is smaller than its channel count");
+        d.x = static_cast<const uint16_t*>(s.x.p) + s.x.coff; d.x_cs = s.x.cs;
+        d.dy = static_cast<const uint16_t*>(s.dy.p) + s.dy.coff; d.dy_cs = s.dy.cs;
+        d.dw = s.dw; d.db = s.db; d.scale = s.scale;
+        d.Cin = s.Cin; d.Cout = s.Cout; d.nci = (s.Cin + 31) / 32; d.nco = (s.Cout + 31) / 32;
+        d.pair0 = (int)npairs; d.bco0 = nbco;
+        npairs += (int64_t)d.nci * d.nco;
+        if (npairs > 0x7fffffff / 9) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: too many channels");
+        nbco += d.nco;
+        any_b = any_b || s.db;
+    }
+    tab.n = n; tab.npairs = (int)npairs; tab.nbco = nbco;
     const int tilesX = (W + WB_TW - 1) / WB_TW, tilesY = (H + WB_TH - 1) / WB_TH;
     if ((int64_t)B * tilesY * tilesX > 0x7fffffff) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: too many tiles");
     const int ntile = B * tilesY * tilesX;
-    // pixel splits: enough workgroups for ~1.5 per CU, each a whole number of tiles
-    int nsplit = (3 * ctx->cu_count() / 2 + nci * nco - 1) / (nci * nco);
+    // pixel splits: enough workgroups for ~1.5 per CU over all the group's pairs, each a whole number of tiles
+    int nsplit = (3 * ctx->cu_count() / 2 + tab.npairs - 1) / tab.npairs;
     if (nsplit > ntile) nsplit = ntile;
     if (nsplit > WB_MAX_SPLIT) nsplit = WB_MAX_SPLIT;
     if (nsplit < 1) nsplit = 1;
     const int tiles_per_wg = (ntile + nsplit - 1) / nsplit;
     nsplit = (ntile + tiles_per_wg - 1) / tiles_per_wg;
-    const size_t tile_bytes = (size_t)nsplit * ntiles * 1024 * sizeof(float);
-    float* partial = static_cast<float*>(ctx->scratch(tile_bytes + (size_t)nsplit * nco * 32 * sizeof(double)));
+    const size_t tile_bytes = (size_t)nsplit * tab.npairs * 9 * 1024 * sizeof(float);
+    float* partial = static_cast<float*>(ctx->scratch(tile_bytes + (size_t)nsplit * nbco * 32 * sizeof(double)));
     if (!partial) return SR_ERR_OOM;
-    double* bpart = db ? reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + tile_bytes) : nullptr;
-    hipLaunchKernelGGL(wgrad3_bf16_kernel, dim3(nci * nco, nsplit), dim3(256), 0, st, reinterpret_cast<const uint16_t*>(x), x_cs, reinterpret_cast<const uint16_t*>(dy), dy_cs, B, H, W,
-                       Cin, Cout, nci, nco, tiles_per_wg, tilesX, tilesY, partial, bpart);
-    hipLaunchKernelGGL(wgrad_bf16_finish_kernel, dim3(ntiles, 4), dim3(256), 0, st, partial, ntiles, nsplit, Cin, Cout, nci, nco, scale, dw, bpart, db);
+    double* bpart = any_b ? reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + tile_bytes) : nullptr;
+    hipLaunchKernelGGL(wgrad3_bf16_group_kernel, dim3(tab.npairs, nsplit), dim3(256), 0, st, tab, B, H, W, tiles_per_wg, tilesX, tilesY, partial, bpart);
+    hipLaunchKernelGGL(wgrad_bf16_finish_kernel, dim3(tab.npairs * 9, 4), dim3(256), 0, st, tab, partial, nsplit, bpart);
+    SR_HIP(ctx, hipGetLastError());
+    return SR_OK;
+}
+
+// one layer: the group of one job (the same tiles, splits and orders of summation)
+int wgrad_bf16_launch(sr_ctx* ctx, const bf16_t* x, int64_t x_cs, const bf16_t* dy, int64_t dy_cs, int B, int H, int W, int Cin, int Cout, float scale, float* dw, float* db,
+                      hipStream_t st) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return ctx->fail(SR_ERR_INVALID, "wgrad_bf16: empty tensor");
+    sr_wgrad_job jb = {};
+    jb.x = sr_view{x, x_cs, 0}; jb.dy = sr_view{dy, dy_cs, 0};
+    jb.Cin = Cin; jb.Cout = Cout; jb.scale = scale; jb.dw = dw; jb.db = db;
+    return wgrad_group_bf16_launch(ctx, &jb, 1, B, H, W, st);
+}
+
+int eltwise_views_bf16_launch(sr_ctx* ctx, int op, const bf16_t* a, int64_t a_cs, const bf16_t* b, int64_t b_cs, float alpha, float beta, bf16_t* out, int64_t o_cs, int64_t npix,
+                              int C, hipStream_t st) {
+    if (npix <= 0 || C <= 0) return ctx->fail(SR_ERR_INVALID, "eltwise_views_bf16: empty tensor");
+    if (op != SR_ELT_AXPBY && op != SR_ELT_RELU_BWD) return ctx->fail(SR_ERR_INVALID, "eltwise_views_bf16: AXPBY and RELU_BWD only");
+    if (op == SR_ELT_RELU_BWD && !b) return ctx->fail(SR_ERR_INVALID, "eltwise_views_bf16: RELU_BWD needs the activation as b");
+    const uint16_t* ap = reinterpret_cast<const uint16_t*>(a); const uint16_t* bp = reinterpret_cast<const uint16_t*>(b);
+    uint16_t* op_ = reinterpret_cast<uint16_t*>(out);
+    if (op == SR_ELT_RELU_BWD) hipLaunchKernelGGL(eltwise_views_bf16_kernel<true>, dim3(grid_n(npix * C)), dim3(256), 0, st, ap, a_cs, bp, b_cs, alpha, beta, op_, o_cs, npix, C);
+    else hipLaunchKernelGGL(eltwise_views_bf16_kernel<false>, dim3(grid_n(npix * C)), dim3(256), 0, st, ap, a_cs, bp, b_cs, alpha, beta, op_, o_cs, npix, C);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
 }

@@ -39,6 +39,11 @@ class PackDesc(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("K", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32), ("rot", C.c_int32)]
 
 
+class WgradJob(C.Structure):
+    """sr_wgrad_job: one layer of sr_conv2d_wgrad_group_bf16 (include/sr355.h)."""
+    _fields_ = [("x", View), ("dy", View), ("Cin", C.c_int32), ("Cout", C.c_int32), ("scale", C.c_float), ("dw", C.c_void_p), ("db", C.c_void_p)]
+
+
 class SnDesc(C.Structure):
     """sr_sn_desc: one spectrally normalised kernel of a flat parameter bucket (include/sr355.h)."""
     _fields_ = [("koff", C.c_int64), ("K", C.c_int32), ("Cout", C.c_int32), ("uoff", C.c_int64)]
@@ -102,6 +107,9 @@ SIGNATURES = {
     "sr_relu_bwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "sr_space_to_depth_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "sr_mse_clip_grad_bf16": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "sr_conv2d_dev_views_bf16": (_i, [_vp, _vw, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vw, _f, _vw, _f, _vw, _vp]),
+    "sr_conv2d_wgrad_group_bf16": (_i, [_vp, C.POINTER(WgradJob), _i, _i, _i, _i, _vp]),
+    "sr_eltwise_views_bf16": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
     "sr_conv2d_wgrad_views": (_i, [_vp, _vw, _vw, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_eltwise_views": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
     "sr_eltwise": (_i, [_vp, _i, _vp, _vp, _f, _f, _vp, _i64, _vp]),

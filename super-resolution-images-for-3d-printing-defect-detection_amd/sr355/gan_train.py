@@ -21,6 +21,9 @@ backward (sr_disc_head_step), and the step's six loss scalars come back in one c
 The generator's parameters are device-resident in both modes; kernels are packed into MFMA fragment order on the device per layer call
 (sr_conv2d_dev); the tape bookkeeping stays on the host.  cfg3's throughput is the `cfg3 ESRGAN _train_step` row of bench.py --full
 (sr355/bench_rows.py cfg3_train_step), and tools/bench_train.py measures it alone, in either mode.
+train_dtype="bf16" (opt-in; ESRGANTrainer, ESRGAN) runs the RRDB trunk of the taped training pass in bf16 mixed precision -- Tape.trunk_bf16, one tape op
+on bf16 concat buffers with fp32 master weights and gradients; everything outside the trunk, and the default, stay fp32 (DESIGN.md 3.26;
+tools/bench_esrgan_mixed.py measures it against the fp32 trainer).
 """
 import contextlib
 
@@ -28,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .train import Adam, DeviceAdam, ParamBucket, _rot
+from .train import Adam, DeviceAdam, FlatGrads, ParamBucket, _rot
 
 
 # ----------------------------------------------------------------------------------------------------------------- tape
@@ -43,6 +46,35 @@ def check_attention_impl(value):
     return value
 
 
+TRAIN_DTYPES = ("f32", "bf16")
+
+
+def check_train_dtype(value):
+    """What the taped training pass stores inside the RRDB trunk: "f32" (the default, the reference's training) or "bf16" (bf16 activations and activation
+    gradients between the trunk's kernels, fp32 everywhere else: Tape.trunk_bf16)."""
+    if value not in TRAIN_DTYPES:
+        raise ValueError(f"train_dtype must be one of {TRAIN_DTYPES}, got {value!r}")
+    return value
+
+
+def trunk_layers(weights, num_rrdb):
+    """The trunk's conv layers in forward order; ValueError where a dense block's growth width is not a whole number of the bf16 conv kernels' 32-channel chunks."""
+    names = []
+    for b in range(num_rrdb):
+        for d in (1, 2, 3):
+            n = f"rrdb_{b}_dense{d}"
+            for k in range(1, 5):
+                g = weights[f"{n}_conv{k}"][0].shape[3]
+                if g % 32 != 0:
+                    raise ValueError(f"train_dtype='bf16': {n}_conv{k} has {g} growth channels; the bf16 conv kernels work in chunks of 32 channels "
+                                     f"(growth_channels must be a multiple of 32; train this graph with train_dtype='f32')")
+            c0 = weights[f"{n}_conv5"][0].shape[3]
+            if c0 % 32 != 0:
+                raise ValueError(f"train_dtype='bf16': {n}_conv5 has {c0} output channels; the bf16 conv kernels work in chunks of 32 channels")
+            names += [f"{n}_conv{k}" for k in range(1, 6)]
+    return names
+
+
 class Var:
     __slots__ = ("v", "g", "need")
 
@@ -54,9 +86,14 @@ class Tape:
     """Reverse-mode bookkeeping: ops push a closure; backward() runs them last-to-first.  Parameter gradients land in `grads`
     ({layer: [dk, db]}, summed over uses) when `wgrad` is on."""
 
-    def __init__(self, ctx, weights, wgrad=True, devcache=None, attention_impl="materialised"):
+    def __init__(self, ctx, weights, wgrad=True, devcache=None, attention_impl="materialised", trunk_dtype="f32", flat_grads=None):
         self.ctx, self.w, self.wgrad = ctx, weights, wgrad
         self.attention_impl = check_attention_impl(attention_impl)
+        self.trunk_dtype = check_train_dtype(trunk_dtype)      # "bf16": generator_forward runs the RRDB trunk as ONE op on bf16 buffers (trunk_bf16)
+        # A FlatGrads of the parameter bucket: the trunk's weight-gradient kernels write straight into its views, the fp32 layers' gradients are copied into
+        # theirs, and `grads` holds the views of the layers written so far; ParamBucket.gather then hands the flat tensor on as it is.
+        self.flat = flat_grads
+        self.trunk_tape = None                                  # tests: a list here receives (name, tensor) for every tensor trunk_bf16 stores
         self.ops, self.grads = [], {}
         self.masks = None                                       # diagnostics: a dict here collects {layer: activation > 0} of every ReLU / LeakyReLU conv
         self.dev = devcache if devcache is not None else {}     # id(host array) -> (host array, device tensor): one upload per array
@@ -75,7 +112,13 @@ class Tape:
         var.g = g if var.g is None else self.ctx.eltwise(L.ELT_AXPBY, var.g, g, 1.0, 1.0)
 
     def _pgrad(self, name, dw, db):
-        if name in self.grads:
+        if self.flat is not None:
+            vw, vb = self.flat[name]
+            first = name not in self.grads
+            vw.copy_(dw if first else self.ctx.eltwise(L.ELT_AXPBY, vw, dw, 1.0, 1.0))
+            vb.copy_(db if first else self.ctx.eltwise(L.ELT_AXPBY, vb, db, 1.0, 1.0))
+            self.grads[name] = [vw, vb]
+        elif name in self.grads:
             self.grads[name][0] = self.ctx.eltwise(L.ELT_AXPBY, self.grads[name][0], dw, 1.0, 1.0)
             self.grads[name][1] = self.ctx.eltwise(L.ELT_AXPBY, self.grads[name][1], db, 1.0, 1.0)
         else:
@@ -173,6 +216,113 @@ class Tape:
         self.ops.append(bwd)
         return y
 
+    def trunk_bf16(self, x, num_rrdb, tape=None):
+        """The RRDB trunk (ESRGAN_model.py:212-300: num_rrdb x three dense blocks, each RRDB closed by r_in + 0.2 * x) as ONE tape op in bf16 mixed precision
+        (DESIGN.md 3.26).  x: the fp32 output of initial_conv; returns the fp32 input of trunk_conv (a widening, exact).  Every tensor in between is bf16:
+        each kernel widens to fp32, accumulates and applies its whole epilogue in fp32 and rounds once on store.
+        Forward: F = [x | f1 | f2 | f3 | f4] is one bf16 buffer per dense block; conv k reads its channel prefix and writes slice k; conv5's epilogue
+        x + 0.2 * conv5 -- for an RRDB's third block r_in + 0.2 * (x + 0.2 * conv5), r_in being slice 0 of the RRDB's first F -- writes slice 0 of the NEXT block's F.
+        Backward, per block: G = a5 * dgrad(dY, conv5) fills a buffer of F's shape; for k = 4..2 dz_k = G slice k where F slice k > 0, G[..., :cin_k] += dgrad(dz_k)
+        in place; dX = dgrad(dz_1) + G[..., :64] + bx * dY; the five layers' weight and bias gradients by one grouped launch, written into the flat gradient
+        bucket (conv5's scaled by a5: there is no stored a5 * dY).  Per RRDB one add: d r_in = dX1 + dR.
+        With `tape` (default: the tape's `trunk_tape`) a list, every stored tensor is appended as (name, tensor) -- x0_f32 (the fp32 input), F_b_d, out, dout_f32 (the fp32 gradient
+        arriving), dR_last, then per block in reverse G_b_d_s5 / _s4 / _s3 / _s2 (G as a clone after conv5's input gradient and after each in-place accumulate),
+        dz_b_d (dz_k is channel slice k - 1), dX_b_d and per RRDB drin_b."""
+        ctx = self.ctx
+        if self.flat is None and self.wgrad:
+            raise ValueError("trunk_bf16: the weight gradients need a FlatGrads to write into")
+        BF = torch.bfloat16
+        B, H, W, C0 = x.v.shape
+        tape = self.trunk_tape if tape is None else tape
+        rec = tape.append if tape is not None else None
+        blocks = []                                             # (b, d, name, F, growth, ws, a5, bx)
+        g0 = self.w["rrdb_0_dense1_conv1"][0].shape[3]
+        F = ctx.empty((B, H, W, C0 + 4 * g0), BF)
+        F[..., :C0].copy_(x.v)                                  # the one rounding of x0, into slice 0 of the first F
+        if rec:
+            rec(("x0_f32", x.v))
+        out = None
+        for b in range(num_rrdb):
+            r_in = F
+            for d in (1, 2, 3):
+                name = f"rrdb_{b}_dense{d}"
+                ws = [self.w[f"{name}_conv{k}"] for k in range(1, 6)]
+                g = ws[0][0].shape[3]
+                Ct = C0 + 4 * g
+                for k in range(1, 5):
+                    kk, bb = ws[k - 1]
+                    cin = C0 + (k - 1) * g
+                    ctx.conv2d_dev_view_bf16(F, 0, cin, self._dev(kk), self._dev(bb), g, F, cin, act="relu")
+                    if self.masks is not None:
+                        self.masks[f"{name}_conv{k}"] = F[..., cin:cin + g] > 0
+                last = b == num_rrdb - 1 and d == 3
+                if last:
+                    nxt = out = ctx.empty((B, H, W, C0), BF)
+                else:
+                    nn = f"rrdb_{b}_dense{d + 1}" if d < 3 else f"rrdb_{b + 1}_dense1"
+                    nxt = ctx.empty((B, H, W, C0 + 4 * self.w[f"{nn}_conv1"][0].shape[3]), BF)
+                k5, b5 = ws[4]
+                if d < 3:
+                    a5, bx = 0.2, 1.0
+                    ctx.conv2d_dev_view_bf16(F, 0, Ct, self._dev(k5), self._dev(b5), C0, nxt, 0, alpha=a5, skip1=(F, 0), beta1=bx)
+                else:                                           # r_in + 0.2 * (x + 0.2 * conv5) in one epilogue, one rounding
+                    a5, bx = 0.04, 0.2
+                    ctx.conv2d_dev_view_bf16(F, 0, Ct, self._dev(k5), self._dev(b5), C0, nxt, 0, alpha=a5, skip1=(F, 0), beta1=bx, skip2=(r_in, 0), beta2=1.0)
+                if rec:
+                    rec((f"F_{b}_{d}", F))
+                blocks.append((b, d, name, F, g, ws, a5, bx))
+                F = nxt
+        if rec:
+            rec(("out", out))
+        y = Var(out.float())
+
+        def bwd():
+            if y.g is None:
+                return
+            dR = y.g.to(BF)                                     # the one rounding of the gradient entering the trunk
+            if rec:
+                rec(("dout_f32", y.g))
+                rec((f"dR_{num_rrdb - 1}", dR))
+            dY = dR
+            for b, d, name, F, g, ws, a5, bx in reversed(blocks):
+                Ct = C0 + 4 * g
+                G = ctx.empty((B, H, W, Ct), BF)
+                ctx.conv2d_dev_view_bf16(dY, 0, C0, self._dev(ws[4][0]), None, Ct, G, 0, rot=True, alpha=a5)        # fills every channel of G
+                if rec:
+                    rec((f"G_{b}_{d}_s5", G.clone()))
+                dz = ctx.empty((B, H, W, 4 * g), BF)            # dz_k is slice k - 1
+                for k in range(4, 0, -1):
+                    kk = self._dev(ws[k - 1][0])
+                    cin = C0 + (k - 1) * g
+                    ctx.eltwise_view_bf16(L.ELT_RELU_BWD, G, cin, F, cin, dz, (k - 1) * g, g)                      # slice k of G is complete: convs k+1..5 have added to it
+                    if k > 1:
+                        ctx.conv2d_dev_view_bf16(dz, (k - 1) * g, g, kk, None, cin, G, 0, rot=True, skip1=(G, 0), beta1=1.0)       # G[..., :cin] += dgrad
+                        if rec:
+                            rec((f"G_{b}_{d}_s{k}", G.clone()))
+                    else:
+                        dX = ctx.empty((B, H, W, C0), BF)
+                        ctx.conv2d_dev_view_bf16(dz, 0, g, kk, None, C0, dX, 0, rot=True, skip1=(G, 0), beta1=1.0, skip2=(dY, 0), beta2=bx)
+                if self.wgrad:
+                    jobs = [(F, 0, C0 + (k - 1) * g, dz, (k - 1) * g, g, 1.0) + tuple(self.flat[f"{name}_conv{k}"]) for k in range(1, 5)]
+                    jobs.append((F, 0, Ct, dY, 0, C0, a5) + tuple(self.flat[f"{name}_conv5"]))
+                    ctx.conv2d_wgrad_group_bf16(jobs)
+                    for k in range(1, 6):
+                        self.grads[f"{name}_conv{k}"] = list(self.flat[f"{name}_conv{k}"])
+                if rec:
+                    rec((f"dz_{b}_{d}", dz))
+                    rec((f"dX_{b}_{d}", dX))
+                dY = dX
+                if d == 1:
+                    d_rin = ctx.empty((B, H, W, C0), BF)
+                    ctx.eltwise_view_bf16(L.ELT_AXPBY, dX, 0, dR, 0, d_rin, 0, C0, 1.0, 1.0)
+                    if rec:
+                        rec((f"drin_{b}", d_rin))
+                    dR = dY = d_rin
+            if x.need:
+                self._acc(x, dR.float())
+        self.ops.append(bwd)
+        return y
+
     def axpby(self, a, b, alpha, beta):
         y = Var(self.ctx.eltwise(L.ELT_AXPBY, a.v, b.v, alpha, beta))
 
@@ -254,6 +404,8 @@ def generator_forward(t, x, scale, num_rrdb, attention=True):
     """ESRGAN_model.py:303-345 on the tape; x Var [B,h,w,3] in [-1,1]."""
     x = t.conv(x, "initial_conv")
     trunk = x
+    if t.trunk_dtype == "bf16":
+        x, num_rrdb = t.trunk_bf16(x, num_rrdb), 0
     for b in range(num_rrdb):
         r_in = x
         for d in (1, 2, 3):
@@ -530,9 +682,12 @@ class ESRGANTrainer:
     dw, u, d_opt, d_params = (_discriminator_attr(name) for name in ("weights", "u", "opt", "params"))
 
     def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None, discriminator="host", attention_impl="materialised"):
+                 allreduce_flat=None, discriminator="host", attention_impl="materialised", train_dtype="f32"):
         if discriminator not in ("host", "device"):
             raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
+        # what the taped training pass stores inside the RRDB trunk (Tape.trunk_bf16); refused before anything is uploaded or launched
+        self.train_dtype = check_train_dtype(train_dtype)
+        self._trunk = set(trunk_layers(g_weights, num_rrdb)) if train_dtype == "bf16" else set()
         self.attention_impl = check_attention_impl(attention_impl)      # the generator tape's SelfAttention core (Tape.attention)
         self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
         self.discriminator = discriminator
@@ -571,15 +726,24 @@ class ESRGANTrainer:
         if with_vgg not in self._packs:
             uses = []
             for params in [self.g_params] + ([self._vgg] if with_vgg else []):
-                for kd, bd in params.dev.values():
+                for n, (kd, bd) in params.dev.items():
+                    if params is self.g_params and n in self._trunk:      # train_dtype="bf16": the trunk's layers stand in the bf16 list only
+                        continue
                     if kd.dim() == 4 and kd.shape[0] == kd.shape[1] and kd.shape[0] in (1, 3):
                         uses += [(kd, bd, False), (kd, None, True)]
             self._packs[with_vgg] = self.ctx.pack_list(uses)
+        if self._trunk and "bf16" not in self._packs:         # every trunk kernel rounded to bf16 once per step, for its forward and its input-gradient use
+            dev = self.g_params.dev
+            self._packs["bf16"] = self.ctx.pack_list([u for n in dev if n in self._trunk for u in ((dev[n][0], dev[n][1], False), (dev[n][0], None, True))])
         self.ctx.conv_prepack(self._packs[with_vgg])
+        if self._trunk:
+            self.ctx.conv_prepack_bf16(self._packs["bf16"])
         try:
             yield
         finally:
             self.ctx.conv_prepack(None)
+            if self._trunk:
+                self.ctx.conv_prepack_bf16(None)
 
     @property
     def gw(self):
@@ -600,8 +764,11 @@ class ESRGANTrainer:
             self.g_opt.t = 0
 
     def generator_tape(self, wgrad=True):
-        """A tape over the generator's device-resident parameters (no upload, no host copy)."""
-        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache), attention_impl=self.attention_impl)
+        """A tape over the generator's device-resident parameters (no upload, no host copy).  With train_dtype="bf16" the taped training pass (wgrad) runs the
+        trunk in bf16 and collects every gradient in one flat bucket; the forward-only tape stays fp32."""
+        bf16 = wgrad and self.train_dtype == "bf16"
+        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache), attention_impl=self.attention_impl,
+                    trunk_dtype="bf16" if bf16 else "f32", flat_grads=FlatGrads(self.g_params) if bf16 else None)
 
     @property
     def last_grads(self):
@@ -614,9 +781,9 @@ class ESRGANTrainer:
         self._last["d"] = self.disc.last_grads()
         return self._last
 
-    def _update_generator(self, grads):
+    def _update_generator(self, tape):
         """The generator's Adam step from its tape's gradients (averaged over the ranks first when data parallel) -> the flat gradient applied."""
-        g_flat = self.g_params.gather(grads)
+        g_flat = self.g_params.gather(tape.flat if tape.flat is not None else tape.grads)
         if self.allreduce_flat is not None:
             g_flat = self.allreduce_flat(g_flat)
         elif self.allreduce is not None:                   # dict route (host): the 2-rank gloo tests
@@ -638,7 +805,7 @@ class ESRGANTrainer:
             pix = float(ctx.l1(hr_t, y.v).item())
             y.g = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 1.0 / y.v.numel(), 0.0)
             tg.backward()
-        self._update_generator(tg.grads)
+        self._update_generator(tg)
         return pix
 
     def train_step(self, lr_images, hr_images):
@@ -674,7 +841,7 @@ class ESRGANTrainer:
             l_real, l_fake, adv, perc, pix, spec = _floats([l_real, l_fake, adv, perc, pix, spec])
             y.g = self.last_dy = dy
             tg.backward()
-            self._last = {"g_flat": self._update_generator(tg.grads), "g_names": set(tg.grads)}
+            self._last = {"g_flat": self._update_generator(tg), "g_names": set(tg.grads)}
             self.last_fake = fake
         return {"g_loss": adv + 1.0 * perc + 100.0 * pix + 1.0 * spec, "d_loss": l_real + l_fake, "adversarial": adv, "perceptual": perc,
                 "pixel": pix, "spectral": spec}

@@ -878,6 +878,80 @@ class Context:
                                                  self.stream()))
         return dw, db
 
+    # ---- the same on channel ranges of bf16 buffers (sr355/gan_train.py, Tape.trunk_bf16: a dense block's virtual-concat buffers)
+    def cu_count(self):
+        """Compute units of the context's GPU (the pixel-split counts of the weight-gradient kernels follow it)."""
+        return int(torch.cuda.get_device_properties(self.torch_device).multi_processor_count)
+
+    @staticmethod
+    def _view_bf16(t, coff, c):
+        """(tensor [B,H,W,Cbuf] bf16 contiguous, first channel, channels) -> sr_view (in bf16 elements)."""
+        if not (isinstance(t, torch.Tensor) and t.dim() == 4 and t.dtype == torch.bfloat16 and t.is_contiguous() and t.is_cuda):
+            raise ValueError("a bf16 view needs a contiguous bf16 NHWC device tensor")
+        if coff < 0 or c <= 0 or coff + c > t.shape[3]:
+            raise ValueError(f"channel range [{coff}, {coff + c}) outside the buffer's {t.shape[3]} channels")
+        return L.View(t.data_ptr(), int(t.shape[3]), int(coff))
+
+    def conv2d_dev_view_bf16(self, xbuf, x_coff, cin, w_dev, b_dev, cout, ybuf, y_coff, rot=False, act="linear", alpha=1.0, skip1=None, beta1=0.0, skip2=None, beta2=0.0):
+        """conv2d_dev_view on bf16 buffers with the fp32 device kernel w_dev (sr_conv2d_dev_views_bf16): reads xbuf[..., x_coff : x_coff + cin], writes
+        ybuf[..., y_coff : y_coff + cout] = bf16(alpha * act(conv + b) + beta1 * skip1 + beta2 * skip2); skip1 / skip2: (buffer, first channel) or None -- a skip may be
+        the output range itself.  Channel offsets and buffer widths are multiples of 8, cin a multiple of 32."""
+        B, H, W, _ = xbuf.shape
+        if tuple(ybuf.shape[:3]) != (B, H, W):
+            raise ValueError("conv2d_dev_view_bf16: input and output buffers must share [B,H,W]")
+        _check_tensor(self, w_dev, "conv2d_dev_view_bf16 kernel")
+        if b_dev is not None:
+            _check_tensor(self, b_dev, "conv2d_dev_view_bf16 bias")
+        k = w_dev.shape[0]
+        want = (k, k, cout, cin) if rot else (k, k, cin, cout)
+        if tuple(w_dev.shape) != want:
+            raise ValueError(f"conv2d_dev_view_bf16: kernel shape {tuple(w_dev.shape)} does not match {want}")
+        xv, yv = self._view_bf16(xbuf, x_coff, cin), self._view_bf16(ybuf, y_coff, cout)
+        svs = []
+        for sk in (skip1, skip2):
+            if sk is not None and tuple(sk[0].shape[:3]) != (B, H, W):
+                raise ValueError("conv2d_dev_view_bf16: a skip buffer must share [B,H,W]")
+            svs.append(None if sk is None else self._view_bf16(sk[0], sk[1], cout))
+        actc = {"linear": L.ACT_LINEAR, None: L.ACT_LINEAR, "relu": L.ACT_RELU, "lrelu": L.ACT_LRELU, "tanh": L.ACT_TANH}[act]
+        self.check(self.lib.sr_conv2d_dev_views_bf16(self.h, C.byref(xv), B, H, W, int(cin), w_dev.data_ptr(), None if b_dev is None else b_dev.data_ptr(), k, int(cout),
+                                                     int(bool(rot)), actc, float(alpha), None if svs[0] is None else C.byref(svs[0]), float(beta1),
+                                                     None if svs[1] is None else C.byref(svs[1]), float(beta2), C.byref(yv), self.stream()))
+
+    def conv2d_wgrad_group_bf16(self, jobs):
+        """The kernel and bias gradients of up to 8 3x3 layers that share [B,H,W] by one main and one finish launch (sr_conv2d_wgrad_group_bf16).
+        jobs: [(xbuf, x_coff, cin, dybuf, dy_coff, cout, scale, dw fp32 [3,3,cin,cout], db fp32 [cout] or None)] on bf16 buffers; dw / db are written in place
+        (views of a flat gradient bucket)."""
+        if not jobs:
+            raise ValueError("wgrad_group_bf16: at least one job")
+        arr = (L.WgradJob * len(jobs))()
+        B, H, W, _ = jobs[0][0].shape
+        for d, (xbuf, x_coff, cin, dybuf, dy_coff, cout, scale, dw, db) in zip(arr, jobs):
+            if tuple(xbuf.shape[:3]) != (B, H, W) or tuple(dybuf.shape[:3]) != (B, H, W):
+                raise ValueError("wgrad_group_bf16: every buffer must share [B,H,W]")
+            _check_tensor(self, dw, "wgrad_group_bf16 dw")
+            if tuple(dw.shape) != (3, 3, cin, cout):
+                raise ValueError(f"wgrad_group_bf16: dw must be [3,3,{cin},{cout}], got {tuple(dw.shape)}")
+            if db is not None:
+                _check_tensor(self, db, "wgrad_group_bf16 db")
+                if tuple(db.shape) != (cout,):
+                    raise ValueError(f"wgrad_group_bf16: db must be [{cout}]")
+            d.x, d.dy = self._view_bf16(xbuf, x_coff, cin), self._view_bf16(dybuf, dy_coff, cout)
+            d.Cin, d.Cout, d.scale = int(cin), int(cout), float(scale)
+            d.dw, d.db = dw.data_ptr(), (None if db is None else db.data_ptr())
+        self.check(self.lib.sr_conv2d_wgrad_group_bf16(self.h, arr, len(jobs), B, H, W, self.stream()))
+
+    def eltwise_view_bf16(self, op, abuf, a_coff, bbuf, b_coff, obuf, o_coff, c, alpha=1.0, beta=0.0):
+        """sr_eltwise_views_bf16 over c channels of every pixel of bf16 buffers: L.ELT_RELU_BWD (out = a where b > 0, else 0: a select on bits) or L.ELT_AXPBY
+        (out = bf16(alpha * a + beta * b), bbuf None for alpha * a)."""
+        B, H, W, _ = abuf.shape
+        av, ov = self._view_bf16(abuf, a_coff, c), self._view_bf16(obuf, o_coff, c)
+        bv = None if bbuf is None else self._view_bf16(bbuf, b_coff, c)
+        for t in (bbuf, obuf):
+            if t is not None and tuple(t.shape[:3]) != (B, H, W):
+                raise ValueError("eltwise_view_bf16: every buffer must share [B,H,W]")
+        self.check(self.lib.sr_eltwise_views_bf16(self.h, int(op), C.byref(av), None if bv is None else C.byref(bv), float(alpha), float(beta), C.byref(ov), B * H * W, int(c),
+                                                  self.stream()))
+
     def relu_bwd_bf16(self, dy, y):
         """dy where y > 0, else 0, on bf16 tensors of one shape (sr_relu_bwd_bf16)."""
         _check_tensor(self, dy, "relu_bwd_bf16 dy", self._BF16)
