@@ -141,9 +141,12 @@ __global__ void __launch_bounds__(256, 3) attn_bf16_kernel(AttnParams p) {
     // projection conv, api.hip, so the scores arrive in the exp2 domain.)
     bf16x8 kneg = {};
     kneg[0] = (bf16_t)-1.f; kneg[1] = (bf16_t)-1.f; kneg[2] = (bf16_t)-1.f;
+    // The general groups' key fetch (the first group, a group whose bound failed, the tail, and a full group whose successor's first 32 keys
+    // do not all exist): keys past N are clamped to N - 1 (the ragged tile masks their scores), the fragment is rebuilt from kneg on every
+    // call and the address is per-lane 64-bit arithmetic -- about 14 vector instructions per call.  Runs of unguarded groups do not pay
+    // them: they use fetch_k below.  The lane number is re-derived here (two v_mbcnt) rather than kept: at the 168-register budget hipcc
+    // spilled the copy of r this address needs, and the reload's s_waitcnt vmcnt(0) also waited for the key fragment requested just before.
     auto load_k = [&](int kb) {
-        // the lane number is re-derived here (two v_mbcnt) rather than kept: at the 168-register budget hipcc spilled the copy of r this address
-        // needs, and the reload's s_waitcnt vmcnt(0) at the head of every key group also waited for the key fragment requested just before
         int l;
         asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
         bf16x8 kf = kneg;
@@ -232,10 +235,12 @@ __global__ void __launch_bounds__(256, 3) attn_bf16_kernel(AttnParams p) {
     // Fast tile: a full tile whose scores stay within 2^GROW_OK of the running max needs no rescale at all -- the probabilities are
     // then simply taken relative to the (stale) running max, which is exact: numerator and denominator carry the same power of two.
     // It returns false, before touching any state, when some score exceeds that bound; the caller then redoes the tile with the
-    // full logic above.  The point is what the fast loop does NOT contain: with the rescale branch inside the key loop, hipcc
-    // joins the branch's new accumulators / denominators / query fragments with the untouched ones in a phi and copies all 48
-    // registers on the common path of every tile (24 v_mov_b64), and the loop also pays the vote; a loop made of fast tiles only
-    // has neither (attention 241 -> ~185 ms per two bench steps).
+    // full logic above.  The point is what the tile does NOT contain: with the rescale branch inside the tile, hipcc joins the
+    // branch's new accumulators / denominators / query fragments with the untouched ones in a phi and copies all 48 registers on
+    // the common path of every tile (24 v_mov_b64), and the tile also pays the vote (attention 241 -> ~185 ms per two bench steps).
+    // Taking the branch out of the tile does not remove those copies by itself: any group that CAN fall back to the full logic
+    // joins the same registers where the group ends (~65 v_mov_b64 per group in the general group of the key loop below).  They
+    // are gone only from the loop of unguarded groups, which has no such branch (175 -> 149 ms per two bench steps).
     constexpr float GROW_OK = 40.f;    // 2^40 x 9216 keys x |v|: far inside fp32 for the sums and the bf16 probabilities
     // guard (wave-uniform) = false: the group-level bound below already says that no score of this group exceeds the running max of any of
     // the wave's queries by more than 2^GROW_OK -- the tile then carries no max chain and no vote: score MFMA, 16 exps, 8 converts, 3 MFMAs.
@@ -297,14 +302,16 @@ __global__ void __launch_bounds__(256, 3) attn_bf16_kernel(AttnParams p) {
     // V^T of KT2 keys into LDS, two keys per dword (every wave of the workgroup passes here once per key group, in either mode).
     // (Round 3 measured a double-buffered image with the rows requested a whole group ahead: no faster -- the loop is bound by vector
     // issue, 16 v_exp_f32 + 8 converts + 5 MFMAs per 32 x 32 scores, not by this staging -- and eight more live registers.)
-    auto stage_v = [&](const int k0) {
+    // whole_tag (as tile's ragged_tag): the caller knows that all KT2 keys exist, and the rows are fetched without the clamps.
+    auto stage_v = [&](const int k0, auto whole_tag) {
+        constexpr bool WHOLE = sizeof(whole_tag) > 1;
         __syncthreads();
 #pragma unroll
         for (int part = 0; part < KT2 / 128; ++part) {
             const int ka = k0 + part * 128 + 2 * kp, kbb = ka + 1;
-            if (ka - 2 * kp >= N) break;                  // this 128-key part lies wholly beyond the keys (workgroup-uniform)
-            const bf16x8 va = *reinterpret_cast<const bf16x8*>(base + (int64_t)(ka < N ? ka : N - 1) * cs + p.voff + oct * 8);
-            const bf16x8 vb = *reinterpret_cast<const bf16x8*>(base + (int64_t)(kbb < N ? kbb : N - 1) * cs + p.voff + oct * 8);
+            if (!WHOLE && ka - 2 * kp >= N) break;        // this 128-key part lies wholly beyond the keys (workgroup-uniform)
+            const bf16x8 va = *reinterpret_cast<const bf16x8*>(base + (int64_t)(WHOLE || ka < N ? ka : N - 1) * cs + p.voff + oct * 8);
+            const bf16x8 vb = *reinterpret_cast<const bf16x8*>(base + (int64_t)(WHOLE || kbb < N ? kbb : N - 1) * cs + p.voff + oct * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
@@ -325,29 +332,81 @@ __global__ void __launch_bounds__(256, 3) attn_bf16_kernel(AttnParams p) {
         }
     };
 
-    // Key groups: fast tiles while they last, the full logic for the rest of the group (the first group, which sets the running max,
-    // the ragged tail, and any group in which a score outgrew the bound).  The conditional slow part sits once per GROUP, so the
-    // copies its phi costs are paid once per four tiles instead of in every tile.
-    for (int k0 = 0; k0 < N; k0 += KT2) {
-        stage_v(k0);
-        int sub = 0;
-        bf16x8 kf = knext;
-        const bool full = k0 != 0 && k0 + KT2 <= N;
-        if (full) {
-            // group-level bound (scalar): every score k.q - m of this group is <= |k|max |q|max - min m; where it holds the tiles run unguarded
-            const bool guard = !(knorm_bits[k0 / KT2] <= thresh_bits);       // NaN norms have bits above every finite threshold: guarded
+    // The unguarded loop's key fetch: one global_load_dwordx4 on a scalar base (the tile's first key) plus a per-lane 32-bit offset that never
+    // changes (lane r: key r's row), issued with the upper half of the wave masked off, so lanes h == 1 of the destination keep their kneg
+    // pattern and nothing re-initialises them; the base advances in scalar registers.  No clamp: the caller only asks for 32 keys that exist.
+    // hipcc does not count a load it cannot see, so the statement that requests the next fragment first waits for the one about to be used
+    // (`use`; nothing else of this wave is in flight there: the V rows of stage_v were waited for before their LDS writes) and ties it, so
+    // that no consumer is scheduled above the wait.  The two fragments alternate (ka / kb below): the one in flight is never the one in use.
+    const unsigned kvoff = (unsigned)r * (unsigned)cs * 2u;
+    auto fetch_k = [&](bf16x8& use, bf16x8& next, const char* tile_base) {
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_mov_b32 exec_hi, 0\n\tglobal_load_dwordx4 %1, %2, %3\n\ts_mov_b32 exec_hi, -1"
+                     : "+v"(use), "+v"(next) : "v"(kvoff), "s"(tile_base) : "memory");
+    };
+    // How many key groups from g on run unguarded in the loop below: consecutive groups whose bound holds, one group per lane and one vote,
+    // so the loop itself reads no norms.  Only groups below nfast qualify: full groups other than group 0 whose last tile can request 32
+    // existing keys for the group behind it -- or, when N is a multiple of the group, nothing anyone will use.
+    const int nfast = N % KT2 == 0 ? N / KT2 : (N - 32) / KT2;
+    auto fast_run = [&](const int g) -> int {
+        if (g >= nfast) return 0;
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        const int gi = g + l;
+        const bool ok = gi < nfast && knorm_bits[gi < nfast ? gi : nfast - 1] <= thresh_bits;   // NaN norms have bits above every finite threshold
+        const unsigned long long fails = ~__ballot(ok);
+        return fails ? __builtin_ctzll(fails) : 64;
+    };
+    const char* const kimg = reinterpret_cast<const char*>(base + p.koff);
+    const int64_t tile_bytes = (int64_t)32 * cs * 2;
+
+    // Key groups.  The general group below is the first group (it sets the running max), a group whose bound failed (guarded fast tiles while
+    // they pass, the full logic for the rest), the tail, and the last full group when a ragged tile follows it.  Its conditional slow part
+    // makes hipcc join the accumulators, denominators and key registers in phis and copy them at the group's end (~65 v_mov_b64), so runs of
+    // groups whose bound holds do not pass through it: they execute in the loop behind it, whose only loop-carried vector state is oacc,
+    // lacc and the two key fragments, and which contains no branch, no vector address arithmetic and no copy.
+    for (int k0 = 0; k0 < N;) {
+        {
+            stage_v(k0, false_c);
+            int sub = 0;
+            bf16x8 kf = knext;
+            const bool full = k0 != 0 && k0 + KT2 <= N;
+            if (full) {
+                // group-level bound (scalar): every score k.q - m of this group is <= |k|max |q|max - min m; where it holds the tiles run unguarded
+                const bool guard = !(knorm_bits[k0 / KT2] <= thresh_bits);       // NaN norms have bits above every finite threshold: guarded
 #pragma unroll
-            for (; sub < KT2 / 32; ++sub) {
-                kf = knext;
-                knext = load_k(k0 + sub * 32 + 32);          // next tile's keys fly under this tile's softmax
-                if (!tile_fast(kf, sub, guard)) break;
+                for (; sub < KT2 / 32; ++sub) {
+                    kf = knext;
+                    knext = load_k(k0 + sub * 32 + 32);          // next tile's keys fly under this tile's softmax
+                    if (!tile_fast(kf, sub, guard)) break;
+                }
+            } else {
+                knext = load_k(k0 + 32);
             }
-        } else {
-            knext = load_k(k0 + 32);
+            if (sub < KT2 / 32) {
+                slow_tiles(k0, sub, kf);
+                thresh_bits = thresh_of_wave();
+            }
+            k0 += KT2;
         }
-        if (sub < KT2 / 32) {
-            slow_tiles(k0, sub, kf);
-            thresh_bits = thresh_of_wave();
+        int run = fast_run(k0 / KT2);
+        if (run > 0) {
+            bf16x8 ka = knext, kb = kneg;                          // knext holds tile 0 of group k0 (requested by the group before)
+            const char* kt = kimg + (int64_t)(k0 + 32) * cs * 2;
+            do {
+                stage_v(k0, true_c);
+                fetch_k(ka, kb, kt); kt += tile_bytes;
+                tile_fast(ka, 0, false);
+                fetch_k(kb, ka, kt); kt += tile_bytes;
+                tile_fast(kb, 1, false);
+                fetch_k(ka, kb, kt); kt += tile_bytes;
+                tile_fast(ka, 2, false);
+                // tile 0 of the next group; behind the last group of an N that is a multiple of the group, this group's tile 3 again (never used)
+                fetch_k(kb, ka, k0 + KT2 + 32 <= N ? kt : kt - tile_bytes); kt += tile_bytes;
+                tile_fast(kb, 3, false);
+                k0 += KT2;
+            } while (--run);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(ka));
+            knext = ka;
         }
     }
 #pragma unroll

@@ -16,6 +16,8 @@ Exit status 0 = proven for every conv3_rows kernel; 1 = a violation (printed wit
 
     python tools/check_prefetch_hazards.py [--keep-asm PATH]
     python tools/check_prefetch_hazards.py --source .../csrc/dense_fused.hip --match chain2_kernel --scratch-only
+    python tools/check_prefetch_hazards.py --source .../csrc/attention.hip --match attn_bf16_kernel --allow-scratch
+(the last: the key fragments the loop of unguarded groups requests with an inline-asm load)
 """
 import argparse
 import os
@@ -88,11 +90,11 @@ def parse_kernels(asm):
     return kernels
 
 
-def check_kernel(name, k):
+def check_kernel(name, k, allow_scratch=False):
     ins, labels = k["ins"], k["labels"]
     problems = []
     for t in k["meta"]:
-        if t.startswith(".amdhsa_private_segment_fixed_size") and int(t.split()[1]) != 0:
+        if not allow_scratch and t.startswith(".amdhsa_private_segment_fixed_size") and int(t.split()[1]) != 0:
             problems.append(f"{name}: uses {t.split()[1]} bytes of scratch per lane (register spills)")
     seen = set()
     work = [(0, ())]                             # (instruction index, queue of outstanding vmem ops: tuple of frozenset(dest regs))
@@ -104,7 +106,7 @@ def check_kernel(name, k):
                 break
             seen.add(key)
             no, op, args = ins[pc]
-            if op.startswith("scratch_"):
+            if op.startswith("scratch_") and not allow_scratch:
                 problems.append(f"{name}: line {no}: scratch access `{op} {args}`")
             pending = set().union(*(d for d, _ in q)) if q else set()
             pending_other = set().union(*(d for d, io in q if not io)) if q else set()     # destinations of in-flight loads that are NOT global_/buffer_ loads
@@ -161,6 +163,9 @@ def main():
     ap.add_argument("--scratch-only", action="store_true",
                     help="only prove that the matching kernels use no scratch (csrc/dense_fused.hip: a spill reload in a loader wave would "
                          "count in the vmcnt its counted waits rely on)")
+    ap.add_argument("--allow-scratch", action="store_true",
+                    help="prove item 1 only, for a kernel that spills by design (csrc/attention.hip, attn_bf16_kernel: its spill stores and reloads "
+                         "are modelled as the vector-memory operations they are, and its hand-written waits are all vmcnt(0))")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as td:
         out = args.keep_asm or os.path.join(td, "conv_rows.s")
@@ -173,7 +178,7 @@ def main():
         return 1
     spills = [int(v) for v in re.findall(r"\.vgpr_spill_count:\s*(\d+)", asm)]
     problems = []
-    if any(spills):
+    if any(spills) and not args.allow_scratch:
         problems.append(f"vgpr_spill_count is non-zero somewhere in {os.path.basename(args.source)}: {spills}")
     for n, k in kernels.items():
         if args.scratch_only:
@@ -181,7 +186,7 @@ def main():
                          if t.startswith(".amdhsa_private_segment_fixed_size") and int(t.split()[1]) != 0]
             problems += [f"{n}: line {no}: scratch access `{op} {a}`" for no, op, a in k["ins"] if op.startswith("scratch_")][:5]
         else:
-            problems += check_kernel(n, k)
+            problems += check_kernel(n, k, args.allow_scratch)
     for p in problems:
         print("HAZARD:", p)
     print(f"{len(kernels)} kernels checked, {sum(len(k['ins']) for k in kernels.values())} instructions, {len(problems)} problems")
