@@ -290,6 +290,26 @@ int  sr_conv2d_dev_views_bf16(sr_ctx* ctx, const sr_view* x, int B, int H, int W
                               int act, float alpha, const sr_view* skip1, float beta1, const sr_view* skip2, float beta2, const sr_view* y, void* stream);
 int  sr_conv2d_wgrad_group_bf16(sr_ctx* ctx, const sr_wgrad_job* jobs, int n, int B, int H, int W, void* stream);
 int  sr_eltwise_views_bf16(sr_ctx* ctx, int op, const sr_view* a, const sr_view* b, float alpha, float beta, const sr_view* out, int64_t npix, int C, void* stream);
+/* ---- a G = 8 dense block trained on the LDS-resident image (ESRGAN_model.py:212-254 at the notebook's growth width) ----
+ * The arithmetic is that of the bf16 trunk above: fp32 master kernels rounded to bf16 once per step, bf16 tensors between stages, fp32 accumulation and epilogues, one
+ * rounding per store.  All buffers are NHWC bf16; sr_view as above (cs, coff multiples of 8).
+ * sr_dense_block_pack_sizes: bytes of the forward fragments, floats of the bias table and bytes of the input-gradient fragments of ONE block.
+ * sr_dense_block_pack_dev: one launch packs nblocks blocks.  d_table: device array of nblocks x 10 pointers -- per block the five fp32 HWIO kernels [3,3,64 + 8 i,8] (i < 4) /
+ *   [3,3,96,64], then the five biases.  fwd / bias / bwd: nblocks consecutive images of the sizes above; the forward half is bit for bit what sr_model_finalize packs for
+ *   the same weights, the backward half holds the kernels rotated by 180 degrees with cin and cout swapped.
+ * sr_dense_block_fwd_bf16: F [B,H,W,f_cs >= 96]: channels [0,64) are read, slice k = bf16(relu(conv_k(F[:64 + 8 (k - 1)]) + b_k)) is written into [64,96) of the same buffer;
+ *   out (64 channels, not in F's buffer) = bf16(alpha * (conv5(F) + b5) + beta1 * F[:64] + beta2 * skip2), skip2 NULL for none.  sr_dense_block_lds_bytes(8, H, W) must be > 0.
+ * sr_dense_block_bwd_bf16: from dY (64 channels) and the stored F: G = bf16(a5 * dgrad(dY, conv5)); for k = 4 .. 2 dz_k = G slice k where F slice k > 0, else +0 (a select on
+ *   bits), G[:cin_k] = bf16(dgrad(dz_k, conv_k) + G[:cin_k]); dz_1 likewise; dX (64 channels) = bf16(dgrad(dz_1, conv1) + G[:64] + bx * dY).  dz [B,H,W,32]: dz_k in channels
+ *   [8 (k - 1), 8 k).  stages: NULL, or [4,B,H,W,96] receiving G after conv5's input gradient and after the accumulate of k = 4, 3, 2 (channels >= cin_k of the later stages
+ *   hold the dz already selected).  The image must also have (H + 2)(W + 2) <= sr_dense_block_train_max_pixels().  G never leaves the CU's LDS. */
+int  sr_dense_block_train_max_pixels(void);
+void sr_dense_block_pack_sizes(int64_t* fwd_bytes, int64_t* bias_floats, int64_t* bwd_bytes);
+int  sr_dense_block_pack_dev(sr_ctx* ctx, const void* d_table, int nblocks, void* fwd, float* bias, void* bwd, void* stream);
+int  sr_dense_block_fwd_bf16(sr_ctx* ctx, const void* fwd_w, const float* bias, void* F, int64_t f_cs, int B, int H, int W, const sr_view* out, const sr_view* skip2, float alpha,
+                             float beta1, float beta2, void* stream);
+int  sr_dense_block_bwd_bf16(sr_ctx* ctx, const void* bwd_w, const sr_view* dY, const void* F, int64_t f_cs, int B, int H, int W, float a5, float bx, void* dz, const sr_view* dX,
+                             void* stages, void* stream);
 int  sr_eltwise(sr_ctx* ctx, int op, const void* a, const void* b, float alpha, float beta, void* out, int64_t n, void* stream);
 /* keras.optimizers.Adam's dense update (the optimiser of ESRGAN_model.py:176-195, SRCNN_model.py:55-60, EDSR_model.py:127-140) over one flat
  * fp32 bucket of n parameters, in place on the device: g is first multiplied by grad_scale (1 / world size after a summing all-reduce; 1 leaves

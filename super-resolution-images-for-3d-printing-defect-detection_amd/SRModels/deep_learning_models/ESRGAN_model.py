@@ -26,7 +26,7 @@ class _Normalised:
 
 
 class ESRGAN(DeviceModelMixin):
-    def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised", train_dtype="f32"):
+    def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised", train_dtype="f32", train_dense_block="layers"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
         >= 100 dB against the fp64 oracle) or "bf16" (opt-in: bf16 storage, fp32 accumulation -- BASELINE configs[2]'s dtype and what
         bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md).
@@ -38,8 +38,11 @@ class ESRGAN(DeviceModelMixin):
         train_dtype: what the taped training forward and backward of _train_step / pixel_step store inside the RRDB trunk -- "f32" (default: the reference's
         fp32 training) or "bf16" (opt-in: bf16 activations and activation gradients between the trunk's kernels, fp32 master weights, gradients and Adam;
         growth_channels must be a multiple of 32, checked when the trainer is built: DESIGN.md 3.26); anything else raises ValueError here.  Inference,
-        validation and everything outside the trunk are not affected."""
-        from sr355.gan_train import check_attention_impl, check_train_dtype
+        validation and everything outside the trunk are not affected.
+        train_dense_block: how train_dtype="bf16" runs a dense block -- "layers" (default: conv by conv) or "lds" (opt-in: one forward and one backward kernel per
+        block on an LDS-resident image, the same arithmetic; for the notebook's graph: growth_channels = 8, checked when the trainer is built, and LR patches up to
+        24 x 24, checked by every step: DESIGN.md 3.28); "lds" without train_dtype="bf16", or anything else, raises ValueError here."""
+        from sr355.gan_train import check_attention_impl, check_dense_block_impl, check_train_dtype
         self.generator = None
         self.discriminator = None
         self.vgg_model = None
@@ -50,6 +53,7 @@ class ESRGAN(DeviceModelMixin):
         self.discriminator_update = discriminator_update
         self.train_attention = check_attention_impl(train_attention)
         self.train_dtype = check_train_dtype(train_dtype)
+        self.train_dense_block = check_dense_block_impl(train_dense_block, self.train_dtype)
 
     def _mark_trained(self, v):
         self.trained = v
@@ -132,15 +136,18 @@ class ESRGAN(DeviceModelMixin):
     def _ensure_trainer(self):
         """The optimisers live from setup_model on in the reference (ESRGAN_model.py:176-195): one trainer (weights, Adam moments,
         spectral-norm vectors, step counter) per model, kept across fit() calls."""
-        from sr355.gan_train import ESRGANTrainer, trunk_layers
+        from sr355.gan_train import ESRGANTrainer, trunk_layers, trunk_layers_lds
         if getattr(self, "_trainer", None) is None:
-            if self.train_dtype == "bf16":                  # a growth width the bf16 kernels cannot take is refused before the loss networks are built
+            if self.train_dense_block == "lds":             # a growth width the trunk's kernels cannot take is refused before the loss networks are built
+                trunk_layers_lds(self.weights, self.num_rrdb_blocks)
+            elif self.train_dtype == "bf16":
                 trunk_layers(self.weights, self.num_rrdb_blocks)
             self._ensure_loss_networks()
             self._trainer = ESRGANTrainer(self.ctx, self.weights, self.d_weights, self.vgg_weights, self.scale_factor,
                                           self.num_rrdb_blocks, attention=self.use_attention, g_lr=1e-4, d_lr=1e-5,
                                           allreduce=getattr(self, "grad_allreduce", None), allreduce_flat=getattr(self, "grad_allreduce_flat", None),
-                                          discriminator=self.discriminator_update, attention_impl=self.train_attention, train_dtype=self.train_dtype)
+                                          discriminator=self.discriminator_update, attention_impl=self.train_attention, train_dtype=self.train_dtype,
+                                          dense_block_impl=self.train_dense_block)
             self.g_optimizer, self.d_optimizer = self._trainer.g_opt, self._trainer.d_opt
         return self._trainer
 

@@ -110,6 +110,11 @@ SIGNATURES = {
     "sr_conv2d_dev_views_bf16": (_i, [_vp, _vw, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vw, _f, _vw, _f, _vw, _vp]),
     "sr_conv2d_wgrad_group_bf16": (_i, [_vp, C.POINTER(WgradJob), _i, _i, _i, _i, _vp]),
     "sr_eltwise_views_bf16": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
+    "sr_dense_block_train_max_pixels": (_i, []),
+    "sr_dense_block_pack_sizes": (None, [_i64p, _i64p, _i64p]),
+    "sr_dense_block_pack_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sr_dense_block_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vw, _vw, _f, _f, _f, _vp]),
+    "sr_dense_block_bwd_bf16": (_i, [_vp, _vp, _vw, _vp, _i64, _i, _i, _i, _f, _f, _vp, _vw, _vp, _vp]),
     "sr_conv2d_wgrad_views": (_i, [_vp, _vw, _vw, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_eltwise_views": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
     "sr_eltwise": (_i, [_vp, _i, _vp, _vp, _f, _f, _vp, _i64, _vp]),

@@ -24,6 +24,8 @@ The generator's parameters are device-resident in both modes; kernels are packed
 train_dtype="bf16" (opt-in; ESRGANTrainer, ESRGAN) runs the RRDB trunk of the taped training pass in bf16 mixed precision -- Tape.trunk_bf16, one tape op
 on bf16 concat buffers with fp32 master weights and gradients; everything outside the trunk, and the default, stay fp32 (DESIGN.md 3.26;
 tools/bench_esrgan_mixed.py measures it against the fp32 trainer).
+dense_block_impl="lds" (opt-in, with train_dtype="bf16", growth width 8, patches up to 24 x 24) runs every dense block of that trunk as one forward and one backward
+kernel whose concat tensor and its gradient live in a CU's LDS -- Tape.trunk_lds, the same arithmetic contract (tools/bench_dense_block_train.py).
 """
 import contextlib
 
@@ -57,6 +59,43 @@ def check_train_dtype(value):
     return value
 
 
+DENSE_BLOCK_IMPLS = ("layers", "lds")
+
+
+def check_dense_block_impl(value, train_dtype="bf16"):
+    """How the bf16 trunk runs a dense block: "layers" (the default: conv by conv on the virtual-concat buffer, Tape.trunk_bf16) or "lds" (one forward and one
+    backward kernel per block on an LDS-resident image, Tape.trunk_lds: growth width 8, patches up to 24 x 24).  "lds" is bf16 arithmetic: it needs train_dtype="bf16"."""
+    if value not in DENSE_BLOCK_IMPLS:
+        raise ValueError(f"dense_block_impl must be one of {DENSE_BLOCK_IMPLS}, got {value!r}")
+    if value == "lds" and train_dtype != "bf16":
+        raise ValueError(f"dense_block_impl='lds' runs the trunk in bf16 mixed precision: it needs train_dtype='bf16', got train_dtype={train_dtype!r}")
+    return value
+
+
+def trunk_layers_lds(weights, num_rrdb):
+    """The trunk's conv layers in forward order; ValueError naming the first layer that is not a 64-channel dense block of growth width 8's (the LDS-resident kernels)."""
+    names = []
+    for b in range(num_rrdb):
+        for d in (1, 2, 3):
+            n = f"rrdb_{b}_dense{d}"
+            for k in range(1, 6):
+                want = (3, 3, 64 + 8 * (k - 1), 8 if k < 5 else 64)
+                got = tuple(weights[f"{n}_conv{k}"][0].shape)
+                if got != want:
+                    what = f"{got[3]} growth channels" if k < 5 and got[:3] == want[:3] else f"a kernel of shape {got}"
+                    raise ValueError(f"dense_block_impl='lds': {n}_conv{k} has {what}; the LDS-resident dense-block kernels take 64-channel blocks of growth width 8 "
+                                     f"(kernel {want}); train this graph with dense_block_impl='layers'")
+            names += [f"{n}_conv{k}" for k in range(1, 6)]
+    return names
+
+
+def lds_patch_check(ctx, H, W):
+    """ValueError where an H x W patch does not fit the LDS-resident training kernels (there is no other path behind dense_block_impl='lds')."""
+    if not ctx.dense_block_train_fits(H, W):
+        raise ValueError(f"dense_block_impl='lds': a patch of H = {H}, W = {W} does not fit the LDS-resident dense-block kernels, which take (H + 2)(W + 2) <= "
+                         f"{ctx.dense_block_train_max_pixels()} (24 x 24); train larger patches with dense_block_impl='layers'")
+
+
 def trunk_layers(weights, num_rrdb):
     """The trunk's conv layers in forward order; ValueError where a dense block's growth width is not a whole number of the bf16 conv kernels' 32-channel chunks."""
     names = []
@@ -86,10 +125,13 @@ class Tape:
     """Reverse-mode bookkeeping: ops push a closure; backward() runs them last-to-first.  Parameter gradients land in `grads`
     ({layer: [dk, db]}, summed over uses) when `wgrad` is on."""
 
-    def __init__(self, ctx, weights, wgrad=True, devcache=None, attention_impl="materialised", trunk_dtype="f32", flat_grads=None):
+    def __init__(self, ctx, weights, wgrad=True, devcache=None, attention_impl="materialised", trunk_dtype="f32", flat_grads=None, dense_block_impl="layers"):
         self.ctx, self.w, self.wgrad = ctx, weights, wgrad
         self.attention_impl = check_attention_impl(attention_impl)
         self.trunk_dtype = check_train_dtype(trunk_dtype)      # "bf16": generator_forward runs the RRDB trunk as ONE op on bf16 buffers (trunk_bf16)
+        self.dense_block_impl = check_dense_block_impl(dense_block_impl, trunk_dtype)      # "lds": ... by trunk_lds instead
+        self.lds_packs = None                                   # (fwd, bias, bwd, {block name: row}) of sr_dense_block_pack_dev: a trainer's, packed once per step; None: trunk_lds packs
+        self.trunk_stages = False                               # tests: with trunk_tape, trunk_lds also records the G_b_d_s* stages (the backward kernel's stage dump)
         # A FlatGrads of the parameter bucket: the trunk's weight-gradient kernels write straight into its views, the fp32 layers' gradients are copied into
         # theirs, and `grads` holds the views of the layers written so far; ParamBucket.gather then hands the flat tensor on as it is.
         self.flat = flat_grads
@@ -323,6 +365,99 @@ class Tape:
         self.ops.append(bwd)
         return y
 
+    def pack_lds(self, num_rrdb):
+        """(fwd, bias, bwd, {block name: row}): the trunk's dense blocks packed for the LDS-resident kernels from the tape's device weights, by one launch."""
+        ctx = self.ctx
+        trunk_layers_lds(self.w, num_rrdb)
+        names = [f"rrdb_{b}_dense{d}" for b in range(num_rrdb) for d in (1, 2, 3)]
+        ws = [[self.w[f"{n}_conv{k}"] for k in range(1, 6)] for n in names]
+        table = ctx.dense_block_pack_table([([self._dev(k) for k, _ in w], [self._dev(b) for _, b in w]) for w in ws])
+        fwd, bias, bwd = ctx.dense_block_pack_buffers(len(names))
+        ctx.dense_block_pack_dev(table, fwd, bias, bwd)
+        return fwd, bias, bwd, {n: i for i, n in enumerate(names)}
+
+    def trunk_lds(self, x, num_rrdb, tape=None):
+        """trunk_bf16 at growth width 8 with every dense block as ONE forward and ONE backward kernel on an LDS-resident image: the same contract,
+        the same stored tensors (F per block, dz, dX) and the same grouped weight-gradient launch; G, the gradient of F, never reaches HBM.  `tape` as in
+        trunk_bf16; the G_b_d_s* stages are recorded only with `trunk_stages` (the kernel's stage dump; channels >= cin_k of stage k hold dz already selected)."""
+        ctx = self.ctx
+        if self.flat is None and self.wgrad:
+            raise ValueError("trunk_lds: the weight gradients need a FlatGrads to write into")
+        BF = torch.bfloat16
+        B, H, W, C0 = x.v.shape
+        lds_patch_check(ctx, H, W)
+        fwd, bias, bwd, row = self.lds_packs if self.lds_packs is not None else self.pack_lds(num_rrdb)
+        tape = self.trunk_tape if tape is None else tape
+        rec = tape.append if tape is not None else None
+        g, Ct = 8, C0 + 32
+        blocks = []                                             # (b, d, name, F, a5, bx)
+        F = ctx.empty((B, H, W, Ct), BF)
+        F[..., :C0].copy_(x.v)                                  # the one rounding of x0, into slice 0 of the first F
+        if rec:
+            rec(("x0_f32", x.v))
+        out = None
+        for b in range(num_rrdb):
+            r_in = F
+            for d in (1, 2, 3):
+                name = f"rrdb_{b}_dense{d}"
+                i = row[name]
+                last = b == num_rrdb - 1 and d == 3
+                nxt = ctx.empty((B, H, W, C0 if last else Ct), BF)
+                if d < 3:
+                    a5, bx = 0.2, 1.0
+                    ctx.dense_block_fwd_bf16(fwd[i], bias[i], F, nxt, alpha=a5, beta1=bx)
+                else:                                           # r_in + 0.2 * (x + 0.2 * conv5) in one epilogue, one rounding
+                    a5, bx = 0.04, 0.2
+                    ctx.dense_block_fwd_bf16(fwd[i], bias[i], F, nxt, skip2=(r_in, 0), alpha=a5, beta1=bx, beta2=1.0)
+                if self.masks is not None:
+                    for k in range(1, 5):
+                        self.masks[f"{name}_conv{k}"] = F[..., C0 + (k - 1) * g:C0 + k * g] > 0
+                if rec:
+                    rec((f"F_{b}_{d}", F))
+                blocks.append((b, d, name, F, a5, bx))
+                F = nxt
+        out = F
+        if rec:
+            rec(("out", out))
+        y = Var(out.float())
+
+        def bwd_op():
+            if y.g is None:
+                return
+            dR = y.g.to(BF)                                     # the one rounding of the gradient entering the trunk
+            if rec:
+                rec(("dout_f32", y.g))
+                rec((f"dR_{num_rrdb - 1}", dR))
+            dY = dR
+            for b, d, name, F, a5, bx in reversed(blocks):
+                dz = ctx.empty((B, H, W, 4 * g), BF)            # dz_k is slice k - 1
+                dX = ctx.empty((B, H, W, C0), BF)
+                stages = ctx.empty((4, B, H, W, Ct), BF) if rec and self.trunk_stages else None
+                ctx.dense_block_bwd_bf16(bwd[row[name]], dY, F, a5, bx, dz, dX, stages=stages)
+                if stages is not None:
+                    for j, k in enumerate((5, 4, 3, 2)):
+                        rec((f"G_{b}_{d}_s{k}", stages[j]))
+                if self.wgrad:
+                    jobs = [(F, 0, C0 + (k - 1) * g, dz, (k - 1) * g, g, 1.0) + tuple(self.flat[f"{name}_conv{k}"]) for k in range(1, 5)]
+                    jobs.append((F, 0, Ct, dY, 0, C0, a5) + tuple(self.flat[f"{name}_conv5"]))
+                    ctx.conv2d_wgrad_group_bf16(jobs)
+                    for k in range(1, 6):
+                        self.grads[f"{name}_conv{k}"] = list(self.flat[f"{name}_conv{k}"])
+                if rec:
+                    rec((f"dz_{b}_{d}", dz))
+                    rec((f"dX_{b}_{d}", dX))
+                dY = dX
+                if d == 1:
+                    d_rin = ctx.empty((B, H, W, C0), BF)
+                    ctx.eltwise_view_bf16(L.ELT_AXPBY, dX, 0, dR, 0, d_rin, 0, C0, 1.0, 1.0)
+                    if rec:
+                        rec((f"drin_{b}", d_rin))
+                    dR = dY = d_rin
+            if x.need:
+                self._acc(x, dR.float())
+        self.ops.append(bwd_op)
+        return y
+
     def axpby(self, a, b, alpha, beta):
         y = Var(self.ctx.eltwise(L.ELT_AXPBY, a.v, b.v, alpha, beta))
 
@@ -405,7 +540,7 @@ def generator_forward(t, x, scale, num_rrdb, attention=True):
     x = t.conv(x, "initial_conv")
     trunk = x
     if t.trunk_dtype == "bf16":
-        x, num_rrdb = t.trunk_bf16(x, num_rrdb), 0
+        x, num_rrdb = (t.trunk_lds if t.dense_block_impl == "lds" else t.trunk_bf16)(x, num_rrdb), 0
     for b in range(num_rrdb):
         r_in = x
         for d in (1, 2, 3):
@@ -682,12 +817,16 @@ class ESRGANTrainer:
     dw, u, d_opt, d_params = (_discriminator_attr(name) for name in ("weights", "u", "opt", "params"))
 
     def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None, discriminator="host", attention_impl="materialised", train_dtype="f32"):
+                 allreduce_flat=None, discriminator="host", attention_impl="materialised", train_dtype="f32", dense_block_impl="layers"):
         if discriminator not in ("host", "device"):
             raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
-        # what the taped training pass stores inside the RRDB trunk (Tape.trunk_bf16); refused before anything is uploaded or launched
+        # what the taped training pass stores inside the RRDB trunk (Tape.trunk_bf16 / trunk_lds); refused before anything is uploaded or launched
         self.train_dtype = check_train_dtype(train_dtype)
-        self._trunk = set(trunk_layers(g_weights, num_rrdb)) if train_dtype == "bf16" else set()
+        self.dense_block_impl = check_dense_block_impl(dense_block_impl, train_dtype)
+        if self.dense_block_impl == "lds":
+            self._trunk = set(trunk_layers_lds(g_weights, num_rrdb))
+        else:
+            self._trunk = set(trunk_layers(g_weights, num_rrdb)) if train_dtype == "bf16" else set()
         self.attention_impl = check_attention_impl(attention_impl)      # the generator tape's SelfAttention core (Tape.attention)
         self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
         self.discriminator = discriminator
@@ -717,6 +856,7 @@ class ESRGANTrainer:
         self.last_masks = self.last_dy = self.last_fake = None
         self._last = None
         self._packs = {}
+        self._lds_packed = False
 
     @contextlib.contextmanager
     def _prepacked(self, with_vgg):
@@ -732,17 +872,26 @@ class ESRGANTrainer:
                     if kd.dim() == 4 and kd.shape[0] == kd.shape[1] and kd.shape[0] in (1, 3):
                         uses += [(kd, bd, False), (kd, None, True)]
             self._packs[with_vgg] = self.ctx.pack_list(uses)
-        if self._trunk and "bf16" not in self._packs:         # every trunk kernel rounded to bf16 once per step, for its forward and its input-gradient use
+        lds = self.dense_block_impl == "lds"
+        if self._trunk and not lds and "bf16" not in self._packs:      # every trunk kernel rounded to bf16 once per step, for its forward and its input-gradient use
             dev = self.g_params.dev
             self._packs["bf16"] = self.ctx.pack_list([u for n in dev if n in self._trunk for u in ((dev[n][0], dev[n][1], False), (dev[n][0], None, True))])
+        if lds and "lds" not in self._packs:                  # dense_block_impl="lds": the trunk's blocks as fragments of the LDS-resident kernels, in buffers of the trainer's
+            dev, names = self.g_params.dev, [f"rrdb_{b}_dense{d}" for b in range(self.nb) for d in (1, 2, 3)]
+            table = self.ctx.dense_block_pack_table([([dev[f"{n}_conv{k}"][0] for k in range(1, 6)], [dev[f"{n}_conv{k}"][1] for k in range(1, 6)]) for n in names])
+            self._packs["lds"] = (table,) + self.ctx.dense_block_pack_buffers(len(names)) + ({n: i for i, n in enumerate(names)},)
         self.ctx.conv_prepack(self._packs[with_vgg])
-        if self._trunk:
+        if lds:
+            self.ctx.dense_block_pack_dev(*self._packs["lds"][:4])     # ... rounded to bf16 once per step, by one launch
+            self._lds_packed = True
+        elif self._trunk:
             self.ctx.conv_prepack_bf16(self._packs["bf16"])
         try:
             yield
         finally:
             self.ctx.conv_prepack(None)
-            if self._trunk:
+            self._lds_packed = False                          # the weights move on in the step's last lines: a tape made outside the block packs for itself
+            if self._trunk and not lds:
                 self.ctx.conv_prepack_bf16(None)
 
     @property
@@ -767,8 +916,18 @@ class ESRGANTrainer:
         """A tape over the generator's device-resident parameters (no upload, no host copy).  With train_dtype="bf16" the taped training pass (wgrad) runs the
         trunk in bf16 and collects every gradient in one flat bucket; the forward-only tape stays fp32."""
         bf16 = wgrad and self.train_dtype == "bf16"
-        return Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache), attention_impl=self.attention_impl,
-                    trunk_dtype="bf16" if bf16 else "f32", flat_grads=FlatGrads(self.g_params) if bf16 else None)
+        lds = bf16 and self.dense_block_impl == "lds"
+        t = Tape(self.ctx, self.g_params.arrays, wgrad=wgrad, devcache=dict(self.g_params.devcache), attention_impl=self.attention_impl,
+                 trunk_dtype="bf16" if bf16 else "f32", flat_grads=FlatGrads(self.g_params) if bf16 else None, dense_block_impl="lds" if lds else "layers")
+        if lds and self._lds_packed:                           # inside _prepacked: this step's pack
+            t.lds_packs = self._packs["lds"][1:]
+        return t
+
+    def _check_patch(self, lr_images):
+        """dense_block_impl="lds": a batch whose patch the LDS-resident kernels cannot take is refused before the step touches anything."""
+        if self.dense_block_impl == "lds":
+            shape = lr_images.shape if hasattr(lr_images, "shape") else np.shape(lr_images)
+            lds_patch_check(self.ctx, int(shape[1]), int(shape[2]))
 
     @property
     def last_grads(self):
@@ -798,9 +957,10 @@ class ESRGANTrainer:
         """One generator update on the pixel loss alone (mean |hr - G(lr)|, ESRGAN_model.py:433-445; the generator half of _train_step,
         :506-531, without the adversarial / perceptual / spectral terms): sr355.recipes' fit.  -> the L1 value before the update."""
         ctx = self.ctx
+        self._check_patch(lr_images)
         lr_t, hr_t = _device_batch(ctx, lr_images), _device_batch(ctx, hr_images)
-        tg = self.generator_tape()
         with self._prepacked(False):
+            tg = self.generator_tape()
             y = generator_forward(tg, Var(lr_t, need=False), self.scale, self.nb, self.att)
             pix = float(ctx.l1(hr_t, y.v).item())
             y.g = ctx.eltwise(L.ELT_SIGN_DIFF, y.v, hr_t, 1.0 / y.v.numel(), 0.0)
@@ -813,6 +973,7 @@ class ESRGANTrainer:
         discriminator the step issues two uploads (the image batches) and one read (the six loss scalars)."""
         if self.disc is None or self.vw is None:
             raise RuntimeError("ESRGANTrainer was built without discriminator / VGG19 weights: only pixel_step is available")
+        self._check_patch(lr_images)
         if self._vgg_src is not self.vw:                  # the first step, or ESRGAN.set_loss_network_weights has replaced the VGG19 weights
             self._vgg, self._vgg_src = ParamBucket(self.ctx, self.vw), self.vw
             self._packs.pop(True, None)

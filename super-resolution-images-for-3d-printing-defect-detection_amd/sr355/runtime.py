@@ -952,6 +952,86 @@ class Context:
         self.check(self.lib.sr_eltwise_views_bf16(self.h, int(op), C.byref(av), None if bv is None else C.byref(bv), float(alpha), float(beta), C.byref(ov), B * H * W, int(c),
                                                   self.stream()))
 
+    # ---- a G = 8 dense block trained on the LDS-resident image (csrc/dense_block_train.hip; sr355/gan_train.py, Tape.trunk_lds)
+    @staticmethod
+    def dense_block_train_max_pixels():
+        """The largest (H + 2)(W + 2) dense_block_bwd_bf16 takes (sr_dense_block_train_max_pixels)."""
+        return int(L.load().sr_dense_block_train_max_pixels())
+
+    @classmethod
+    def dense_block_train_fits(cls, H, W):
+        """Whether the LDS-resident training kernels take an H x W image: the forward's LDS bound and the backward's pixel bound."""
+        return cls.dense_block_lds_bytes(8, H, W) != -1 and (int(H) + 2) * (int(W) + 2) <= cls.dense_block_train_max_pixels()
+
+    @staticmethod
+    def dense_block_pack_sizes():
+        """(bytes of the forward fragments, floats of the bias table, bytes of the input-gradient fragments) of one packed block (sr_dense_block_pack_sizes)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        L.load().sr_dense_block_pack_sizes(C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def dense_block_pack_table(self, blocks):
+        """blocks: per dense block ([five fp32 HWIO device kernels], [five fp32 device biases]) -> the device pointer table sr_dense_block_pack_dev reads.  The
+        caller keeps the tensors alive and in place for as long as it uses the table."""
+        rows = []
+        for ks, bs in blocks:
+            if len(ks) != 5 or len(bs) != 5:
+                raise ValueError("dense_block_pack_table: five kernels and five biases per block")
+            for i, (k, b) in enumerate(zip(ks, bs)):
+                _check_tensor(self, k, "dense_block_pack_table kernel")
+                _check_tensor(self, b, "dense_block_pack_table bias")
+                want = (3, 3, 64 + 8 * i, 8) if i < 4 else (3, 3, 96, 64)
+                if tuple(k.shape) != want or tuple(b.shape) != (want[3],):
+                    raise ValueError(f"dense_block_pack_table: conv{i + 1} must be {want} with a bias of {want[3]}, got {tuple(k.shape)} and {tuple(b.shape)}")
+            rows.append([k.data_ptr() for k in ks] + [b.data_ptr() for b in bs])
+        return self.to_device(np.asarray(rows, np.int64))
+
+    def dense_block_pack_buffers(self, nblocks):
+        """Uninitialised (fwd uint8 [n, bytes], bias fp32 [n, floats], bwd uint8 [n, bytes]) for dense_block_pack_dev."""
+        fb, nb, bb = self.dense_block_pack_sizes()
+        return self.empty((nblocks, fb), torch.uint8), self.empty((nblocks, nb), torch.float32), self.empty((nblocks, bb), torch.uint8)
+
+    def dense_block_pack_dev(self, table, fwd, bias, bwd):
+        """sr_dense_block_pack_dev: one launch packs the current weights of every block of `table` (dense_block_pack_table) into fwd / bias / bwd
+        (dense_block_pack_buffers)."""
+        n = int(table.shape[0])
+        fb, nb, bb = self.dense_block_pack_sizes()
+        if table.dtype != torch.int64 or tuple(table.shape) != (n, 10) or not table.is_cuda or not table.is_contiguous():
+            raise ValueError("dense_block_pack_dev: the table is an int64 device tensor [n, 10]")
+        for t, shape, dt in ((fwd, (n, fb), torch.uint8), (bias, (n, nb), torch.float32), (bwd, (n, bb), torch.uint8)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == shape):
+                raise ValueError(f"dense_block_pack_dev: a pack buffer must be a contiguous device tensor {shape} of {dt}")
+        self.check(self.lib.sr_dense_block_pack_dev(self.h, table.data_ptr(), n, fwd.data_ptr(), bias.data_ptr(), bwd.data_ptr(), self.stream()))
+
+    def dense_block_fwd_bf16(self, fwd_w, bias, F, out, out_coff=0, skip2=None, alpha=0.2, beta1=1.0, beta2=0.0):
+        """sr_dense_block_fwd_bf16: a whole G = 8 dense block on the bf16 NHWC concat buffer F [B,H,W,>=96] as ONE kernel: reads F[..., :64], writes the four growth
+        slices into F[..., 64:96] and out[..., out_coff : out_coff + 64] = bf16(alpha * (conv5 + b5) + beta1 * F[..., :64] + beta2 * skip2); skip2: (buffer, first
+        channel) or None.  fwd_w / bias: one block's rows of dense_block_pack_dev's buffers."""
+        B, H, W, _ = F.shape
+        self._view_bf16(F, 0, 96)
+        ov = self._view_bf16(out, out_coff, 64)
+        sv = None if skip2 is None else self._view_bf16(skip2[0], skip2[1], 64)
+        for t in (out,) + (() if skip2 is None else (skip2[0],)):
+            if tuple(t.shape[:3]) != (B, H, W):
+                raise ValueError("dense_block_fwd_bf16: every buffer must share [B,H,W]")
+        self.check(self.lib.sr_dense_block_fwd_bf16(self.h, fwd_w.data_ptr(), bias.data_ptr(), F.data_ptr(), int(F.shape[3]), B, H, W, C.byref(ov),
+                                                    None if sv is None else C.byref(sv), float(alpha), float(beta1), float(beta2), self.stream()))
+
+    def dense_block_bwd_bf16(self, bwd_w, dY, F, a5, bx, dz, dX, dy_coff=0, dx_coff=0, stages=None):
+        """sr_dense_block_bwd_bf16: the whole backward of that block's activations as ONE kernel, from dY[..., dy_coff : dy_coff + 64] and the stored F: writes
+        dz [B,H,W,32] (dz_k in slice k - 1) and dX[..., dx_coff : dx_coff + 64]; stages: None or a bf16 [4,B,H,W,96] receiving G after conv5's input gradient and
+        after each in-place accumulate.  bwd_w: one block's row of dense_block_pack_dev's bwd buffer."""
+        B, H, W, _ = F.shape
+        self._view_bf16(F, 0, 96)
+        yv, xv = self._view_bf16(dY, dy_coff, 64), self._view_bf16(dX, dx_coff, 64)
+        self._view_bf16(dz, 0, 32)
+        if tuple(dz.shape) != (B, H, W, 32) or tuple(dY.shape[:3]) != (B, H, W) or tuple(dX.shape[:3]) != (B, H, W):
+            raise ValueError("dense_block_bwd_bf16: dY and dX share F's [B,H,W], dz is [B,H,W,32]")
+        if stages is not None and not (stages.dtype == torch.bfloat16 and stages.is_cuda and stages.is_contiguous() and tuple(stages.shape) == (4, B, H, W, 96)):
+            raise ValueError("dense_block_bwd_bf16: stages is a contiguous bf16 device tensor [4,B,H,W,96]")
+        self.check(self.lib.sr_dense_block_bwd_bf16(self.h, bwd_w.data_ptr(), C.byref(yv), F.data_ptr(), int(F.shape[3]), B, H, W, float(a5), float(bx), dz.data_ptr(),
+                                                    C.byref(xv), None if stages is None else stages.data_ptr(), self.stream()))
+
     def relu_bwd_bf16(self, dy, y):
         """dy where y > 0, else 0, on bf16 tensors of one shape (sr_relu_bwd_bf16)."""
         _check_tensor(self, dy, "relu_bwd_bf16 dy", self._BF16)
