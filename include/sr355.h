@@ -310,6 +310,42 @@ int  sr_dense_block_fwd_bf16(sr_ctx* ctx, const void* fwd_w, const float* bias, 
                              float beta1, float beta2, void* stream);
 int  sr_dense_block_bwd_bf16(sr_ctx* ctx, const void* bwd_w, const sr_view* dY, const void* F, int64_t f_cs, int B, int H, int W, float a5, float bx, void* dz, const sr_view* dX,
                              void* stages, void* stream);
+/* ---- 3x3 convs over many small images with hundreds of channels (the frozen VGG19 of ESRGAN's perceptual loss on training patches, whose blocks 4-5 see 6 x 6 and
+ * 3 x 3 images of 512 channels; the trainer sends a call here only where this kernel measured fastest -- images up to 3 x 3, or up to 6 x 6 with at most 1008 pixels
+ * in the call; 12 x 12 images stay on sr_conv2d_dev_bf16 -- ESRGAN_model.py:379-408, 514-524) ----
+ * sr_conv3x3_small_bf16 (ESRGAN_model.py:379-408 the extractor's convs, :514-524 their input gradients under the tape): Conv2D(3 x 3, SAME, stride 1) on bf16 x [B,H,W,Cin]
+ *   -> bf16 y [B,H,W,Cout] with H * W <= 144, Cin and Cout multiples of 32, any B >= 1; anything else is SR_ERR_INVALID.  The contract is sr_conv2d_dev_bf16's: d_w is the
+ *   fp32 device kernel (HWIO [3,3,Cin,Cout], or with rot = 1 the forward kernel [3,3,Cout,Cin] of the layer whose input gradient is wanted), rounded to bf16 once by a device
+ *   pack; fp32 accumulation on MFMA; fp32 bias (NULL: none); y = bf16(act(conv + b)), act SR_ACT_LINEAR or SR_ACT_RELU, the whole epilogue in fp32 and one rounding to nearest
+ *   even.  mask (NULL: none) is a bf16 tensor of y's shape: where mask <= 0 (sr_relu_bwd_bf16's predicate, on the bits) the stored value is +0 -- the ReLU gradient of
+ *   the layer in front, as a select on the rounded result.  The GEMM's pixel axis runs over all images together and K is split over the four waves of a workgroup in a way
+ *   that depends on Cin alone: an image's bits depend neither on B nor on its place in the batch; a tap outside its own image is a zero operand that is never loaded.
+ *   packed: NULL, or a kernel packed by sr_conv3x3_small_pack_bf16 for the same (Cin, Cout); then d_w and rot are not looked at.
+ * sr_conv3x3_small_pack_bytes / sr_conv3x3_small_pack_bf16 (ESRGAN_model.py:379-400, the extractor's weights are frozen): the packed-kernel handle for weights that outlive a
+ *   step.  The caller owns the buffer (pack_bytes bytes, 16-byte aligned; 0 for channel counts the kernel refuses); it is no part of sr_conv_prepack_bf16's per-step list
+ *   and never answers for it.  The caller packs again after changing the weights.
+ * The other kernels of the bf16 perceptual branch (bf16 values travel as their bits: a select never rounds):
+ * sr_vgg_preprocess_bf16 (ESRGAN_model.py:401-408, keras vgg19.preprocess_input of both feature passes of :514-516): fake and hr fp32 [B,H,W,3] RGB in [-1,1] -> out bf16
+ *   [2B,H,W,6], fake first.  Per pixel v = (x + 1) * 127.5 in BGR order minus the caffe means, as SR_SP_VGG_PREPROCESS computes it in fp32; channels 0-2 hold
+ *   hi = bf16(v), channels 3-5 lo = bf16(v - hi): with block1_conv1's kernel stacked twice along Cin the entry carries 16 bits of v at no MFMA cost (Cin pads to 8 anyway).
+ * sr_vgg_preprocess_bwd (ESRGAN_model.py:514-524, the tape through preprocess_input): dv bf16 [npix,3], the gradient of v -> dfake fp32 [npix,3] = 127.5 * dv with the
+ *   channels flipped back.
+ * sr_maxpool2_bf16 / sr_maxpool2_bwd_bf16 (ESRGAN_model.py:379-400, VGG19's MaxPooling2D(2,2) and its gradient under the tape): x bf16 [B,H,W,C] -> y [B,H/2,W/2,C], VALID
+ *   (an odd last row / column is dropped); the winner of a window is the first of (0,0), (0,1), (1,0), (1,1) that equals the maximum -- sr_maxpool2_bwd's order and tie
+ *   rule.  The backward takes the pre-pool activation x and dy [B,H/2,W/2,C]: dx = dy at the window's winner where x > 0 (the ReLU of the conv in front of the pool,
+ *   sr_relu_bwd_bf16's predicate), else +0.  C a multiple of 8, H, W >= 2.
+ * sr_mse_grad_bf16 (ESRGAN_model.py:514-516, mean_squared_error of the two feature maps and its gradient): feats bf16 = [ff | fr], n elements each -> perc1 fp32 [1] =
+ *   mean((ff - fr)^2), summed in fp64 in a fixed order; dff bf16 [n] = bf16(fp32(2 / n) * (ff - fr)), both operations rounded on their own, where ff > 0 (block5_conv4's
+ *   own ReLU), else +0. */
+int64_t sr_conv3x3_small_pack_bytes(int Cin, int Cout);
+int  sr_conv3x3_small_pack_bf16(sr_ctx* ctx, const float* d_w, int Cin, int Cout, int rot, void* packed, void* stream);
+int  sr_conv3x3_small_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int Cin, const float* d_w, const void* packed, const float* d_bias, int Cout, int rot, int act,
+                           const void* mask, void* y, void* stream);
+int  sr_vgg_preprocess_bf16(sr_ctx* ctx, const float* fake, const float* hr, int B, int H, int W, void* out, void* stream);
+int  sr_vgg_preprocess_bwd(sr_ctx* ctx, const void* dv, int64_t npix, float* dfake, void* stream);
+int  sr_maxpool2_bf16(sr_ctx* ctx, const void* x, int B, int H, int W, int C, void* y, void* stream);
+int  sr_maxpool2_bwd_bf16(sr_ctx* ctx, const void* x, const void* dy, int B, int H, int W, int C, void* dx, void* stream);
+int  sr_mse_grad_bf16(sr_ctx* ctx, const void* feats, int64_t n, float* perc1, void* dff, void* stream);
 int  sr_eltwise(sr_ctx* ctx, int op, const void* a, const void* b, float alpha, float beta, void* out, int64_t n, void* stream);
 /* keras.optimizers.Adam's dense update (the optimiser of ESRGAN_model.py:176-195, SRCNN_model.py:55-60, EDSR_model.py:127-140) over one flat
  * fp32 bucket of n parameters, in place on the device: g is first multiplied by grad_scale (1 / world size after a summing all-reduce; 1 leaves

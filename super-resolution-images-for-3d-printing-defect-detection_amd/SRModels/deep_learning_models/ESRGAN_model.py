@@ -26,7 +26,8 @@ class _Normalised:
 
 
 class ESRGAN(DeviceModelMixin):
-    def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised", train_dtype="f32", train_dense_block="layers"):
+    def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised", train_dtype="f32", train_dense_block="layers",
+                 perceptual_dtype="f32"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
         >= 100 dB against the fp64 oracle) or "bf16" (opt-in: bf16 storage, fp32 accumulation -- BASELINE configs[2]'s dtype and what
         bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md).
@@ -41,8 +42,11 @@ class ESRGAN(DeviceModelMixin):
         validation and everything outside the trunk are not affected.
         train_dense_block: how train_dtype="bf16" runs a dense block -- "layers" (default: conv by conv) or "lds" (opt-in: one forward and one backward kernel per
         block on an LDS-resident image, the same arithmetic; for the notebook's graph: growth_channels = 8, checked when the trainer is built, and LR patches up to
-        24 x 24, checked by every step: DESIGN.md 3.28); "lds" without train_dtype="bf16", or anything else, raises ValueError here."""
-        from sr355.gan_train import check_attention_impl, check_dense_block_impl, check_train_dtype
+        24 x 24, checked by every step: DESIGN.md 3.28); "lds" without train_dtype="bf16", or anything else, raises ValueError here.
+        perceptual_dtype: the arithmetic of _train_step's VGG19 perceptual term and of its gradient -- "f32" (default: the reference's) or "bf16" (opt-in: one bf16
+        forward over [fake | hr] and one backward over fake, fp32 master weights packed once, the small-image conv kernel on the 3 x 3 and small 6 x 6 calls of blocks 4-5 where it measured fastest: DESIGN.md 3.29); anything
+        else raises ValueError here.  Independent of the options above; evaluate and fit's validation pass stay fp32."""
+        from sr355.gan_train import check_attention_impl, check_dense_block_impl, check_perceptual_dtype, check_train_dtype
         self.generator = None
         self.discriminator = None
         self.vgg_model = None
@@ -54,6 +58,7 @@ class ESRGAN(DeviceModelMixin):
         self.train_attention = check_attention_impl(train_attention)
         self.train_dtype = check_train_dtype(train_dtype)
         self.train_dense_block = check_dense_block_impl(train_dense_block, self.train_dtype)
+        self.perceptual_dtype = check_perceptual_dtype(perceptual_dtype)
 
     def _mark_trained(self, v):
         self.trained = v
@@ -147,7 +152,7 @@ class ESRGAN(DeviceModelMixin):
                                           self.num_rrdb_blocks, attention=self.use_attention, g_lr=1e-4, d_lr=1e-5,
                                           allreduce=getattr(self, "grad_allreduce", None), allreduce_flat=getattr(self, "grad_allreduce_flat", None),
                                           discriminator=self.discriminator_update, attention_impl=self.train_attention, train_dtype=self.train_dtype,
-                                          dense_block_impl=self.train_dense_block)
+                                          dense_block_impl=self.train_dense_block, perceptual_dtype=self.perceptual_dtype)
             self.g_optimizer, self.d_optimizer = self._trainer.g_opt, self._trainer.d_opt
         return self._trainer
 

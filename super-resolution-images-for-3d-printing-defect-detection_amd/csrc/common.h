@@ -53,6 +53,7 @@ struct sr_ctx {
     struct Arena { void* p = nullptr; size_t cap = 0; };
     Arena attn_kn;                // attention: per-key-group largest key norm (stream-ordered reuse)
     Arena attn_d;                 // attention_train.hip: D_i = <dO_i, o_i> of the backward pass in flight (stream-ordered reuse)
+    Arena small_w;                // conv_small.hip: the packed kernel of a sr_conv3x3_small_bf16 call that brought no handle (stream-ordered reuse)
     Arena dev_w, dev_b, dev_x;    // sr_conv2d_dev: packed weights / padded bias / padded input of the call in flight (stream-ordered reuse)
     Arena cls_tab, cls_work, cls_fft;   // classic.hip: tap tables, per-call work buffers, the DFT products' operands (stream-ordered reuse)
     std::unordered_map<int64_t, double*> dft_ops;   // classic.hip: (N << 32 | n) -> A_{N,n} of frequency extrapolation, built once per shape;

@@ -115,6 +115,14 @@ SIGNATURES = {
     "sr_dense_block_pack_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "sr_dense_block_fwd_bf16": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _vw, _vw, _f, _f, _f, _vp]),
     "sr_dense_block_bwd_bf16": (_i, [_vp, _vp, _vw, _vp, _i64, _i, _i, _i, _f, _f, _vp, _vw, _vp, _vp]),
+    "sr_conv3x3_small_pack_bytes": (_i64, [_i, _i]),
+    "sr_conv3x3_small_pack_bf16": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sr_conv3x3_small_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_vgg_preprocess_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sr_vgg_preprocess_bwd": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "sr_maxpool2_bf16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_maxpool2_bwd_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_mse_grad_bf16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sr_conv2d_wgrad_views": (_i, [_vp, _vw, _vw, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_eltwise_views": (_i, [_vp, _i, _vw, _vw, _f, _f, _vw, _i64, _i, _vp]),
     "sr_eltwise": (_i, [_vp, _i, _vp, _vp, _f, _f, _vp, _i64, _vp]),

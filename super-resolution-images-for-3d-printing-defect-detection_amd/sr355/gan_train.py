@@ -26,6 +26,8 @@ on bf16 concat buffers with fp32 master weights and gradients; everything outsid
 tools/bench_esrgan_mixed.py measures it against the fp32 trainer).
 dense_block_impl="lds" (opt-in, with train_dtype="bf16", growth width 8, patches up to 24 x 24) runs every dense block of that trunk as one forward and one backward
 kernel whose concat tensor and its gradient live in a CU's LDS -- Tape.trunk_lds, the same arithmetic contract (tools/bench_dense_block_train.py).
+perceptual_dtype="bf16" (opt-in; independent of the options above) runs train_step's VGG19 perceptual term and its gradient in bf16 mixed precision -- PerceptualBf16:
+one forward over [fake | hr], one backward over fake, frozen weights packed once (tools/bench_perceptual_mixed.py).
 """
 import contextlib
 
@@ -616,6 +618,123 @@ def vgg19_features(t, x):
     return h
 
 
+PERCEPTUAL_DTYPES = ("f32", "bf16")
+
+
+def check_perceptual_dtype(value):
+    """The arithmetic of _train_step's VGG19 perceptual term: "f32" (the reference's) or "bf16" (PerceptualBf16)."""
+    if value not in PERCEPTUAL_DTYPES:
+        raise ValueError(f"perceptual_dtype must be one of {PERCEPTUAL_DTYPES}, got {value!r}")
+    return value
+
+
+SMALL_CONV_WINS_TINY, SMALL_CONV_WINS_PIXELS, SMALL_CONV_WINS_TOTAL = 9, 36, 1008
+
+
+def small_conv_wins(h, w, cin, cout, images):
+    """Where sr_conv3x3_small_bf16 is the fastest of the three conv routes per launch (tools/bench_perceptual_mixed.py, profiles/perceptual_mixed_aba.txt,
+    DESIGN.md 3.29), channel counts multiples of 32: images of at most 3 x 3 pixels at any batch (measured from 144 to 2304 pixels per call: 0.29-0.60 of the
+    best other route), and images of at most 6 x 6 pixels while the call has at most 1008 pixels (measured on 6 x 6 at 288 .. 1008: 0.68-0.78; at 1152 and 2304,
+    where the grid no longer fits the CUs in one round, 1.05-1.11).  Image sizes between 3 x 3 and 6 x 6 were not measured: they take the 6 x 6 rule.  The
+    kernel itself takes images up to 144 pixels and any batch; on 12 x 12 images sr_conv2d_dev_bf16 measured 1.35-2.96 x faster and keeps those calls."""
+    if cin % 32 or cout % 32:
+        return False
+    return h * w <= SMALL_CONV_WINS_TINY or (h * w <= SMALL_CONV_WINS_PIXELS and images * h * w <= SMALL_CONV_WINS_TOTAL)
+
+
+def perceptual_routes(H, W, B=None):
+    """The sixteen convs of the extractor on a batch of B HR patches of H x W -> [(layer, h, w, cin, cout, forward route, pooled, input-gradient route)]: the
+    layer's image size and channels, the kernel of its forward over the 2 B images [fake | hr] and of its input gradient over the B images of fake -- "small"
+    (sr_conv3x3_small_bf16 where small_conv_wins) or "conv2d" (sr_conv2d_dev_bf16) -- and whether a 2 x 2 max-pool follows.  B None: the image-size rule alone."""
+    out, h, w, cin = [], int(H), int(W), 3
+    fwd_images, bwd_images = (1, 1) if B is None else (2 * int(B), int(B))
+    for blk, n, cout in VGG19_CFG:
+        if h < 1 or w < 1:
+            raise ValueError(f"perceptual_dtype='bf16': HR patches of {H} x {W} leave no pixel for block{blk} of VGG19")
+        for k in range(1, n + 1):
+            route = lambda images, ci, co: "small" if small_conv_wins(h, w, ci, co, images) else "conv2d"
+            out.append((f"block{blk}_conv{k}", h, w, cin, cout, route(fwd_images, cin, cout), k == n and blk < 5, route(bwd_images, cout, cin)))
+            cin = cout
+        h, w = h // 2, w // 2
+    return out
+
+
+class PerceptualBf16:
+    """perceptual_dtype="bf16": mean((VGG19(fake) - VGG19(hr))^2) at block5_conv4 and its gradient w.r.t. fake in bf16 mixed precision -- fp32
+    master weights rounded to bf16 once, bf16 activations and activation gradients, fp32 accumulation and epilogues, one rounding per stored tensor.  ONE forward
+    over the batch [fake | hr], one loss launch pair, one backward over the fake half; every ReLU gradient is a select fused into the kernel that writes the tensor
+    (the small-image conv's mask operand, the pool's backward, the loss) except behind an sr_conv2d_dev_bf16 input gradient that follows another conv.
+    `bucket`: the frozen VGG19's ParamBucket.  The packs of the small-image kernel live here for as long as the weights do; the few large-image layers are listed
+    by pack_uses() for the step's sr_conv_prepack_bf16."""
+
+    def __init__(self, ctx, bucket):
+        self.ctx, self.dev = ctx, bucket.dev
+        k, _ = self.dev["block1_conv1"]
+        self.k6 = torch.cat([k, k], dim=2).contiguous()        # the hi + lo entry: the layer's kernel twice along Cin
+        self._handles = {}
+        self.tape = None                                        # tests: a list here receives (name, tensor) for every tensor the branch stores
+
+    def handle(self, name, rot):
+        if (name, rot) not in self._handles:
+            self._handles[(name, rot)] = self.ctx.conv3x3_small_pack(self.dev[name][0], rot=rot)
+        return self._handles[(name, rot)]
+
+    def pack_uses(self, B, H, W):
+        """pack_list entries of the calls sr_conv2d_dev_bf16 runs on a batch of B HR patches of H x W: forward and input-gradient uses."""
+        uses = []
+        for i, (name, _, _, _, _, route, _, route_bwd) in enumerate(perceptual_routes(H, W, B)):
+            kd, bd = self.dev[name]
+            if i == 0:
+                uses += [(self.k6, bd, False), (kd, None, True)]
+                continue
+            uses += [(kd, bd, False)] if route == "conv2d" else []
+            uses += [(kd, None, True)] if route_bwd == "conv2d" else []
+        return uses
+
+    def _keep(self, name, t):
+        if self.tape is not None:
+            self.tape.append((name, t))
+        return t
+
+    def __call__(self, hr_t, fake):
+        """hr_t, fake fp32 [B,H,W,3] in [-1,1] -> (perc fp32 [1] device tensor, d perc / d fake fp32 [B,H,W,3])."""
+        ctx, dev = self.ctx, self.dev
+        B, H, W, _ = fake.shape
+        routes = perceptual_routes(H, W, B)
+        h = self._keep("pre", ctx.vgg_preprocess_bf16(fake, hr_t))
+        acts = []
+        for i, (name, _, _, _, cout, route, pooled, _) in enumerate(routes):
+            kd, bd = dev[name]
+            if i == 0:
+                h = ctx.conv2d_dev_bf16(h, self.k6, bd, cout, act="relu")
+            elif route == "small":
+                h = ctx.conv3x3_small_bf16(h, None, bd, cout, act="relu", packed=self.handle(name, False))
+            else:
+                h = ctx.conv2d_dev_bf16(h, kd, bd, cout, act="relu")
+            acts.append(self._keep(name, h))
+            if pooled:
+                h = self._keep(name + "_pool", ctx.maxpool2_bf16(h))
+        perc, g = ctx.mse_grad_bf16(h)
+        self._keep("d_" + routes[-1][0], g)
+        for i in range(len(routes) - 1, 0, -1):                 # g: the gradient of layer i's pre-activation -> of layer i - 1's, over the fake half
+            name, _, _, cin, _, _, _, route = routes[i]
+            prev, prev_pooled = routes[i - 1][0], routes[i - 1][6]
+            a_prev = acts[i - 1][:B]
+            if route == "small":
+                g = ctx.conv3x3_small_bf16(g, None, None, cin, rot=True, mask=None if prev_pooled else a_prev, packed=self.handle(name, True))
+            else:
+                g = ctx.conv2d_dev_bf16(g, dev[name][0], None, cin, rot=True)
+                if not prev_pooled:
+                    self._keep("dx_" + name, g)
+                    g = ctx.relu_bwd_bf16(g, a_prev)
+            if prev_pooled:
+                self._keep("d_" + prev + "_pool", g)
+                g = ctx.maxpool2_bwd_bf16(a_prev, g)
+            self._keep("d_" + prev, g)
+        dv = self._keep("d_pre", ctx.conv2d_dev_bf16(g, dev["block1_conv1"][0], None, 3, rot=True))
+        return perc, ctx.vgg_preprocess_bwd(dv)
+
+
 def bce_mean(target, p, eps=1e-7):
     """mean(keras.backend.binary_crossentropy) on probabilities and its gradient w.r.t. p (clip passes the gradient inside [eps, 1-eps])."""
     pc = np.clip(p, eps, 1.0 - eps)
@@ -817,9 +936,10 @@ class ESRGANTrainer:
     dw, u, d_opt, d_params = (_discriminator_attr(name) for name in ("weights", "u", "opt", "params"))
 
     def __init__(self, ctx, g_weights, d_weights, vgg_weights, scale, num_rrdb, attention=True, g_lr=1e-4, d_lr=1e-5, u_seed=0, allreduce=None,
-                 allreduce_flat=None, discriminator="host", attention_impl="materialised", train_dtype="f32", dense_block_impl="layers"):
+                 allreduce_flat=None, discriminator="host", attention_impl="materialised", train_dtype="f32", dense_block_impl="layers", perceptual_dtype="f32"):
         if discriminator not in ("host", "device"):
             raise ValueError(f"discriminator must be 'host' or 'device', got {discriminator!r}")
+        self.perceptual_dtype = check_perceptual_dtype(perceptual_dtype)      # the VGG19 perceptual term of train_step (PerceptualBf16); refused before any upload
         # what the taped training pass stores inside the RRDB trunk (Tape.trunk_bf16 / trunk_lds); refused before anything is uploaded or launched
         self.train_dtype = check_train_dtype(train_dtype)
         self.dense_block_impl = check_dense_block_impl(dense_block_impl, train_dtype)
@@ -837,6 +957,7 @@ class ESRGANTrainer:
         self.g_params = ParamBucket(ctx, g_weights)
         self.vw = vgg_weights
         self._vgg = self._vgg_src = None                   # the frozen VGG19 on the device (a bucket of self.vw), uploaded by train_step
+        self._perc16 = None                                # perceptual_dtype="bf16": the branch and its packed kernels, remade when the VGG19 weights are replaced
         self.g_lr0, self.d_lr0 = g_lr, d_lr
         self.g_opt = DeviceAdam(ctx, self.g_params.flat, g_lr, epsilon=1e-7)
         # d_weights / vgg_weights None: a generator-only trainer (pixel_step: sr355.recipes' L1 fit); it has no discriminator object and train_step refuses
@@ -859,13 +980,16 @@ class ESRGANTrainer:
         self._lds_packed = False
 
     @contextlib.contextmanager
-    def _prepacked(self, with_vgg):
+    def _prepacked(self, with_vgg, hr_shape=None):
         """Pack every generator (and VGG19) conv's weights for its forward and its input-gradient use by ONE launch (sr_conv_prepack; ~700 of a step's ~800
         per-use packs, 3.5 ms of 53) for the duration of the block.  The discriminator's kernels are renormalised inside the step and keep packing per use.
-        The list is dropped when the block ends: nobody else on this context may meet a pack older than the weights."""
+        The list is dropped when the block ends: nobody else on this context may meet a pack older than the weights.
+        perceptual_dtype="bf16" (hr_shape: the step's (B, H, W) of HR patches): the VGG19 layers stand in no fp32 list; the calls of the small-image kernel keep
+        the handles PerceptualBf16 packed once, the others join the step's bf16 list."""
+        vgg16 = with_vgg and self.perceptual_dtype == "bf16"
         if with_vgg not in self._packs:
             uses = []
-            for params in [self.g_params] + ([self._vgg] if with_vgg else []):
+            for params in [self.g_params] + ([self._vgg] if with_vgg and not vgg16 else []):
                 for n, (kd, bd) in params.dev.items():
                     if params is self.g_params and n in self._trunk:      # train_dtype="bf16": the trunk's layers stand in the bf16 list only
                         continue
@@ -873,9 +997,12 @@ class ESRGANTrainer:
                         uses += [(kd, bd, False), (kd, None, True)]
             self._packs[with_vgg] = self.ctx.pack_list(uses)
         lds = self.dense_block_impl == "lds"
-        if self._trunk and not lds and "bf16" not in self._packs:      # every trunk kernel rounded to bf16 once per step, for its forward and its input-gradient use
+        trunk16 = bool(self._trunk) and not lds
+        key16 = ("bf16", tuple((r[5], r[7]) for r in perceptual_routes(hr_shape[1], hr_shape[2], hr_shape[0]))) if vgg16 else "bf16"      # what changes the list: which calls stay on sr_conv2d_dev_bf16
+        if (trunk16 or vgg16) and key16 not in self._packs:   # every trunk kernel rounded to bf16 once per step, for its forward and its input-gradient use
             dev = self.g_params.dev
-            self._packs["bf16"] = self.ctx.pack_list([u for n in dev if n in self._trunk for u in ((dev[n][0], dev[n][1], False), (dev[n][0], None, True))])
+            uses16 = [u for n in dev if n in self._trunk for u in ((dev[n][0], dev[n][1], False), (dev[n][0], None, True))] if trunk16 else []
+            self._packs[key16] = self.ctx.pack_list(uses16 + (self._perc16.pack_uses(*hr_shape) if vgg16 else []))
         if lds and "lds" not in self._packs:                  # dense_block_impl="lds": the trunk's blocks as fragments of the LDS-resident kernels, in buffers of the trainer's
             dev, names = self.g_params.dev, [f"rrdb_{b}_dense{d}" for b in range(self.nb) for d in (1, 2, 3)]
             table = self.ctx.dense_block_pack_table([([dev[f"{n}_conv{k}"][0] for k in range(1, 6)], [dev[f"{n}_conv{k}"][1] for k in range(1, 6)]) for n in names])
@@ -884,14 +1011,14 @@ class ESRGANTrainer:
         if lds:
             self.ctx.dense_block_pack_dev(*self._packs["lds"][:4])     # ... rounded to bf16 once per step, by one launch
             self._lds_packed = True
-        elif self._trunk:
-            self.ctx.conv_prepack_bf16(self._packs["bf16"])
+        if trunk16 or vgg16:
+            self.ctx.conv_prepack_bf16(self._packs[key16])
         try:
             yield
         finally:
             self.ctx.conv_prepack(None)
             self._lds_packed = False                          # the weights move on in the step's last lines: a tape made outside the block packs for itself
-            if self._trunk and not lds:
+            if trunk16 or vgg16:
                 self.ctx.conv_prepack_bf16(None)
 
     @property
@@ -976,9 +1103,12 @@ class ESRGANTrainer:
         self._check_patch(lr_images)
         if self._vgg_src is not self.vw:                  # the first step, or ESRGAN.set_loss_network_weights has replaced the VGG19 weights
             self._vgg, self._vgg_src = ParamBucket(self.ctx, self.vw), self.vw
-            self._packs.pop(True, None)
+            for key in [k for k in self._packs if k is True or (isinstance(k, tuple) and k[0] == "bf16")]:
+                del self._packs[key]
+            self._perc16 = PerceptualBf16(self.ctx, self._vgg) if self.perceptual_dtype == "bf16" else None
         ctx, disc = self.ctx, self.disc
-        with self._prepacked(True):                        # the generator's weights change only in the step's last lines, VGG19's never
+        hr_shape = hr_images.shape if hasattr(hr_images, "shape") else np.shape(hr_images)
+        with self._prepacked(True, tuple(int(v) for v in hr_shape[:3])):                     # the generator's weights change only in the step's last lines, VGG19's never
             lr_t, hr_t = _device_batch(ctx, lr_images), _device_batch(ctx, hr_images)
             # The reference runs the generator twice per step, once under each tape (ESRGAN_model.py:490, :508); its weights do not change
             # in between (the discriminator is updated first), so both runs are the same tensor: one taped forward serves both.
@@ -1011,18 +1141,22 @@ class ESRGANTrainer:
         """The generator loss beside its adversarial term: VGG19 perceptual (x 1), pixel L1 (x 100) and spectral (x 1) of `fake` against hr_t
         -> (perc, pix, spec as one-element device tensors, d g_loss / d fake: their gradients and d_adv, the adversarial term's)."""
         ctx = self.ctx
-        tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
-        fr = vgg19_features(tv, Var(hr_t, need=False))
-        tv.ops = []
-        yv = Var(fake)
-        ff = vgg19_features(tv, yv)
-        perc = ctx.mse(fr.v, ff.v)
-        ff.g = ctx.eltwise(L.ELT_AXPBY, ff.v, fr.v, 2.0 / ff.v.numel(), -2.0 / ff.v.numel())
-        tv.backward()
+        if self.perceptual_dtype == "bf16":
+            perc, d_perc = self._perc16(hr_t, fake)
+        else:
+            tv = Tape(ctx, self._vgg.arrays, wgrad=False, devcache=self._vgg.devcache)
+            fr = vgg19_features(tv, Var(hr_t, need=False))
+            tv.ops = []
+            yv = Var(fake)
+            ff = vgg19_features(tv, yv)
+            perc = ctx.mse(fr.v, ff.v)
+            ff.g = ctx.eltwise(L.ELT_AXPBY, ff.v, fr.v, 2.0 / ff.v.numel(), -2.0 / ff.v.numel())
+            tv.backward()
+            d_perc = yv.g
         pix = ctx.l1(hr_t, fake)
         spec = ctx.spectral_l1(fake, hr_t)
         dy = ctx.eltwise(L.ELT_SIGN_DIFF, fake, hr_t, 100.0 / fake.numel(), 0.0)
         dy = ctx.eltwise(L.ELT_AXPBY, dy, ctx.spectral_l1_bwd(fake, hr_t, 1.0), 1.0, 1.0)
         dy = ctx.eltwise(L.ELT_AXPBY, dy, d_adv, 1.0, 1.0)
-        dy = ctx.eltwise(L.ELT_AXPBY, dy, yv.g, 1.0, 1.0)
+        dy = ctx.eltwise(L.ELT_AXPBY, dy, d_perc, 1.0, 1.0)
         return perc, pix, spec, dy

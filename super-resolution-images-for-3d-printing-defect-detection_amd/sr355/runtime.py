@@ -1042,6 +1042,112 @@ class Context:
         self.check(self.lib.sr_relu_bwd_bf16(self.h, dy.data_ptr(), y.data_ptr(), out.data_ptr(), dy.numel(), self.stream()))
         return out
 
+    # ---- 3x3 convs over many small images (sr_conv3x3_small_bf16: the 3 x 3 and 6 x 6 images of the VGG19 extractor's blocks 4-5 on training patches; gan_train.small_conv_wins says which calls)
+    SMALL_CONV_MAX_PIXELS = 144
+
+    @classmethod
+    def small_conv_takes(cls, H, W, cin, cout):
+        """The shape class of sr_conv3x3_small_bf16: images of at most 144 pixels, channel counts multiples of 32."""
+        return H >= 1 and W >= 1 and H * W <= cls.SMALL_CONV_MAX_PIXELS and cin > 0 and cout > 0 and cin % 32 == 0 and cout % 32 == 0
+
+    def conv3x3_small_pack(self, w_dev, rot=False):
+        """The packed-kernel handle of conv3x3_small_bf16 for the fp32 device kernel w_dev ([3,3,Cin,Cout], or with rot=True the forward kernel of the layer whose
+        input gradient is wanted): a bf16 tensor the caller keeps for as long as the weights stand (sr_conv3x3_small_pack_bf16)."""
+        _check_tensor(self, w_dev, "conv3x3_small_pack kernel")
+        if w_dev.dim() != 4 or tuple(w_dev.shape[:2]) != (3, 3):
+            raise ValueError("conv3x3_small_pack: the kernel must be [3,3,I,O]")
+        cin, cout = (int(w_dev.shape[3]), int(w_dev.shape[2])) if rot else (int(w_dev.shape[2]), int(w_dev.shape[3]))
+        nbytes = int(self.lib.sr_conv3x3_small_pack_bytes(cin, cout))
+        packed = self.empty((max(nbytes, 2) // 2,), torch.bfloat16)
+        self.check(self.lib.sr_conv3x3_small_pack_bf16(self.h, w_dev.data_ptr(), cin, cout, int(bool(rot)), packed.data_ptr(), self.stream()))
+        return packed
+
+    def conv3x3_small_bf16(self, x, w_dev, b_dev, cout, rot=False, act="linear", mask=None, packed=None):
+        """bf16 x [B,H,W,Cin] (H * W <= 144, Cin and cout multiples of 32) -> bf16(act(conv3x3(x) + b)), zeroed where mask <= 0 (sr_conv3x3_small_bf16).  The
+        kernel comes from w_dev as conv2d_dev_bf16 takes it, or from a handle of conv3x3_small_pack (then w_dev may be None)."""
+        _check_tensor(self, x, "conv3x3_small_bf16 input", self._BF16)
+        if x.dim() != 4:
+            raise ValueError("conv3x3_small_bf16: x must be [B,H,W,C]")
+        B, H, W, Cx = x.shape
+        if packed is None:
+            _check_tensor(self, w_dev, "conv3x3_small_bf16 kernel")
+            want = (3, 3, cout, Cx) if rot else (3, 3, Cx, cout)
+            if tuple(w_dev.shape) != want:
+                raise ValueError(f"conv3x3_small_bf16: kernel shape {tuple(w_dev.shape)} does not match {want}")
+        else:
+            _check_tensor(self, packed, "conv3x3_small_bf16 packed kernel", self._BF16)
+            if packed.numel() * 2 != int(self.lib.sr_conv3x3_small_pack_bytes(Cx, int(cout))):
+                raise ValueError("conv3x3_small_bf16: the packed kernel was made for other channel counts")
+        if b_dev is not None:
+            _check_tensor(self, b_dev, "conv3x3_small_bf16 bias")
+            if b_dev.numel() != cout:
+                raise ValueError("conv3x3_small_bf16: the bias must have one value per output channel")
+        if mask is not None:
+            _check_tensor(self, mask, "conv3x3_small_bf16 mask", self._BF16)
+            if tuple(mask.shape) != (B, H, W, cout):
+                raise ValueError("conv3x3_small_bf16: the mask must have the output's shape")
+        if act not in ("linear", None, "relu"):
+            raise ValueError("conv3x3_small_bf16: act is 'linear' or 'relu'")
+        y = self.empty((B, H, W, cout), torch.bfloat16)
+        self.check(self.lib.sr_conv3x3_small_bf16(self.h, x.data_ptr(), B, H, W, Cx, None if packed is not None else w_dev.data_ptr(),
+                                                  None if packed is None else packed.data_ptr(), None if b_dev is None else b_dev.data_ptr(), int(cout),
+                                                  int(bool(rot)), L.ACT_RELU if act == "relu" else L.ACT_LINEAR, None if mask is None else mask.data_ptr(),
+                                                  y.data_ptr(), self.stream()))
+        return y
+
+    # ---- the other kernels of the bf16 perceptual branch (sr355/gan_train.py, PerceptualBf16)
+    def vgg_preprocess_bf16(self, fake, hr):
+        """fake, hr fp32 [B,H,W,3] in [-1,1] -> bf16 [2B,H,W,6], fake first: caffe preprocessing as a hi + lo pair of bf16 (sr_vgg_preprocess_bf16)."""
+        _check_tensor(self, fake, "vgg_preprocess_bf16 fake")
+        _check_tensor(self, hr, "vgg_preprocess_bf16 hr")
+        if fake.dim() != 4 or fake.shape[3] != 3 or hr.shape != fake.shape:
+            raise ValueError("vgg_preprocess_bf16: two [B,H,W,3] tensors of one shape")
+        B, H, W, _ = fake.shape
+        out = self.empty((2 * B, H, W, 6), torch.bfloat16)
+        self.check(self.lib.sr_vgg_preprocess_bf16(self.h, fake.data_ptr(), hr.data_ptr(), B, H, W, out.data_ptr(), self.stream()))
+        return out
+
+    def vgg_preprocess_bwd(self, dv):
+        """The bf16 gradient [B,H,W,3] of the preprocessed image -> the fp32 gradient of the [-1,1] RGB image (sr_vgg_preprocess_bwd)."""
+        _check_tensor(self, dv, "vgg_preprocess_bwd dv", self._BF16)
+        if dv.dim() != 4 or dv.shape[3] != 3:
+            raise ValueError("vgg_preprocess_bwd: dv must be [B,H,W,3]")
+        out = self.empty(dv.shape, torch.float32)
+        self.check(self.lib.sr_vgg_preprocess_bwd(self.h, dv.data_ptr(), dv.numel() // 3, out.data_ptr(), self.stream()))
+        return out
+
+    def maxpool2_bf16(self, x):
+        """MaxPooling2D(2,2) VALID on bf16 [B,H,W,C] (sr_maxpool2_bf16)."""
+        _check_tensor(self, x, "maxpool2_bf16 input", self._BF16)
+        if x.dim() != 4:
+            raise ValueError("maxpool2_bf16: x must be [B,H,W,C]")
+        B, H, W, Cx = x.shape
+        y = self.empty((B, H // 2, W // 2, Cx), torch.bfloat16)
+        self.check(self.lib.sr_maxpool2_bf16(self.h, x.data_ptr(), B, H, W, Cx, y.data_ptr(), self.stream()))
+        return y
+
+    def maxpool2_bwd_bf16(self, x, dy):
+        """dy routed to each window's winner where the pre-pool activation x is positive, else 0 (sr_maxpool2_bwd_bf16)."""
+        _check_tensor(self, x, "maxpool2_bwd_bf16 x", self._BF16)
+        _check_tensor(self, dy, "maxpool2_bwd_bf16 dy", self._BF16)
+        if x.dim() != 4 or tuple(dy.shape) != (x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3]):
+            raise ValueError("maxpool2_bwd_bf16: dy must be [B,H/2,W/2,C] of x [B,H,W,C]")
+        B, H, W, Cx = x.shape
+        dx = torch.empty_like(x)
+        self.check(self.lib.sr_maxpool2_bwd_bf16(self.h, x.data_ptr(), dy.data_ptr(), B, H, W, Cx, dx.data_ptr(), self.stream()))
+        return dx
+
+    def mse_grad_bf16(self, feats):
+        """feats bf16 [2B,...] = [ff | fr] -> (perc fp32 [1] = mean((ff - fr)^2), dff bf16 [B,...] = 2 / n * (ff - fr) where ff > 0, else 0) (sr_mse_grad_bf16)."""
+        _check_tensor(self, feats, "mse_grad_bf16 feats", self._BF16)
+        if feats.dim() < 1 or feats.shape[0] % 2:
+            raise ValueError("mse_grad_bf16: the leading axis holds the two halves of the batch")
+        half = feats.shape[0] // 2
+        perc = self.empty((1,), torch.float32)
+        dff = self.empty((half,) + tuple(feats.shape[1:]), torch.bfloat16)
+        self.check(self.lib.sr_mse_grad_bf16(self.h, feats.data_ptr(), dff.numel(), perc.data_ptr(), dff.data_ptr(), self.stream()))
+        return perc, dff
+
     def space_to_depth_bf16(self, x, r):
         """space_to_depth on a bf16 tensor (sr_space_to_depth_bf16)."""
         _check_tensor(self, x, "space_to_depth_bf16 input", self._BF16)
