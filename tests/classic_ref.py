@@ -108,6 +108,37 @@ def nl_means(x_u8, h, patch=5, distance=6):
     return num / 255.0 / den
 
 
+def nl_means_dist(x_u8, h, patch=5, distance=6):
+    """nl_means' own `dist` of every (shift, pixel) pair, [(2d+1)^2, h, w] in its shift order, and the shifted pixel values beside it (the same
+    expressions as in nl_means; tests/test_classic_args_cpu.py holds nl_means_of_dist(dist, vals, dist <= 5) to nl_means bit for bit)."""
+    s = patch // 2
+    R = s + distance
+    hh, ww = x_u8.shape
+    P = np.pad(x_u8.astype(np.int64), R, mode="reflect")
+    h2s2 = h * h * patch * patch
+    dist, vals = [], []
+    for ty in range(-distance, distance + 1):
+        for tx in range(-distance, distance + 1):
+            sq = (P[distance:distance + hh + 2 * s, distance:distance + ww + 2 * s]
+                  - P[distance + ty:distance + ty + hh + 2 * s, distance + tx:distance + tx + ww + 2 * s]) ** 2
+            c = np.cumsum(np.cumsum(np.pad(sq, ((1, 0), (1, 0))), axis=0), axis=1)
+            D = c[patch:, patch:] - c[:-patch, patch:] - c[patch:, :-patch] + c[:-patch, :-patch]
+            dist.append(D.astype(np.float64) / 65025.0 / h2s2)
+            vals.append(P[R + ty:R + ty + hh, R + tx:R + tx + ww])
+    return np.stack(dist), np.stack(vals)
+
+
+def nl_means_of_dist(dist, vals, keep):
+    """nl_means' weighted mean from nl_means_dist's arrays, with the weights of the pairs where `keep` is false dropped."""
+    num = np.zeros(dist.shape[1:])
+    den = np.zeros(dist.shape[1:])
+    for d, v, k in zip(dist, vals, keep):
+        wgt = np.where(k, np.exp(-np.minimum(d, 5.0)), 0.0)
+        den += wgt
+        num += wgt * v
+    return num / 255.0 / den
+
+
 def nl_means_pairloop(x_u8, h, patch=5, distance=6):
     """The same denoising as skimage's fast-mode loop runs it: pad by s + d + 1, for each shift (t_row, t_col >= 0) an integral image
     of the squared differences, the patch distance from four corners, and each pair (p, p+t) visited once, with weight alpha*w added
