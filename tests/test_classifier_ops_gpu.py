@@ -19,6 +19,8 @@ from sr355 import Model
 from sr355 import _lib as L
 from sr355.weights import bf16_rounded, init_weights, round_to_bf16
 
+from tap_util import forward_tapped, host
+
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24          # unit round-off of fp32
@@ -28,10 +30,6 @@ U = 2.0 ** -24          # unit round-off of fp32
 def restore_fused(ctx):
     yield
     ctx.set_fused(ctx.FUSED_ALL, 0)
-
-
-def host(t):
-    return t.float().cpu().numpy()
 
 
 def rel_l2(a, b):
@@ -178,26 +176,6 @@ def pool_ops(m, n_pools):
     for k, i in enumerate(idx):
         assert ops[i - 1][0].startswith(f"block{k + 1}_conv") and ops[i - 1][1] == ops[i][1] > 0, (ops[i - 1], ops[i])
     return idx
-
-
-def forward_tapped(m, x, idx):
-    """forward with a tap on every op of `idx` -> (y, {op index: fp32 NHWC tensor}).  The tap buffers start out as NaN: a tap that is never
-    written, or written in part, cannot pass for the values an earlier call left in the same memory."""
-    ctx, ops = m.ctx, m.ops()
-    B, H, W, _ = x.shape
-    taps = {}
-    try:
-        for i in idx:
-            h, w = Model._op_hw(ops[i], H, W)
-            t = torch.full((B, h, w, ops[i][1]), float("nan"), dtype=torch.float32, device=ctx.torch_device)
-            ctx.check(ctx.lib.sr_model_set_tap(m.h, i, t.data_ptr(), t.numel()))
-            taps[i] = t
-        y = m.forward(x)
-        torch.cuda.synchronize()
-    finally:
-        for i in idx:
-            ctx.lib.sr_model_set_tap(m.h, i, None, 0)
-    return y, taps
 
 
 def kernels_of(ctx, fn):
