@@ -117,6 +117,22 @@ int  sr_debug_set_fused(sr_ctx* ctx, int mask, int max_workgroups);
  * image of 96 bf16 channels, in whole 256-byte bank rows per 8-channel plane), or -1 where that kernel does not apply: growth_channels != 8, H or W < 1, or more than
  * the 160 KiB of a CU.  Every H, W with (H + 2)(W + 2) <= 676 fits.  Pure function, no context: sr_forward's router and the kernel's launcher both ask it. */
 int64_t sr_dense_block_lds_bytes(int growth_channels, int H, int W);
+/* The streamed dense-block kernel (dense_block_stream<bf16,g8>): the same block as ONE kernel for images too large to be LDS-resident, their rows streamed through a
+ * ring in LDS (ESRGAN.super_resolve_image's default 48 x 48 patches).  Any height; the ring sets the width.
+ * sr_dense_block_stream_lds_bytes: the dynamic LDS of the ring for images W pixels wide, or -1 where the kernel does not apply: growth_channels != 8, W < 1, or
+ *   more than the 160 KiB of a CU at the smallest ring (8 rows).  Every W <= 96 fits; never falls as W grows.  Pure, no context: router, launcher and tests ask it.
+ * sr_dense_block_stream_bands: a work item of the kernel is (image, band of consecutive output rows); halo rows are recomputed, nothing is exchanged.  Returns the
+ *   band count for B images of H rows on num_cus CUs -- 1 when B >= num_cus, else as many bands as leave every (image, band) a CU of its own, none shorter than 3 rows -- and, with y0_out
+ *   not NULL, writes each band's first row (band b ends where b + 1 starts, the last at H).  -1 for B, H or num_cus < 1, or when `cap` entries do not hold
+ *   the bands (nothing is written).  Pure.  The result of a forward does not depend on the band count.
+ * sr_model_set_dense_block_stream: when a forward of this model takes the kernel, under the conditions of the resident kernel (mask bits 0, 1 and 5).  mode 0, the
+ *   default: never.  1: where the resident kernel does not fit and the ring does.  2: wherever the ring fits, also in place of the resident kernel (diagnostic).
+ *   SR_ERR_INVALID for another mode, or for a model that is not ESRGAN_G / bf16 / 8 growth channels on row-blocked concat buffers.
+ * sr_debug_set_block_stream_bands: test hook.  n = 0: automatic; n > 0: that many bands (at most H). */
+int64_t sr_dense_block_stream_lds_bytes(int growth_channels, int W);
+int  sr_dense_block_stream_bands(int B, int H, int num_cus, int32_t* y0_out, int cap);
+int  sr_model_set_dense_block_stream(sr_model* m, int mode);
+int  sr_debug_set_block_stream_bands(sr_ctx* ctx, int n);
 /* The bits of sr_debug_set_fused's mask, as described above.  SR_FUSE_TWO_UP: the bits the two-up packing of 24-pixel-wide images needs. */
 enum { SR_FUSE_DENSE_TAIL = 1, SR_FUSE_DENSE_MID = 2, SR_FUSE_RGB_TAIL = 4, SR_FUSE_ATTN_PROJ = 8, SR_FUSE_CELLS = 16, SR_FUSE_CONV1_STREAM = 32,
        SR_FUSE_POOL = 64, SR_FUSE_CONV_STREAM = 128, SR_FUSE_SRCNN_1X1 = 256, SR_FUSE_ALL = 511,

@@ -25,9 +25,12 @@ class _Normalised:
         self.t = t
 
 
+INFER_DENSE_BLOCK_IMPLS = ("layers", "stream")
+
+
 class ESRGAN(DeviceModelMixin):
     def __init__(self, compute_dtype="f32", discriminator_update="host", train_attention="materialised", train_dtype="f32", train_dense_block="layers",
-                 perceptual_dtype="f32"):
+                 perceptual_dtype="f32", infer_dense_block="layers"):
         """compute_dtype: "f32" (default: what the reference computes in, like SRCNNModel / EDSR / FineTunedVGG16 here; fp32 MFMA,
         >= 100 dB against the fp64 oracle) or "bf16" (opt-in: bf16 storage, fp32 accumulation -- BASELINE configs[2]'s dtype and what
         bench.py passes; ~49 dB against the fp32 graph on the bench patches, |dPSNR vs HR| well under 0.01 dB: INTEGRATION.md).
@@ -45,7 +48,13 @@ class ESRGAN(DeviceModelMixin):
         24 x 24, checked by every step: DESIGN.md 3.28); "lds" without train_dtype="bf16", or anything else, raises ValueError here.
         perceptual_dtype: the arithmetic of _train_step's VGG19 perceptual term and of its gradient -- "f32" (default: the reference's) or "bf16" (opt-in: one bf16
         forward over [fake | hr] and one backward over fake, fp32 master weights packed once, the small-image conv kernel on the 3 x 3 and small 6 x 6 calls of blocks 4-5 where it measured fastest: DESIGN.md 3.29); anything
-        else raises ValueError here.  Independent of the options above; evaluate and fit's validation pass stay fp32."""
+        else raises ValueError here.  Independent of the options above; evaluate and fit's validation pass stay fp32.
+        infer_dense_block: how inference (super_resolve_image, the generator's forward) runs a dense block of the notebook's graph on patches too large for the
+        LDS-resident kernel -- "layers" (default: conv by conv, as before) or "stream" (opt-in: one kernel per block that streams the patch's rows through a ring in
+        LDS, dense_block_stream<bf16,g8>: super_resolve_image's default patch_size_lr = 48, any height, widths up to 96: DESIGN.md 3.30; patches up to 24 x 24 keep
+        the resident kernel, and a wider image silently runs conv by conv, per call).  "stream" needs compute_dtype="bf16" and growth_channels = 8 (also when the
+        width is read from a checkpoint): setup_model raises ValueError otherwise; anything else raises ValueError here.  Training, evaluate's fp32 passes and
+        the fp32 default are not affected."""
         from sr355.gan_train import check_attention_impl, check_dense_block_impl, check_perceptual_dtype, check_train_dtype
         self.generator = None
         self.discriminator = None
@@ -59,6 +68,9 @@ class ESRGAN(DeviceModelMixin):
         self.train_dtype = check_train_dtype(train_dtype)
         self.train_dense_block = check_dense_block_impl(train_dense_block, self.train_dtype)
         self.perceptual_dtype = check_perceptual_dtype(perceptual_dtype)
+        if infer_dense_block not in INFER_DENSE_BLOCK_IMPLS:
+            raise ValueError(f"infer_dense_block must be one of {INFER_DENSE_BLOCK_IMPLS}, got {infer_dense_block!r}")
+        self.infer_dense_block = infer_dense_block
 
     def _mark_trained(self, v):
         self.trained = v
@@ -75,8 +87,12 @@ class ESRGAN(DeviceModelMixin):
             growth_channels = int(weights["rrdb_0_dense1_conv1"][0].shape[-1]) if "rrdb_0_dense1_conv1" in weights else growth_channels
             num_rrdb_blocks = len({n.split("_")[1] for n in weights if n.startswith("rrdb_")})
         self.num_rrdb_blocks, self.use_attention, self._trainer = int(num_rrdb_blocks), bool(use_attention), None
+        stream = self.infer_dense_block == "stream"
+        if stream and (self.compute_dtype != "bf16" or int(growth_channels) != 8):     # an explicit opt-in must not silently do nothing
+            raise ValueError(f'infer_dense_block="stream" needs compute_dtype="bf16" and growth_channels=8, got {self.compute_dtype!r} and {growth_channels}')
         self.generator = self._make("esrgan_g", self.compute_dtype, scale_factor=scale_factor, channels=int(input_shape[-1]),
-                                    num_blocks=num_rrdb_blocks, growth_channels=growth_channels, use_attention=use_attention)
+                                    num_blocks=num_rrdb_blocks, growth_channels=growth_channels, use_attention=use_attention,
+                                    **({"dense_block_stream": 1} if stream else {}))
         if weights is not None:
             self.set_weights(weights)
             print(f"- Generator loaded from: {generator_pretrained_path}")

@@ -163,6 +163,7 @@ struct sr_model {
     struct Tap { float* dst; int64_t cap; };
     std::unordered_map<int, Tap> taps; // diagnostic: op index -> device fp32 destination (sr_model_set_tap)
     std::vector<std::string> op_names; // per op, for sr_model_op_info
+    int block_stream = 0;             // sr_model_set_dense_block_stream: 0 never, 1 where the resident dense-block kernel does not fit, 2 wherever the ring fits
 
     int find_param(const std::string& n, int which) const {
         for (size_t i = 0; i < params.size(); ++i) if (params[i].which == which && params[i].name == n) return (int)i;
@@ -526,10 +527,16 @@ struct Layout {
 
 // the dense blocks of this forward run as one LDS-resident kernel each (dense_block.hip): the model has them packed (bf16, 8 growth channels, row-blocked concat
 // buffers), the mask holds the three bits that mean "the whole dense block on fused kernels", and an image of the concat buffers fits the LDS
-bool block_here(const sr_model* m, int H, int W) {
-    return m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && !m->blocks.empty() && (m->ctx->chain_mask & SR_FUSE_TWO_UP) == SR_FUSE_TWO_UP &&
-           sr_dense_block_lds_bytes(m->cfg.growth_channels, H, W) > 0;
+// ... or, where the model asks for it (sr_model_set_dense_block_stream), the row ring of the streamed kernel (dense_block_stream.hip) is no wider than the LDS
+enum BlockKernel { BLOCK_NONE, BLOCK_RESIDENT, BLOCK_STREAM };
+BlockKernel block_kernel(const sr_model* m, int H, int W) {
+    if (!(m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && !m->blocks.empty() && (m->ctx->chain_mask & SR_FUSE_TWO_UP) == SR_FUSE_TWO_UP)) return BLOCK_NONE;
+    const bool ring = m->block_stream && H >= 1 && sr_dense_block_stream_lds_bytes(m->cfg.growth_channels, W) > 0;
+    if (m->block_stream == 2 && ring) return BLOCK_STREAM;
+    if (sr_dense_block_lds_bytes(m->cfg.growth_channels, H, W) > 0) return BLOCK_RESIDENT;
+    return ring ? BLOCK_STREAM : BLOCK_NONE;
 }
+bool block_here(const sr_model* m, int H, int W) { return block_kernel(m, H, W) != BLOCK_NONE; }
 
 Layout choose_layout(const sr_model* m, int B, int H, int W) {
     const int mask = m->ctx->chain_mask;
@@ -598,8 +605,8 @@ int ensure_workspace(sr_model* m, const Layout& L, int H, int W, hipStream_t st)
 
 // ---- the route of every op in one forward: its own kind (OP_CONV: a conv, possibly with the next op in its epilogue), or a fused route --------
 // (CHAIN: a dense-block pair as one kernel, launched at its first conv; CHAIN_SECOND: that pair's second conv; BLOCK: a whole dense block as one kernel, launched
-//  at its conv1; BLOCK_REST: that block's conv2 .. conv5; IN_EPILOGUE: computed by the conv in front of it)
-enum Route { RT_CHAIN = OP_PREPROC + 1, RT_CHAIN_SECOND, RT_BLOCK, RT_BLOCK_REST, RT_CONV1_STREAM, RT_RGB_TAIL, RT_PW2, RT_IN_EPILOGUE };
+//  at its conv1; BLOCK_STREAM: the same on the streamed kernel; BLOCK_REST: that block's conv2 .. conv5; IN_EPILOGUE: computed by the conv in front of it)
+enum Route { RT_CHAIN = OP_PREPROC + 1, RT_CHAIN_SECOND, RT_BLOCK, RT_BLOCK_REST, RT_CONV1_STREAM, RT_RGB_TAIL, RT_PW2, RT_IN_EPILOGUE, RT_BLOCK_STREAM };
 
 bool tapped(const sr_model* m, size_t oi) { return !m->taps.empty() && m->taps.count((int)oi) != 0; }
 // no skips, no clip, no depth_to_space
@@ -657,7 +664,10 @@ void plan_routes(sr_model* m, const Layout& L, int B, int H, int W) {
         if (rt[oi] != OP_CONV) continue;                                      // not a conv, or one the conv in front of it has taken
         int h, w;
         buf_hw(m->bufs[op.in.buf], H, W, &h, &w);
-        if (op.block >= 0 && op.block_pos == 0 && block_here(m, h, w)) { rt[oi] = RT_BLOCK; for (int k = 1; k < 5; ++k) rt[oi + k] = RT_BLOCK_REST; }
+        if (op.block >= 0 && op.block_pos == 0 && block_here(m, h, w)) {
+            rt[oi] = block_kernel(m, h, w) == BLOCK_STREAM ? RT_BLOCK_STREAM : RT_BLOCK;
+            for (int k = 1; k < 5; ++k) rt[oi + k] = RT_BLOCK_REST;
+        }
         else if (chain_fits(m, oi, w, L.pack2)) { rt[oi] = RT_CHAIN; rt[oi + 1] = RT_CHAIN_SECOND; }
         else if (conv1_stream_fits(m, op, w, L.pack2)) rt[oi] = RT_CONV1_STREAM;
         else if (rgb_tail_fits(m, op, oi, B, h, w)) { rt[oi] = RT_RGB_TAIL; rt[oi + 1] = RT_IN_EPILOGUE; }
@@ -757,6 +767,21 @@ int sr_debug_set_fused(sr_ctx* ctx, int mask, int max_workgroups) {
     if (!ctx) return SR_ERR_INVALID;
     ctx->chain_mask = mask;
     ctx->chain_max_wgs = max_workgroups > 0 ? max_workgroups : 0;
+    return SR_OK;
+}
+
+int sr_debug_set_block_stream_bands(sr_ctx* ctx, int n) {
+    if (!ctx) return SR_ERR_INVALID;
+    ctx->block_stream_bands = n > 0 ? n : 0;
+    return SR_OK;
+}
+
+int sr_model_set_dense_block_stream(sr_model* m, int mode) {
+    if (!m) return SR_ERR_INVALID;
+    if (mode < 0 || mode > 2) return m->ctx->fail(SR_ERR_INVALID, "sr_model_set_dense_block_stream: mode is 0, 1 or 2");
+    if (!(m->kind == SR_MODEL_ESRGAN_G && m->T == SR_DTYPE_BF16 && m->cfg.growth_channels == 8 && !m->blocks.empty()))
+        return m->ctx->fail(SR_ERR_INVALID, "sr_model_set_dense_block_stream: the streamed dense-block kernel serves bf16 ESRGAN generators of 8 growth channels only");
+    m->block_stream = mode;
     return SR_OK;
 }
 
@@ -1059,15 +1084,15 @@ int sr_forward(sr_model* m, const void* x, int io_dtype, int B, int H, int W, in
         switch (route) {
             case RT_CHAIN_SECOND: case RT_BLOCK_REST: case RT_IN_EPILOGUE:    // launched with the op in front of it (a tap reads its output below)
                 break;
-            case RT_BLOCK: {
+            case RT_BLOCK: case RT_BLOCK_STREAM: {
                 const Op& o5 = m->ops[oi + 4];
                 // which skip of conv5 is the block's own input (in LDS), which the other tensor (the RRDB's input, from memory)
                 const bool x1 = o5.skip1.buf == op.in.buf && o5.skip1.coff == 0;
                 const Ref& other = x1 ? o5.skip2 : o5.skip1;
                 bool grow = false;                                            // a tapped growth conv needs its slice in memory
                 for (int k = 0; k < 4; ++k) grow = grow || tapped(m, oi + k);
-                rc = block_launch(ctx, m->blocks[op.block].w, vi, B, h, w, m->view(o5.out), other.buf >= 0 ? m->view(other) : TensorView{}, o5.alpha, o5.beta1, o5.beta2,
-                                  x1 ? 1 : 2, grow ? 1 : 0, st);
+                rc = (route == RT_BLOCK ? block_launch : block_stream_launch)(ctx, m->blocks[op.block].w, vi, B, h, w, m->view(o5.out), other.buf >= 0 ? m->view(other) : TensorView{},
+                                                                              o5.alpha, o5.beta1, o5.beta2, x1 ? 1 : 2, grow ? 1 : 0, st);
                 break;
             }
             case RT_CHAIN: {

@@ -94,6 +94,7 @@ struct sr_ctx {
     int cu_count();               // compute units of the device (queried once)
     int chain_mask = 511;          // SR_FUSE_* bits (include/sr355.h): which fused / persistent paths sr_forward may take (sr_debug_set_fused; default all)
     int chain_max_wgs = 0;        // test hook: cap the persistent grid so that small batches still give several images per workgroup
+    int block_stream_bands = 0;   // test hook (sr_debug_set_block_stream_bands): bands per image of the streamed dense-block kernel; 0 = automatic
     int64_t alloc_cap = 0;        // test hook (sr_debug_set_alloc_cap): dalloc fails once cur_bytes would exceed it; 0 = none
     bool route_log = false;       // test hook (sr_debug_conv_routes): conv_launch appends the name of the kernel it runs to route_text
     std::string route_text;
@@ -295,6 +296,10 @@ static inline void block_free_weights(sr_ctx* ctx, BlockWeights* w) { weights_fr
 // The image must fit: sr_dense_block_lds_bytes(8, H, W) > 0.
 int block_launch(sr_ctx* ctx, const BlockWeights& w, TensorView in, int B, int H, int W, TensorView out, TensorView skip_o, float alpha, float beta1,
                  float beta2, int x_skip, int store_growth, hipStream_t st);
+// The same block, same arguments and same bits, with the image's rows streamed through a ring in LDS (dense_block_stream.hip): any H, and every W with
+// sr_dense_block_stream_lds_bytes(8, W) > 0.
+int block_stream_launch(sr_ctx* ctx, const BlockWeights& w, TensorView in, int B, int H, int W, TensorView out, TensorView skip_o, float alpha, float beta1,
+                        float beta2, int x_skip, int store_growth, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
 // attention core: o = softmax(q k^T) v per image, tokens N=H*W.

@@ -73,6 +73,10 @@ SIGNATURES = {
     "sr_debug_set_chain_stamp_buffer": (_i, [_vp, _vp, _i64]),
     "sr_debug_set_fused": (_i, [_vp, _i, _i]),
     "sr_dense_block_lds_bytes": (_i64, [_i, _i, _i]),
+    "sr_dense_block_stream_lds_bytes": (_i64, [_i, _i]),
+    "sr_dense_block_stream_bands": (_i, [_i, _i, _i, C.POINTER(C.c_int32), _i]),
+    "sr_model_set_dense_block_stream": (_i, [_vp, _i]),
+    "sr_debug_set_block_stream_bands": (_i, [_vp, _i]),
     "sr_debug_set_alloc_cap": (_i, [_vp, _i64]),
     "sr_debug_conv_routes": (_i, [_vp, _i, C.c_char_p, _i64]),
     "sr_profile_begin": (_i, [_vp]),

@@ -147,6 +147,28 @@ class Context:
         """Dynamic LDS bytes the LDS-resident dense-block kernel needs for an H x W image, or -1 where it does not apply (sr_dense_block_lds_bytes)."""
         return int(L.load().sr_dense_block_lds_bytes(int(growth_channels), int(H), int(W)))
 
+    @staticmethod
+    def dense_block_stream_lds_bytes(growth_channels, W):
+        """Dynamic LDS bytes of the streamed dense-block kernel's row ring for images W wide (any height), or -1 where it does not apply
+        (sr_dense_block_stream_lds_bytes)."""
+        return int(L.load().sr_dense_block_stream_lds_bytes(int(growth_channels), int(W)))
+
+    @staticmethod
+    def dense_block_stream_bands(B, H, num_cus):
+        """The first rows of the bands the streamed dense-block kernel cuts each of B images of H rows into on num_cus CUs (sr_dense_block_stream_bands)."""
+        lib = L.load()
+        n = int(lib.sr_dense_block_stream_bands(int(B), int(H), int(num_cus), None, 0))
+        if n < 1:
+            raise ValueError("dense_block_stream_bands: B, H and num_cus must be positive")
+        y0 = (C.c_int32 * n)()
+        if int(lib.sr_dense_block_stream_bands(int(B), int(H), int(num_cus), y0, n)) != n:
+            raise RuntimeError("sr_dense_block_stream_bands disagrees with itself")
+        return list(y0)
+
+    def set_block_stream_bands(self, n=0):
+        """Test hook: the streamed dense-block kernel cuts every image into n bands (at most its height); 0 = automatic (sr_debug_set_block_stream_bands)."""
+        self.check(self.lib.sr_debug_set_block_stream_bands(self.h, int(n)))
+
     def set_alloc_cap(self, nbytes):
         """Test hook: allocations through this context fail once it would hold more than nbytes (0 = no cap)."""
         self.check(self.lib.sr_debug_set_alloc_cap(self.h, int(nbytes)))
@@ -1682,9 +1704,10 @@ class Model:
              "esrgan_d": L.MODEL_ESRGAN_D, "vgg19_features": L.MODEL_VGG19_FEATURES}
 
     def __init__(self, kind, compute_dtype="f32", scale_factor=1, channels=3, num_blocks=0, num_filters=64,
-                 growth_channels=32, res_scaling=0.1, num_classes=2, use_attention=True, ctx=None):
+                 growth_channels=32, res_scaling=0.1, num_classes=2, use_attention=True, ctx=None, dense_block_stream=0):
         self.ctx = ctx or Context.get()
         self.kind = kind
+        self.dense_block_stream = int(dense_block_stream)
         self.compute_dtype = _DT2TORCH[dtype_code(compute_dtype)]
         cfg = L.ModelCfg(dtype_code(compute_dtype), int(scale_factor), int(channels), int(num_blocks), int(num_filters),
                          int(growth_channels), float(res_scaling), int(num_classes), int(bool(use_attention)))
@@ -1732,6 +1755,15 @@ class Model:
                 self.ctx.check(lib.sr_model_set_weight(self.h, name.encode(), which, _fptr(a), shp, a.ndim))
         self.ctx.check(lib.sr_model_finalize(self.h))
         self.finalized = True
+        if self.dense_block_stream:
+            self.set_dense_block_stream(self.dense_block_stream)
+
+    def set_dense_block_stream(self, mode):
+        """When forwards of this bf16 ESRGAN generator of 8 growth channels run a dense block as the streamed kernel dense_block_stream<bf16,g8>: 0 never (the
+        default), 1 where the LDS-resident kernel does not fit and the row ring does (48 x 48 patches), 2 wherever the ring fits (diagnostic).  ValueError for
+        any other model (sr_model_set_dense_block_stream)."""
+        self.ctx.check(self.ctx.lib.sr_model_set_dense_block_stream(self.h, int(mode)))
+        self.dense_block_stream = int(mode)
 
     def output_shape(self, B, H, W, Cx):
         s = (C.c_int64 * 4)()
