@@ -133,14 +133,16 @@ __device__ inline int gray_bgr(int b, int g, int r) { return (1868 * b + 9617 * 
 
 static inline int dtype_size(int dt) { return dt == SR_DTYPE_F32 ? 4 : (dt == SR_DTYPE_BF16 ? 2 : 1); }
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
-// fp32 -> bf16 bits on the host, as the device's conversion rounds: to nearest even, NaN stays NaN
-static inline uint16_t f32_to_bf16_host(float f) {
+// fp32 -> bf16 bits, as the device's conversion rounds: to nearest even, NaN stays NaN.  One statement for the host packers and for a device packer that
+// must make the host's bits (f32_to_bf16_host: the host packers' name for it)
+__host__ __device__ static inline uint16_t f32_to_bf16_rne(float f) {
     uint32_t u;
-    memcpy(&u, &f, 4);
+    __builtin_memcpy(&u, &f, 4);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
+static inline uint16_t f32_to_bf16_host(float f) { return f32_to_bf16_rne(f); }
 
 // Every packer's device copies: `packed` and the bias zero-padded from n to npad floats (null bias: zeros), both allocated here and both freed
 // again when anything fails; weights_free releases such a pair and nulls the two pointers.

@@ -1,9 +1,9 @@
 // dense_block_stream.hip -- a whole ESRGAN dense block at 8 growth channels as ONE kernel that streams image rows through a ring in LDS: the line-buffer
-// variant of dense_block.hip for images too large to be LDS-resident (48 x 48 patches: ESRGAN.super_resolve_image's default patch_size_lr).
+// variant of the resident kernel (dense_block_lds.h) for images too large to be LDS-resident (48 x 48 patches: ESRGAN.super_resolve_image's default patch_size_lr).
 //
 // LDS: 12 planes (plane p = channels 8 p .. 8 p + 7) of a ring of R image rows; a row is WP = 16 ceil(W / 16) + 2 sixteen-byte slots: a zero border slot, the W
 // pixels, and zeros up to the end of the last 16-pixel tile and the right border; image row y lies in ring row y mod R.  A plane is R WP slots rounded up to 16, a
-// whole number of 256-byte bank rows: the B operand of v_mfma_f32_16x16x32_bf16 is one conflict-free ds_read_b128 per lane, as in dense_block.hip.  Whole tiles
+// whole number of 256-byte bank rows: the B operand of v_mfma_f32_16x16x32_bf16 is one conflict-free ds_read_b128 per lane, as in dense_block_lds.h.  Whole tiles
 // per row make a tile's slot a constant distance from its neighbour's: one address register per (chunk, row) serves the 3 tiles x 3 horizontal taps of a wave.
 // A wave computes tiles in threes: past the last tile of a row it reads on into the next ring row or plane (finite values, results dropped), past the last
 // plane into DS_OVER spare slots.
@@ -18,8 +18,9 @@
 // weight fragments (27 KiB) stay in its registers from the first work item to the last: the 207 KiB of a block's weights are read once per workgroup, not once
 // per row.  Per row and 48 pixels: 54 + 3 * 81 MFMAs on the growth waves, 4 * 81 on the conv5 waves; waves w and w + 4 share a SIMD.
 //
-// Arithmetic is dense_block_lds.h's: per output element one fp32 accumulator chain from zero, taps outer, 32-channel chunks inner, then bias / ReLU / one
-// rounding (growth) or conv5()'s epilogue.  The result therefore has the resident kernel's bits and depends neither on the band count nor on the schedule.
+// Arithmetic is the resident kernel's: per output element one fp32 accumulator chain from zero, taps outer, 32-channel chunks inner, then the same function
+// as there: db_growth_epilogue or db_conv5_epilogue (dense_block_lds.h).  The result therefore has the resident kernel's bits and depends neither on the band
+// count nor on the schedule.
 //
 // Zeros: the ring is cleared at the start of every work item.  When a ring row is recycled for input row r + 1, its growth planes are cleared with it, and a row
 // outside the image (or outside what the band needs) is cleared in all 12 planes: a growth conv's K tail multiplies zero weights with zeros or with finished
@@ -179,8 +180,7 @@ __global__ void __launch_bounds__(DS_THREADS) dense_block_stream_kernel(StreamPa
 #pragma unroll
                             for (int j = 0; j < DS_NT; ++j) {
                                 if (q < 2 && xs[j] < W) {
-                                    f32x4 v = acc[j] + biasv;
-                                    const bf16x4 o = {(bf16_t)fmaxf(v[0], 0.f), (bf16_t)fmaxf(v[1], 0.f), (bf16_t)fmaxf(v[2], 0.f), (bf16_t)fmaxf(v[3], 0.f)};
+                                    const bf16x4 o = db_growth_epilogue(acc[j], biasv);
                                     reinterpret_cast<bf16x4*>(lds)[((8 + (k - 1)) * np + rb1 + xs[j] + 1) * 2 + q] = o;
                                     if (to_mem) *reinterpret_cast<bf16x4*>(p.grow + ((img * H + y) * 3 + 2) * (int64_t)(W * 32) + xs[j] * 32 + 8 * (k - 1) + 4 * q) = o;
                                 }
@@ -192,17 +192,7 @@ __global__ void __launch_bounds__(DS_THREADS) dense_block_stream_kernel(StreamPa
                                 if (xs[j] < W) {
                                     const int64_t e = e0 + xs[j] * 32;
                                     const bf16x4 xsk = reinterpret_cast<const bf16x4*>(lds)[((2 * nb + (q >> 1)) * np + rb1 + xs[j] + 1) * 2 + (q & 1)];
-                                    const bf16x4 os = has_so ? sov[j] : xsk;
-                                    const bf16x4 k1 = x_first ? xsk : os, k2 = x_first ? os : xsk;
-                                    f32x4 v = acc[j] + biasv;
-#pragma unroll
-                                    for (int i = 0; i < 4; ++i) {
-                                        v[i] = v[i] * alpha;
-                                        v[i] += beta1 * (float)k1[i];
-                                        if (has_so) v[i] += beta2 * (float)k2[i];
-                                    }
-                                    const bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-                                    *reinterpret_cast<bf16x4*>(p.out + e) = o;
+                                    *reinterpret_cast<bf16x4*>(p.out + e) = db_conv5_epilogue(acc[j], biasv, xsk, has_so ? sov[j] : xsk, has_so, x_first, alpha, beta1, beta2);
                                 }
                             }
                         }
@@ -248,33 +238,16 @@ int block_stream_launch(sr_ctx* ctx, const BlockWeights& w, TensorView in, int B
                         float beta2, int x_skip, int store_growth, hipStream_t st) {
     const int64_t lds = ds_lds_bytes(DB_G, W);
     if (!w.w || lds <= 0 || B <= 0 || H <= 0) return ctx->fail(SR_ERR_INVALID, "streamed dense block: the row ring does not fit (sr_dense_block_stream_lds_bytes)");
-    for (const TensorView* v : {&in, &out, &skip_o})
-        if ((v->p || v != &skip_o) && (!v->p || !v->blk || v->coff != 0 || v->cs != DB_CC))
-            return ctx->fail(SR_ERR_INVALID, "streamed dense block: needs row-blocked 96-channel concat buffers");
-    if (in.p == out.p || (x_skip != 1 && x_skip != 2) || (!skip_o.p && x_skip != 1)) return ctx->fail(SR_ERR_INVALID, "streamed dense block: bad skips or in-place output");
-    const int cus = ctx->cu_count();
-    const int nbands = ctx->block_stream_bands > 0 ? std::min(ctx->block_stream_bands, H) : ds_auto_bands(B, H, cus);
+    if (int rc = db_check_blocked_views(ctx, "streamed dense block", in, out, skip_o, x_skip)) return rc;
+    const int nbands = ctx->block_stream_bands > 0 ? std::min(ctx->block_stream_bands, H) : ds_auto_bands(B, H, ctx->cu_count());
     if ((int64_t)B * nbands >= ((int64_t)1 << 31)) return ctx->fail(SR_ERR_INVALID, "streamed dense block: too many work items");
     StreamParams p;
-    p.in = static_cast<const bf16_t*>(in.p); p.grow = static_cast<bf16_t*>(const_cast<void*>(in.p));
-    p.out = static_cast<bf16_t*>(const_cast<void*>(out.p)); p.so = static_cast<const bf16_t*>(skip_o.p);
-    p.w = static_cast<const char*>(w.w); p.bias = w.bias;
-    p.B = B; p.H = H; p.W = W;
     p.phases = ds_phases(W); p.R = ds_rows(p.phases);
-    p.np = (int)ds_plane_slots(p.R, W);
-    p.alpha = alpha; p.beta1 = beta1; p.beta2 = beta2; p.x_skip = x_skip; p.store_growth = store_growth;
+    db_fill_params(p, in.p, out.p, skip_o.p, w.w, w.bias, B, H, W, (int)ds_plane_slots(p.R, W), alpha, beta1, beta2, x_skip, store_growth);
     p.nbands = nbands; p.items = B * nbands;
-    int grid = std::min(p.items, cus);
-    if (ctx->chain_max_wgs > 0) grid = std::min(grid, ctx->chain_max_wgs);
     if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(&dense_block_stream_kernel), (int)lds)) return rc;
-    int rec = -1;
-    if (ctx->prof) {
-        const double px = (double)B * H * W;
-        double macs = 96.0 * 64.0;
-        for (int i = 0; i < 4; ++i) macs += (64.0 + DB_G * i) * DB_G;
-        rec = ctx->prof_open("dense_block_stream<bf16,g8>", 2.0 * px * 9.0 * macs, px * 2.0 * (64.0 + 64.0 + (skip_o.p ? 64.0 : 0.0) + (store_growth ? 32.0 : 0.0)), st);
-    }
-    hipLaunchKernelGGL(dense_block_stream_kernel, dim3(grid), dim3(DS_THREADS), (size_t)lds, st, p);
+    const int rec = db_prof_open(ctx, "dense_block_stream<bf16,g8>", B, H, W, 64.0 + 64.0 + (skip_o.p ? 64.0 : 0.0) + (store_growth ? 32.0 : 0.0), st);
+    hipLaunchKernelGGL(dense_block_stream_kernel, dim3(db_grid(ctx, p.items)), dim3(DS_THREADS), (size_t)lds, st, p);
     ctx->prof_close(rec, st);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;

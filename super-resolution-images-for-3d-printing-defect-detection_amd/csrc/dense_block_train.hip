@@ -1,5 +1,5 @@
-// dense_block_train.hip -- training a G = 8 dense block on the LDS-resident image of dense_block.hip: a device-side weight packer, the forward
-// kernel on a training tape's NHWC buffers and the backward kernel.  Layouts and the forward body: dense_block_lds.h.
+// dense_block_train.hip -- training a G = 8 dense block on the LDS-resident image of dense_block_lds.h: the device-side weight packer, the launcher of
+// the forward kernel on a training tape's NHWC buffers, and the backward kernel.  Layouts, the forward body and the launchers' preamble: dense_block_lds.h.
 //
 // Backward, one workgroup of 12 waves per image, persistent over images.  The 12 planes of the LDS image hold G, the gradient of the concat tensor F; nothing else of
 // size fits beside it, and nothing else is needed:
@@ -21,60 +21,30 @@ typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------------------- the packer
 struct PackPtrs { const float* k[5]; const float* b[5]; };      // one dense block: HWIO kernels [3][3][db_cin][db_cout] and biases, fp32, on the device
 
-__device__ __forceinline__ uint16_t bf16_rne_bits(float f) {       // f32_to_bf16_host on the device
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 constexpr int PACK_ITEMS = (DB_FRAGS + DBT_BFRAGS) * 64 + DB_BIAS;     // per block: a (fragment, lane) each, then a bias entry each
 
+// every item asks dense_block_lds.h's layout functions where its values come from (-1 / conv 0: a zero), as the host packer does for the forward half
 __global__ void __launch_bounds__(256) dense_block_pack_kernel(const PackPtrs* tab, u16x8* fwd, float* bias, u16x8* bwd) {
     const int t = blockIdx.x * 256 + threadIdx.x, blk = blockIdx.y;
     if (t >= PACK_ITEMS) return;
     const PackPtrs& pp = tab[blk];
     if (t >= (DB_FRAGS + DBT_BFRAGS) * 64) {
-        const int i = t - (DB_FRAGS + DBT_BFRAGS) * 64;
-        float v = 0.f;
-        if (i >= 64) v = pp.b[4][i - 64];
-        else if ((i & 15) < DB_G) v = pp.b[i >> 4][i & 15];
-        bias[(size_t)blk * DB_BIAS + i] = v;
+        const int i = t - (DB_FRAGS + DBT_BFRAGS) * 64, c = db_bias_conv(i);
+        bias[(size_t)blk * DB_BIAS + i] = c ? pp.b[c - 1][db_bias_src(i)] : 0.f;
         return;
     }
-    const int f = t >> 6, l = t & 63;
+    const int f = t >> 6, l = t & 63, g = f - DB_FRAGS;
+    const bool forward = f < DB_FRAGS;
+    const DbFrag fr = db_frag_decode(forward ? f : 0);
+    const float* kernel = pp.k[(forward ? fr.k : dbt_bfrag_conv(g)) - 1];
     u16x8 o = {};
-    if (f < DB_FRAGS) {
-        const int k = f >= DB_FRAG5 ? 5 : (f < db_frag0(2) ? 1 : 2 + (f - db_frag0(2)) / 27);
-        const int nc = db_nchunks(k), nb = k < 5 ? 1 : 4, cin = db_cin(k), cout = db_cout(k);
-        int r = f - db_frag0(k);
-        const int n = r % nb; r /= nb;
-        const int c = r % nc, tap = r / nc;
-        const int co = 16 * n + (l & 15);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int ci = 32 * c + 8 * (l >> 4) + j;
-            if (ci < cin && co < cout) o[j] = bf16_rne_bits(pp.k[k - 1][((size_t)tap * cin + ci) * cout + co]);
-        }
-        fwd[((size_t)blk * DB_FRAGS + f) * 64 + l] = o;
-        return;
+    for (int j = 0; j < 8; ++j) {
+        const int s = forward ? db_frag_src(fr, l, j) : dbt_bfrag_src(g, l, j);
+        if (s >= 0) o[j] = f32_to_bf16_rne(kernel[s]);
     }
-    const int g = f - DB_FRAGS;
-    if (g < dbt_bfrag0(1)) {
-        const int n = g % 6, c = (g / 6) & 1, tap = g / 12;
-        const int ci = 16 * n + (l & 15);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = bf16_rne_bits(pp.k[4][((size_t)(8 - tap) * DB_CC + ci) * DB_C0 + 32 * c + 8 * (l >> 4) + j]);
-    } else {
-        const int k = g < dbt_bfrag0(2) ? 1 : g < dbt_bfrag0(3) ? 2 : g < dbt_bfrag0(4) ? 3 : 4;
-        const int nb = dbt_nblocks(k), cin = db_cin(k), r = g - dbt_bfrag0(k);
-        const int n = r % nb, tap = r / nb, ci = 16 * n + l;
-        if (l < 16 && ci < cin) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = bf16_rne_bits(pp.k[k - 1][((size_t)(8 - tap) * cin + ci) * DB_G + j]);
-        }
-    }
-    bwd[((size_t)blk * DBT_BFRAGS + g) * 64 + l] = o;
+    if (forward) fwd[((size_t)blk * DB_FRAGS + f) * 64 + l] = o;
+    else bwd[((size_t)blk * DBT_BFRAGS + g) * 64 + l] = o;
 }
 
 // ------------------------------------------------------------------------------------------------------------- backward
@@ -331,18 +301,6 @@ bool view_ok(const sr_view* v, int C) {
 }
 const bf16_t* view_ptr(const sr_view* v) { return static_cast<const bf16_t*>(v->p) + v->coff; }
 
-int grid_for(sr_ctx* ctx, int B) {
-    int grid = std::min(B, ctx->cu_count());
-    if (ctx->chain_max_wgs > 0) grid = std::min(grid, ctx->chain_max_wgs);
-    return grid;
-}
-
-double block_macs() {
-    double macs = (double)DB_CC * DB_C0;
-    for (int k = 1; k < 5; ++k) macs += (double)db_cin(k) * DB_G;
-    return macs;
-}
-
 }  // namespace
 
 extern "C" {
@@ -382,19 +340,11 @@ int sr_dense_block_fwd_bf16(sr_ctx* ctx, const void* fwd_w, const float* bias, v
     if (!view_ok(out, DB_C0) || (skip2 && skip2->p && !view_ok(skip2, DB_C0))) return ctx->fail(SR_ERR_INVALID, "dense block fwd: a view needs 64 channels, cs and coff multiples of 8");
     if (out->p == F) return ctx->fail(SR_ERR_INVALID, "dense block fwd: the output may not lie in the block's own concat buffer");
     BlockParamsNHWC p;
-    p.in = static_cast<const bf16_t*>(F); p.grow = static_cast<bf16_t*>(F);
-    p.out = const_cast<bf16_t*>(view_ptr(out)); p.so = (skip2 && skip2->p) ? view_ptr(skip2) : nullptr;
-    p.w = static_cast<const char*>(fwd_w); p.bias = bias;
-    p.B = B; p.H = H; p.W = W; p.np = (int)(lds / (DB_PLANES * 16));
-    p.alpha = alpha; p.beta1 = beta1; p.beta2 = beta2; p.x_skip = 1; p.store_growth = 1;
+    db_fill_params(p, F, view_ptr(out), (skip2 && skip2->p) ? view_ptr(skip2) : nullptr, fwd_w, bias, B, H, W, (int)(lds / (DB_PLANES * 16)), alpha, beta1, beta2, 1, 1);
     p.in_cs = (int)f_cs; p.out_cs = (int)out->cs; p.so_cs = p.so ? (int)skip2->cs : 0;
     if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(&dense_block_lds_kernel<BlockParamsNHWC>), (int)lds)) return rc;
-    int rec = -1;
-    if (ctx->prof) {
-        const double px = (double)B * H * W;
-        rec = ctx->prof_open("dense_block_fwd_lds<bf16,g8,nhwc>", 2.0 * px * 9.0 * block_macs(), px * 2.0 * (64.0 + 64.0 + 32.0 + (p.so ? 64.0 : 0.0)), st);
-    }
-    hipLaunchKernelGGL(dense_block_lds_kernel<BlockParamsNHWC>, dim3(grid_for(ctx, B)), dim3(DB_THREADS), (size_t)lds, st, p);
+    const int rec = db_prof_open(ctx, "dense_block_fwd_lds<bf16,g8,nhwc>", B, H, W, 64.0 + 64.0 + 32.0 + (p.so ? 64.0 : 0.0), st);
+    hipLaunchKernelGGL(dense_block_lds_kernel<BlockParamsNHWC>, dim3(db_grid(ctx, B)), dim3(DB_THREADS), (size_t)lds, st, p);
     ctx->prof_close(rec, st);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;
@@ -419,12 +369,8 @@ int sr_dense_block_bwd_bf16(sr_ctx* ctx, const void* bwd_w, const sr_view* dY, c
     p.B = B; p.H = H; p.W = W; p.np = (int)(lds / (DB_PLANES * 16));
     p.a5 = a5; p.bx = bx;
     if (int rc = ctx->ensure_dyn_lds(reinterpret_cast<const void*>(&dense_block_bwd_kernel), (int)lds)) return rc;
-    int rec = -1;
-    if (ctx->prof) {
-        const double px = (double)B * H * W;
-        rec = ctx->prof_open("dense_block_bwd_lds<bf16,g8>", 2.0 * px * 9.0 * block_macs(), px * 2.0 * (64.0 + 64.0 + 32.0 + 32.0 + 64.0), st);
-    }
-    hipLaunchKernelGGL(dense_block_bwd_kernel, dim3(grid_for(ctx, B)), dim3(DB_THREADS), (size_t)lds, st, p);
+    const int rec = db_prof_open(ctx, "dense_block_bwd_lds<bf16,g8>", B, H, W, 64.0 + 64.0 + 32.0 + 32.0 + 64.0, st);
+    hipLaunchKernelGGL(dense_block_bwd_kernel, dim3(db_grid(ctx, B)), dim3(DB_THREADS), (size_t)lds, st, p);
     ctx->prof_close(rec, st);
     SR_HIP(ctx, hipGetLastError());
     return SR_OK;

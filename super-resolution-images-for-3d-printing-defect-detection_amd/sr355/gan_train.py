@@ -74,21 +74,28 @@ def check_dense_block_impl(value, train_dtype="bf16"):
     return value
 
 
+def trunk_blocks(num_rrdb):
+    """The trunk's dense blocks in forward order."""
+    return [f"rrdb_{b}_dense{d}" for b in range(num_rrdb) for d in (1, 2, 3)]
+
+
+def _trunk_walk(weights, num_rrdb, check):
+    """The trunk's conv layers in forward order; check(layer name, k, kernel shape) raises for the first layer that a trunk implementation cannot take."""
+    layers = [(f"{n}_conv{k}", k) for n in trunk_blocks(num_rrdb) for k in range(1, 6)]
+    for layer, k in layers:
+        check(layer, k, tuple(weights[layer][0].shape))
+    return [layer for layer, _ in layers]
+
+
 def trunk_layers_lds(weights, num_rrdb):
     """The trunk's conv layers in forward order; ValueError naming the first layer that is not a 64-channel dense block of growth width 8's (the LDS-resident kernels)."""
-    names = []
-    for b in range(num_rrdb):
-        for d in (1, 2, 3):
-            n = f"rrdb_{b}_dense{d}"
-            for k in range(1, 6):
-                want = (3, 3, 64 + 8 * (k - 1), 8 if k < 5 else 64)
-                got = tuple(weights[f"{n}_conv{k}"][0].shape)
-                if got != want:
-                    what = f"{got[3]} growth channels" if k < 5 and got[:3] == want[:3] else f"a kernel of shape {got}"
-                    raise ValueError(f"dense_block_impl='lds': {n}_conv{k} has {what}; the LDS-resident dense-block kernels take 64-channel blocks of growth width 8 "
-                                     f"(kernel {want}); train this graph with dense_block_impl='layers'")
-            names += [f"{n}_conv{k}" for k in range(1, 6)]
-    return names
+    def check(layer, k, got):
+        want = (3, 3, 64 + 8 * (k - 1), 8 if k < 5 else 64)
+        if got != want:
+            what = f"{got[3]} growth channels" if k < 5 and got[:3] == want[:3] else f"a kernel of shape {got}"
+            raise ValueError(f"dense_block_impl='lds': {layer} has {what}; the LDS-resident dense-block kernels take 64-channel blocks of growth width 8 "
+                             f"(kernel {want}); train this graph with dense_block_impl='layers'")
+    return _trunk_walk(weights, num_rrdb, check)
 
 
 def lds_patch_check(ctx, H, W):
@@ -100,20 +107,20 @@ def lds_patch_check(ctx, H, W):
 
 def trunk_layers(weights, num_rrdb):
     """The trunk's conv layers in forward order; ValueError where a dense block's growth width is not a whole number of the bf16 conv kernels' 32-channel chunks."""
-    names = []
-    for b in range(num_rrdb):
-        for d in (1, 2, 3):
-            n = f"rrdb_{b}_dense{d}"
-            for k in range(1, 5):
-                g = weights[f"{n}_conv{k}"][0].shape[3]
-                if g % 32 != 0:
-                    raise ValueError(f"train_dtype='bf16': {n}_conv{k} has {g} growth channels; the bf16 conv kernels work in chunks of 32 channels "
-                                     f"(growth_channels must be a multiple of 32; train this graph with train_dtype='f32')")
-            c0 = weights[f"{n}_conv5"][0].shape[3]
-            if c0 % 32 != 0:
-                raise ValueError(f"train_dtype='bf16': {n}_conv5 has {c0} output channels; the bf16 conv kernels work in chunks of 32 channels")
-            names += [f"{n}_conv{k}" for k in range(1, 6)]
-    return names
+    def check(layer, k, got):
+        if got[3] % 32 != 0:
+            what, hint = ("growth", " (growth_channels must be a multiple of 32; train this graph with train_dtype='f32')") if k < 5 else ("output", "")
+            raise ValueError(f"train_dtype='bf16': {layer} has {got[3]} {what} channels; the bf16 conv kernels work in chunks of 32 channels{hint}")
+    return _trunk_walk(weights, num_rrdb, check)
+
+
+def lds_pack_plan(ctx, dev, num_rrdb):
+    """(table, fwd, bias, bwd, {block name: row}): what packs the trunk's dense blocks for the LDS-resident kernels -- ctx.dense_block_pack_dev(table, fwd, bias, bwd)
+    fills the three buffers from the weights as they stand then.  dev(layer name) -> (fp32 device kernel, fp32 device bias)."""
+    names = trunk_blocks(num_rrdb)
+    layers = [[dev(f"{n}_conv{k}") for k in range(1, 6)] for n in names]
+    table = ctx.dense_block_pack_table([([k for k, _ in block], [b for _, b in block]) for block in layers])
+    return (table,) + ctx.dense_block_pack_buffers(len(names)) + ({n: i for i, n in enumerate(names)},)
 
 
 class Var:
@@ -260,205 +267,152 @@ class Tape:
         self.ops.append(bwd)
         return y
 
-    def trunk_bf16(self, x, num_rrdb, tape=None):
+    def _trunk_mixed(self, x, num_rrdb, tape, growth, forward, backward):
         """The RRDB trunk (ESRGAN_model.py:212-300: num_rrdb x three dense blocks, each RRDB closed by r_in + 0.2 * x) as ONE tape op in bf16 mixed precision
-        (DESIGN.md 3.26).  x: the fp32 output of initial_conv; returns the fp32 input of trunk_conv (a widening, exact).  Every tensor in between is bf16:
-        each kernel widens to fp32, accumulates and applies its whole epilogue in fp32 and rounds once on store.
-        Forward: F = [x | f1 | f2 | f3 | f4] is one bf16 buffer per dense block; conv k reads its channel prefix and writes slice k; conv5's epilogue
-        x + 0.2 * conv5 -- for an RRDB's third block r_in + 0.2 * (x + 0.2 * conv5), r_in being slice 0 of the RRDB's first F -- writes slice 0 of the NEXT block's F.
-        Backward, per block: G = a5 * dgrad(dY, conv5) fills a buffer of F's shape; for k = 4..2 dz_k = G slice k where F slice k > 0, G[..., :cin_k] += dgrad(dz_k)
-        in place; dX = dgrad(dz_1) + G[..., :64] + bx * dY; the five layers' weight and bias gradients by one grouped launch, written into the flat gradient
-        bucket (conv5's scaled by a5: there is no stored a5 * dY).  Per RRDB one add: d r_in = dX1 + dR.
-        With `tape` (default: the tape's `trunk_tape`) a list, every stored tensor is appended as (name, tensor) -- x0_f32 (the fp32 input), F_b_d, out, dout_f32 (the fp32 gradient
-        arriving), dR_last, then per block in reverse G_b_d_s5 / _s4 / _s3 / _s2 (G as a clone after conv5's input gradient and after each in-place accumulate),
-        dz_b_d (dz_k is channel slice k - 1), dX_b_d and per RRDB drin_b."""
+        (DESIGN.md 3.26), written once for trunk_bf16 and trunk_lds.  They say how ONE block runs: growth {block: growth width}; forward(name, F, nxt, r_in, a5, bx)
+        fills F's growth slices and nxt[..., :64] = a5 * conv5(F) + bx * F[..., :64] (+ r_in[..., :64] unless None); backward(b, d, name, F, dY, a5, bx, rec) -> (dz, dX),
+        dz_k being channel slice k - 1, and records its G stages through rec unless None.
+        x: the fp32 output of initial_conv; returns the fp32 input of trunk_conv (a widening, exact).  Every tensor in between is bf16: each kernel widens to fp32,
+        accumulates and applies its whole epilogue in fp32 and rounds once on store.  F = [x | f1 | f2 | f3 | f4] is one buffer per dense block; a block's output
+        x + 0.2 * conv5 -- for an RRDB's third block r_in + 0.2 * (x + 0.2 * conv5), r_in being slice 0 of the RRDB's first F -- is slice 0 of the NEXT block's F.
+        Backward, per block: the five layers' weight and bias gradients by one grouped launch, written into the flat gradient bucket (conv5's scaled by a5: there is
+        no stored a5 * dY).  Per RRDB one add: d r_in = dX1 + dR.
+        With `tape` (default: the tape's `trunk_tape`) a list, every stored tensor is appended as (name, tensor) -- x0_f32 (the fp32 input), F_b_d, out, dout_f32 (the
+        fp32 gradient arriving), dR_last, then per block in reverse G_b_d_s5 / _s4 / _s3 / _s2 (G after conv5's input gradient and after each in-place accumulate),
+        dz_b_d, dX_b_d and per RRDB drin_b."""
         ctx = self.ctx
-        if self.flat is None and self.wgrad:
-            raise ValueError("trunk_bf16: the weight gradients need a FlatGrads to write into")
         BF = torch.bfloat16
         B, H, W, C0 = x.v.shape
         tape = self.trunk_tape if tape is None else tape
         rec = tape.append if tape is not None else None
-        blocks = []                                             # (b, d, name, F, growth, ws, a5, bx)
-        g0 = self.w["rrdb_0_dense1_conv1"][0].shape[3]
-        F = ctx.empty((B, H, W, C0 + 4 * g0), BF)
+        note = rec or (lambda item: None)                       # here a record is a reference; a block's backward pays for its records, so it is told (rec)
+        names = trunk_blocks(num_rrdb)
+        widths = [C0 + 4 * growth[n] for n in names] + [C0]     # channels of every block's F, and of the trunk's output
+        blocks = []                                             # (b, d, name, F, a5, bx)
+        F = ctx.empty((B, H, W, widths[0]), BF)
         F[..., :C0].copy_(x.v)                                  # the one rounding of x0, into slice 0 of the first F
-        if rec:
-            rec(("x0_f32", x.v))
-        out = None
-        for b in range(num_rrdb):
-            r_in = F
-            for d in (1, 2, 3):
-                name = f"rrdb_{b}_dense{d}"
-                ws = [self.w[f"{name}_conv{k}"] for k in range(1, 6)]
-                g = ws[0][0].shape[3]
-                Ct = C0 + 4 * g
+        note(("x0_f32", x.v))
+        for i, name in enumerate(names):
+            b, d = i // 3, i % 3 + 1
+            if d == 1:
+                r_in = F
+            nxt = ctx.empty((B, H, W, widths[i + 1]), BF)
+            a5, bx = (0.2, 1.0) if d < 3 else (0.04, 0.2)       # the third block: r_in + 0.2 * (x + 0.2 * conv5) in one epilogue, one rounding
+            forward(name, F, nxt, r_in if d == 3 else None, a5, bx)
+            if self.masks is not None:
+                g = growth[name]
                 for k in range(1, 5):
-                    kk, bb = ws[k - 1]
-                    cin = C0 + (k - 1) * g
-                    ctx.conv2d_dev_view_bf16(F, 0, cin, self._dev(kk), self._dev(bb), g, F, cin, act="relu")
-                    if self.masks is not None:
-                        self.masks[f"{name}_conv{k}"] = F[..., cin:cin + g] > 0
-                last = b == num_rrdb - 1 and d == 3
-                if last:
-                    nxt = out = ctx.empty((B, H, W, C0), BF)
-                else:
-                    nn = f"rrdb_{b}_dense{d + 1}" if d < 3 else f"rrdb_{b + 1}_dense1"
-                    nxt = ctx.empty((B, H, W, C0 + 4 * self.w[f"{nn}_conv1"][0].shape[3]), BF)
-                k5, b5 = ws[4]
-                if d < 3:
-                    a5, bx = 0.2, 1.0
-                    ctx.conv2d_dev_view_bf16(F, 0, Ct, self._dev(k5), self._dev(b5), C0, nxt, 0, alpha=a5, skip1=(F, 0), beta1=bx)
-                else:                                           # r_in + 0.2 * (x + 0.2 * conv5) in one epilogue, one rounding
-                    a5, bx = 0.04, 0.2
-                    ctx.conv2d_dev_view_bf16(F, 0, Ct, self._dev(k5), self._dev(b5), C0, nxt, 0, alpha=a5, skip1=(F, 0), beta1=bx, skip2=(r_in, 0), beta2=1.0)
-                if rec:
-                    rec((f"F_{b}_{d}", F))
-                blocks.append((b, d, name, F, g, ws, a5, bx))
-                F = nxt
-        if rec:
-            rec(("out", out))
-        y = Var(out.float())
+                    self.masks[f"{name}_conv{k}"] = F[..., C0 + (k - 1) * g:C0 + k * g] > 0
+            note((f"F_{b}_{d}", F))
+            blocks.append((b, d, name, F, a5, bx))
+            F = nxt
+        note(("out", F))
+        y = Var(F.float())
 
         def bwd():
             if y.g is None:
                 return
             dR = y.g.to(BF)                                     # the one rounding of the gradient entering the trunk
-            if rec:
-                rec(("dout_f32", y.g))
-                rec((f"dR_{num_rrdb - 1}", dR))
+            note(("dout_f32", y.g))
+            note((f"dR_{num_rrdb - 1}", dR))
             dY = dR
-            for b, d, name, F, g, ws, a5, bx in reversed(blocks):
-                Ct = C0 + 4 * g
-                G = ctx.empty((B, H, W, Ct), BF)
-                ctx.conv2d_dev_view_bf16(dY, 0, C0, self._dev(ws[4][0]), None, Ct, G, 0, rot=True, alpha=a5)        # fills every channel of G
-                if rec:
-                    rec((f"G_{b}_{d}_s5", G.clone()))
-                dz = ctx.empty((B, H, W, 4 * g), BF)            # dz_k is slice k - 1
-                for k in range(4, 0, -1):
-                    kk = self._dev(ws[k - 1][0])
-                    cin = C0 + (k - 1) * g
-                    ctx.eltwise_view_bf16(L.ELT_RELU_BWD, G, cin, F, cin, dz, (k - 1) * g, g)                      # slice k of G is complete: convs k+1..5 have added to it
-                    if k > 1:
-                        ctx.conv2d_dev_view_bf16(dz, (k - 1) * g, g, kk, None, cin, G, 0, rot=True, skip1=(G, 0), beta1=1.0)       # G[..., :cin] += dgrad
-                        if rec:
-                            rec((f"G_{b}_{d}_s{k}", G.clone()))
-                    else:
-                        dX = ctx.empty((B, H, W, C0), BF)
-                        ctx.conv2d_dev_view_bf16(dz, 0, g, kk, None, C0, dX, 0, rot=True, skip1=(G, 0), beta1=1.0, skip2=(dY, 0), beta2=bx)
+            for b, d, name, F, a5, bx in reversed(blocks):
+                dz, dX = backward(b, d, name, F, dY, a5, bx, rec)
                 if self.wgrad:
+                    g, Ct = dz.shape[3] // 4, F.shape[3]
                     jobs = [(F, 0, C0 + (k - 1) * g, dz, (k - 1) * g, g, 1.0) + tuple(self.flat[f"{name}_conv{k}"]) for k in range(1, 5)]
                     jobs.append((F, 0, Ct, dY, 0, C0, a5) + tuple(self.flat[f"{name}_conv5"]))
                     ctx.conv2d_wgrad_group_bf16(jobs)
                     for k in range(1, 6):
                         self.grads[f"{name}_conv{k}"] = list(self.flat[f"{name}_conv{k}"])
-                if rec:
-                    rec((f"dz_{b}_{d}", dz))
-                    rec((f"dX_{b}_{d}", dX))
+                note((f"dz_{b}_{d}", dz))
+                note((f"dX_{b}_{d}", dX))
                 dY = dX
                 if d == 1:
                     d_rin = ctx.empty((B, H, W, C0), BF)
                     ctx.eltwise_view_bf16(L.ELT_AXPBY, dX, 0, dR, 0, d_rin, 0, C0, 1.0, 1.0)
-                    if rec:
-                        rec((f"drin_{b}", d_rin))
+                    note((f"drin_{b}", d_rin))
                     dR = dY = d_rin
             if x.need:
                 self._acc(x, dR.float())
         self.ops.append(bwd)
         return y
 
+    def trunk_bf16(self, x, num_rrdb, tape=None):
+        """_trunk_mixed with every dense block conv by conv on channel views of its concat buffer, at any growth width the bf16 conv kernels take.  Forward: conv k
+        reads its channel prefix and writes slice k.  Backward: G = a5 * dgrad(dY, conv5) fills a buffer of F's shape; for k = 4..2 dz_k = G slice k where F slice k > 0,
+        G[..., :cin_k] += dgrad(dz_k) in place; dX = dgrad(dz_1) + G[..., :64] + bx * dY.  A recorded G stage is a clone."""
+        ctx, dev = self.ctx, self._dev
+        if self.flat is None and self.wgrad:
+            raise ValueError("trunk_bf16: the weight gradients need a FlatGrads to write into")
+        C0 = x.v.shape[3]
+        growth = {n: self.w[f"{n}_conv1"][0].shape[3] for n in trunk_blocks(num_rrdb)}
+
+        def forward(name, F, nxt, r_in, a5, bx):
+            g = growth[name]
+            for k in range(1, 5):
+                kk, bb = self.w[f"{name}_conv{k}"]
+                cin = C0 + (k - 1) * g
+                ctx.conv2d_dev_view_bf16(F, 0, cin, dev(kk), dev(bb), g, F, cin, act="relu")
+            k5, b5 = self.w[f"{name}_conv5"]
+            skip2, beta2 = (None, 0.0) if r_in is None else ((r_in, 0), 1.0)
+            ctx.conv2d_dev_view_bf16(F, 0, C0 + 4 * g, dev(k5), dev(b5), C0, nxt, 0, alpha=a5, skip1=(F, 0), beta1=bx, skip2=skip2, beta2=beta2)
+
+        def backward(b, d, name, F, dY, a5, bx, rec):
+            B, H, W, Ct = F.shape
+            g = growth[name]
+            G = ctx.empty((B, H, W, Ct), F.dtype)
+            ctx.conv2d_dev_view_bf16(dY, 0, C0, dev(self.w[f"{name}_conv5"][0]), None, Ct, G, 0, rot=True, alpha=a5)       # fills every channel of G
+            if rec:
+                rec((f"G_{b}_{d}_s5", G.clone()))
+            dz = ctx.empty((B, H, W, 4 * g), F.dtype)           # dz_k is slice k - 1
+            dX = ctx.empty((B, H, W, C0), F.dtype)
+            for k in range(4, 0, -1):
+                kk = dev(self.w[f"{name}_conv{k}"][0])
+                cin = C0 + (k - 1) * g
+                ctx.eltwise_view_bf16(L.ELT_RELU_BWD, G, cin, F, cin, dz, (k - 1) * g, g)                          # slice k of G is complete: convs k+1..5 have added to it
+                if k > 1:
+                    ctx.conv2d_dev_view_bf16(dz, (k - 1) * g, g, kk, None, cin, G, 0, rot=True, skip1=(G, 0), beta1=1.0)       # G[..., :cin] += dgrad
+                    if rec:
+                        rec((f"G_{b}_{d}_s{k}", G.clone()))
+                else:
+                    ctx.conv2d_dev_view_bf16(dz, 0, g, kk, None, C0, dX, 0, rot=True, skip1=(G, 0), beta1=1.0, skip2=(dY, 0), beta2=bx)
+            return dz, dX
+        return self._trunk_mixed(x, num_rrdb, tape, growth, forward, backward)
+
     def pack_lds(self, num_rrdb):
         """(fwd, bias, bwd, {block name: row}): the trunk's dense blocks packed for the LDS-resident kernels from the tape's device weights, by one launch."""
-        ctx = self.ctx
         trunk_layers_lds(self.w, num_rrdb)
-        names = [f"rrdb_{b}_dense{d}" for b in range(num_rrdb) for d in (1, 2, 3)]
-        ws = [[self.w[f"{n}_conv{k}"] for k in range(1, 6)] for n in names]
-        table = ctx.dense_block_pack_table([([self._dev(k) for k, _ in w], [self._dev(b) for _, b in w]) for w in ws])
-        fwd, bias, bwd = ctx.dense_block_pack_buffers(len(names))
-        ctx.dense_block_pack_dev(table, fwd, bias, bwd)
-        return fwd, bias, bwd, {n: i for i, n in enumerate(names)}
+        plan = lds_pack_plan(self.ctx, lambda n: tuple(self._dev(a) for a in self.w[n]), num_rrdb)
+        self.ctx.dense_block_pack_dev(*plan[:4])
+        return plan[1:]
 
     def trunk_lds(self, x, num_rrdb, tape=None):
-        """trunk_bf16 at growth width 8 with every dense block as ONE forward and ONE backward kernel on an LDS-resident image: the same contract,
-        the same stored tensors (F per block, dz, dX) and the same grouped weight-gradient launch; G, the gradient of F, never reaches HBM.  `tape` as in
-        trunk_bf16; the G_b_d_s* stages are recorded only with `trunk_stages` (the kernel's stage dump; channels >= cin_k of stage k hold dz already selected)."""
+        """_trunk_mixed at growth width 8 with every dense block as ONE forward and ONE backward kernel on an LDS-resident image: the same contract,
+        the same stored tensors (F per block, dz, dX) and the same grouped weight-gradient launch; G, the gradient of F, never reaches HBM.  `tape` as there; the
+        G_b_d_s* stages are recorded only with `trunk_stages` (the kernel's stage dump; channels >= cin_k of stage k hold dz already selected)."""
         ctx = self.ctx
         if self.flat is None and self.wgrad:
             raise ValueError("trunk_lds: the weight gradients need a FlatGrads to write into")
-        BF = torch.bfloat16
-        B, H, W, C0 = x.v.shape
-        lds_patch_check(ctx, H, W)
+        lds_patch_check(ctx, x.v.shape[1], x.v.shape[2])
         fwd, bias, bwd, row = self.lds_packs if self.lds_packs is not None else self.pack_lds(num_rrdb)
-        tape = self.trunk_tape if tape is None else tape
-        rec = tape.append if tape is not None else None
-        g, Ct = 8, C0 + 32
-        blocks = []                                             # (b, d, name, F, a5, bx)
-        F = ctx.empty((B, H, W, Ct), BF)
-        F[..., :C0].copy_(x.v)                                  # the one rounding of x0, into slice 0 of the first F
-        if rec:
-            rec(("x0_f32", x.v))
-        out = None
-        for b in range(num_rrdb):
-            r_in = F
-            for d in (1, 2, 3):
-                name = f"rrdb_{b}_dense{d}"
-                i = row[name]
-                last = b == num_rrdb - 1 and d == 3
-                nxt = ctx.empty((B, H, W, C0 if last else Ct), BF)
-                if d < 3:
-                    a5, bx = 0.2, 1.0
-                    ctx.dense_block_fwd_bf16(fwd[i], bias[i], F, nxt, alpha=a5, beta1=bx)
-                else:                                           # r_in + 0.2 * (x + 0.2 * conv5) in one epilogue, one rounding
-                    a5, bx = 0.04, 0.2
-                    ctx.dense_block_fwd_bf16(fwd[i], bias[i], F, nxt, skip2=(r_in, 0), alpha=a5, beta1=bx, beta2=1.0)
-                if self.masks is not None:
-                    for k in range(1, 5):
-                        self.masks[f"{name}_conv{k}"] = F[..., C0 + (k - 1) * g:C0 + k * g] > 0
-                if rec:
-                    rec((f"F_{b}_{d}", F))
-                blocks.append((b, d, name, F, a5, bx))
-                F = nxt
-        out = F
-        if rec:
-            rec(("out", out))
-        y = Var(out.float())
 
-        def bwd_op():
-            if y.g is None:
-                return
-            dR = y.g.to(BF)                                     # the one rounding of the gradient entering the trunk
-            if rec:
-                rec(("dout_f32", y.g))
-                rec((f"dR_{num_rrdb - 1}", dR))
-            dY = dR
-            for b, d, name, F, a5, bx in reversed(blocks):
-                dz = ctx.empty((B, H, W, 4 * g), BF)            # dz_k is slice k - 1
-                dX = ctx.empty((B, H, W, C0), BF)
-                stages = ctx.empty((4, B, H, W, Ct), BF) if rec and self.trunk_stages else None
-                ctx.dense_block_bwd_bf16(bwd[row[name]], dY, F, a5, bx, dz, dX, stages=stages)
-                if stages is not None:
-                    for j, k in enumerate((5, 4, 3, 2)):
-                        rec((f"G_{b}_{d}_s{k}", stages[j]))
-                if self.wgrad:
-                    jobs = [(F, 0, C0 + (k - 1) * g, dz, (k - 1) * g, g, 1.0) + tuple(self.flat[f"{name}_conv{k}"]) for k in range(1, 5)]
-                    jobs.append((F, 0, Ct, dY, 0, C0, a5) + tuple(self.flat[f"{name}_conv5"]))
-                    ctx.conv2d_wgrad_group_bf16(jobs)
-                    for k in range(1, 6):
-                        self.grads[f"{name}_conv{k}"] = list(self.flat[f"{name}_conv{k}"])
-                if rec:
-                    rec((f"dz_{b}_{d}", dz))
-                    rec((f"dX_{b}_{d}", dX))
-                dY = dX
-                if d == 1:
-                    d_rin = ctx.empty((B, H, W, C0), BF)
-                    ctx.eltwise_view_bf16(L.ELT_AXPBY, dX, 0, dR, 0, d_rin, 0, C0, 1.0, 1.0)
-                    if rec:
-                        rec((f"drin_{b}", d_rin))
-                    dR = dY = d_rin
-            if x.need:
-                self._acc(x, dR.float())
-        self.ops.append(bwd_op)
-        return y
+        def forward(name, F, nxt, r_in, a5, bx):
+            i = row[name]
+            skip2, beta2 = (None, 0.0) if r_in is None else ((r_in, 0), 1.0)
+            ctx.dense_block_fwd_bf16(fwd[i], bias[i], F, nxt, skip2=skip2, alpha=a5, beta1=bx, beta2=beta2)
+
+        def backward(b, d, name, F, dY, a5, bx, rec):
+            B, H, W, Ct = F.shape
+            dz = ctx.empty((B, H, W, 32), F.dtype)              # dz_k is slice k - 1
+            dX = ctx.empty((B, H, W, Ct - 32), F.dtype)
+            stages = ctx.empty((4, B, H, W, Ct), F.dtype) if rec and self.trunk_stages else None
+            ctx.dense_block_bwd_bf16(bwd[row[name]], dY, F, a5, bx, dz, dX, stages=stages)
+            if stages is not None:
+                for j, k in enumerate((5, 4, 3, 2)):
+                    rec((f"G_{b}_{d}_s{k}", stages[j]))
+            return dz, dX
+        return self._trunk_mixed(x, num_rrdb, tape, dict.fromkeys(trunk_blocks(num_rrdb), 8), forward, backward)
 
     def axpby(self, a, b, alpha, beta):
         y = Var(self.ctx.eltwise(L.ELT_AXPBY, a.v, b.v, alpha, beta))
@@ -943,10 +897,8 @@ class ESRGANTrainer:
         # what the taped training pass stores inside the RRDB trunk (Tape.trunk_bf16 / trunk_lds); refused before anything is uploaded or launched
         self.train_dtype = check_train_dtype(train_dtype)
         self.dense_block_impl = check_dense_block_impl(dense_block_impl, train_dtype)
-        if self.dense_block_impl == "lds":
-            self._trunk = set(trunk_layers_lds(g_weights, num_rrdb))
-        else:
-            self._trunk = set(trunk_layers(g_weights, num_rrdb)) if train_dtype == "bf16" else set()
+        walk = trunk_layers_lds if self.dense_block_impl == "lds" else trunk_layers
+        self._trunk = set(walk(g_weights, num_rrdb)) if train_dtype == "bf16" else set()
         self.attention_impl = check_attention_impl(attention_impl)      # the generator tape's SelfAttention core (Tape.attention)
         self.ctx, self.scale, self.nb, self.att = ctx, scale, num_rrdb, attention
         self.discriminator = discriminator
@@ -1004,9 +956,7 @@ class ESRGANTrainer:
             uses16 = [u for n in dev if n in self._trunk for u in ((dev[n][0], dev[n][1], False), (dev[n][0], None, True))] if trunk16 else []
             self._packs[key16] = self.ctx.pack_list(uses16 + (self._perc16.pack_uses(*hr_shape) if vgg16 else []))
         if lds and "lds" not in self._packs:                  # dense_block_impl="lds": the trunk's blocks as fragments of the LDS-resident kernels, in buffers of the trainer's
-            dev, names = self.g_params.dev, [f"rrdb_{b}_dense{d}" for b in range(self.nb) for d in (1, 2, 3)]
-            table = self.ctx.dense_block_pack_table([([dev[f"{n}_conv{k}"][0] for k in range(1, 6)], [dev[f"{n}_conv{k}"][1] for k in range(1, 6)]) for n in names])
-            self._packs["lds"] = (table,) + self.ctx.dense_block_pack_buffers(len(names)) + ({n: i for i, n in enumerate(names)},)
+            self._packs["lds"] = lds_pack_plan(self.ctx, self.g_params.dev.__getitem__, self.nb)
         self.ctx.conv_prepack(self._packs[with_vgg])
         if lds:
             self.ctx.dense_block_pack_dev(*self._packs["lds"][:4])     # ... rounded to bf16 once per step, by one launch
